@@ -3,9 +3,14 @@
 (BASELINE.json metric; body of reference evaluate_models_utils.py:126-141) on the Wikipedia-shaped
 synthetic workload of SURVEY.md §8(d): L=64, P=2, batch 200, 2 layers, 2 heads, C=50.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (with the roofline of the timed launches).
+--dump-outputs DIR writes what the last timed step returned (embeddings, link probabilities, ROC AUC) as DIR/<name>.npy;
+the inputs are seeded, so two builds can be compared output for output.  Everything else the benchmark measures (the
+CPU baseline, parity, stages and secondary workloads below; `secondary.lastfm` at N>1) runs only with --full.
 
 One step = one 200-edge batch: hot-path call on (src,dst,t) + hot-path call on (src,neg_dst,t) +
 sigmoid(MergeLayer) on both + the per-step ROC AUC on the device; the per-rank metric sums are all-reduced over RCCL
@@ -14,11 +19,11 @@ Inputs (graph, feature tables, weights, every batch's id/time arrays) are reside
 timed region.  N>1: one process per GPU, graph/tables/weights replicated, whole batches dealt
 round-robin (dyglib_amd.distributed.shard_batch_indices: rank r takes batches r, r+N, ...: weak
 scaling, K steps per rank), no data-path collective; the synthetic graph is generated once per node (local rank 0 ->
-/dev/shm -> the other ranks).  At N>1 the line also carries `secondary.lastfm`: BASELINE config 4's workload (L=512,
+/dev/shm -> the other ranks).  At N>1 with --full the line also carries `secondary.lastfm`: BASELINE config 4's workload (L=512,
 P=8) sharded over the N ranks the same way.  Rank 0 prints ONE JSON line.
 DYGNN_BENCH_FORCE_DIST=1 sets the process group up at world size 1 too (RCCL rehearsal on a one-GPU box).
 
-Besides the contract fields the line carries (rank 0, N = 1):
+With --full the line also carries (rank 0, N = 1):
   parity     the GPU outputs of the timed steps the CPU leg replays, against the oracle: full-size config-1 parity
              observed by whoever runs this file; the process exits non-zero above the 1e-4 bar of BASELINE.json;
   stages     neighbour-lookup rate (bytes by SURVEY §8d's formula), device metrics, `per_call`: the drop-in rate of
@@ -177,7 +182,7 @@ class DygformerWorkload:
 def run_dygformer(wk: DygformerWorkload, steps: int, warmup: int, F: int, rank: int, world: int, dist, n_streams: int = 1, keep: int = 0, prime: int = 12) -> dict:
     """K timed steps of this rank in launches of F steps (the positive and negative calls of F consecutive steps = 2F
     independently padded groups of B pairs form ONE grid).  Returns throughput, the per-launch duration of the hot-path
-    call from HIP events recorded on its stream, and the device outputs of the first `keep` timed steps."""
+    call from HIP events recorded on its stream, the device outputs of the first `keep` timed steps and those of the last timed launch."""
     from dyglib_amd import link_prediction_metrics_device
     dev, B = wk.dev, wk.B
     # batches of this rank, round-robin over the ranks (dyglib_amd/distributed.py), cycled when the run is longer than the span
@@ -187,9 +192,9 @@ def run_dygformer(wk: DygformerWorkload, steps: int, warmup: int, F: int, rank: 
     streams = [torch.cuda.Stream(dev) for _ in range(n_streams)] if n_streams > 1 else [torch.cuda.current_stream(dev)]
     metric_accs = [torch.zeros(3, dtype=torch.float64, device=dev) for _ in streams]     # per stream: [sum AUC, sum mean-prob gap, steps]
     labels_full = torch.cat([torch.ones(F, B), torch.zeros(F, B)], dim=1).to(dev)         # evaluate_models_utils.py:143
-    kept = []
+    kept, last = [], []
 
-    def launch(idx: torch.Tensor, li: int, ev=None, keep_out: bool = False):
+    def launch(idx: torch.Tensor, li: int, ev=None, keep_out: bool = False, keep_last: bool = False):
         """the steps `idx` (batch numbers) as ONE hot-path launch of 2*len(idx) groups"""
         nsteps = idx.numel()
         st = streams[li % len(streams)]
@@ -215,12 +220,15 @@ def run_dygformer(wk: DygformerWorkload, steps: int, warmup: int, F: int, rank: 
             metric_accs[li % len(streams)].add_(m)               # per-rank sums; ONE all-reduce after the timed region (SURVEY §8e needs only the totals)
             if keep_out:
                 kept.append((s, d, prob))
+            if keep_last:
+                last.append((s, d, prob, auc))
 
-    def run_steps(first: int, count: int, evs=None, keep_steps: int = 0):
+    def run_steps(first: int, count: int, evs=None, keep_steps: int = 0, keep_last: bool = False):
         li, done = 0, 0
         while done < count:
             n = min(F, count - done)
-            launch(order[first + done:first + done + n], li, None if evs is None else evs[li], keep_out=done < keep_steps)
+            launch(order[first + done:first + done + n], li, None if evs is None else evs[li], keep_out=done < keep_steps,
+                   keep_last=keep_last and done + n == count)
             done += n
             li += 1
 
@@ -247,7 +255,7 @@ def run_dygformer(wk: DygformerWorkload, steps: int, warmup: int, F: int, rank: 
             e.record(streams[0])
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    run_steps(warmup, steps, events, keep_steps=keep)
+    run_steps(warmup, steps, events, keep_steps=keep, keep_last=True)
     sync_all()
     elapsed = time.perf_counter() - t0
     acc_dev = metric_accs[0] if len(metric_accs) == 1 else torch.stack(metric_accs).sum(dim=0)
@@ -271,7 +279,7 @@ def run_dygformer(wk: DygformerWorkload, steps: int, warmup: int, F: int, rank: 
     acc = acc_dev.cpu().numpy()
     return dict(elapsed=elapsed, value=steps * B * world / elapsed, launch_ms=launch_ms, call_ms=call_ms, steps_per_launch=sizes[0], n_launch=n_launch,
                 timed_launches=len(full), mean_auc=float(acc[0] / max(acc[2], 1)), metric_steps=int(round(acc[2])), metric_allreduce_ms=reduce_ms,
-                kept=kept, order=order_h[warmup:warmup + steps], streams=len(streams))
+                kept=kept, last=last[0], order=order_h[warmup:warmup + steps], streams=len(streams))
 
 
 def dygformer_roofline(wk: DygformerWorkload, res: dict, impl: int) -> dict:
@@ -897,13 +905,30 @@ def parse_args():
                     help="upper bound of the steps per launch: the positive and negative calls of F consecutive steps (2F independently "
                          "padded groups of `batch` pairs) form ONE grid; F = min(this, steps/2) so that at least two launches are timed")
     ap.add_argument("--prime-launches", type=int, default=12, help="untimed launches of the timed shape before the warm-up steps (clock / cache ramp)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="wall budget of the headline CPU-baseline sample (0 = skip CPU legs and parity)")
-    ap.add_argument("--secondary", default="lastfm,tgat,tgn,train", help="comma list of secondary workloads to run at N=1 ('' or 'none' = skip)")
-    ap.add_argument("--full-span-oracle", action="store_true", help="stages.full_span: recompute ALL 237 batches' AP / AUC with the CPU oracle (~1 min)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: wall budget of the headline CPU-baseline sample (0 = skip CPU legs and parity)")
+    ap.add_argument("--secondary", default="lastfm,tgat,tgn,train", help="--full: comma list of secondary workloads to run at N=1 ('' or 'none' = skip)")
+    ap.add_argument("--full-span-oracle", action="store_true", help="--full: stages.full_span recomputes ALL 237 batches' AP / AUC with the CPU oracle (~1 min)")
     ap.add_argument("--sharded-secondary", default="lastfm", choices=["lastfm", "tiny", "none"],
-                    help="N > 1: workload that is also run sharded over the N ranks and printed as secondary.<name> (BASELINE config 4 = lastfm)")
-    ap.add_argument("--budget-seconds", type=float, default=105.0, help="wall budget of the whole run: secondary CPU samples shrink to fit")
+                    help="N > 1 with --full: workload that is also run sharded over the N ranks and printed as secondary.<name> (BASELINE config 4 = lastfm)")
+    ap.add_argument("--budget-seconds", type=float, default=105.0, help="--full: wall budget of the whole run: secondary CPU samples shrink to fit")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: stages, CPU baseline + parity, secondary workloads (N>1: the sharded secondary)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (rank 0) as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
+
+
+def dump_outputs(res: dict, out_dir: str) -> None:
+    """What a caller of the timed path receives for the LAST timed step: row n-1 (positive call) and row 2n-1 (negative call) of the
+    last launch of n steps — node embeddings, link probabilities, and the step's ROC AUC."""
+    s, d, prob, auc = res["last"]
+    n = prob.shape[1]
+    arrays = {"src_node_embeddings": s[n - 1], "dst_node_embeddings": d[n - 1],
+              "neg_src_node_embeddings": s[2 * n - 1], "neg_dst_node_embeddings": d[2 * n - 1],
+              "positive_probabilities": prob[0, n - 1], "negative_probabilities": prob[1, n - 1], "roc_auc": auc[n - 1:]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():                  # float32 embeddings / probabilities, float64 AUC
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().cpu().numpy())
 
 
 def main():
@@ -945,8 +970,11 @@ def main():
     B, L, P = wk.B, wk.L, wk.P
     F = max(1, min(args.fuse_steps, args.steps // 2 if args.steps >= 2 else 1))
     solo = rank == 0 and world == 1
-    keep = min(args.steps, 64) if solo and args.cpu_seconds > 0 else 0
+    keep = min(args.steps, 64) if solo and args.full and args.cpu_seconds > 0 else 0
     res = run_dygformer(wk, args.steps, args.warmup, F, rank, world, dist, args.streams, keep=keep, prime=args.prime_launches)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res, args.dump_outputs)
+    res["last"] = None
 
     out = {
         "metric": "edges/sec (link-prediction fwd) DyGFormer " + WORKLOAD_LABEL[args.workload],
@@ -968,7 +996,7 @@ def main():
         if res["metric_steps"] != args.steps * world:
             raise SystemExit(f"metric all-reduce counted {res['metric_steps']} steps, expected {args.steps * world}")
     failed = False
-    if world > 1 and args.sharded_secondary != "none":
+    if world > 1 and args.full and args.sharded_secondary != "none":
         # BASELINE config 4 is defined at N GPUs: the LastFM-shaped workload (L=512, P=8) sharded exactly like the headline, every rank K' steps
         del wk
         torch.cuda.empty_cache()
@@ -982,7 +1010,7 @@ def main():
             "config": {"workload": wk2.describe()}, "roofline": dygformer_roofline(wk2, res2, args.impl), "mean_auc": round(res2["mean_auc"], 4),
             "metric_allreduce": {"ms": round(res2["metric_allreduce_ms"], 3), "steps_counted": res2["metric_steps"]}}}
         del wk2
-    if solo:
+    if solo and args.full:
         out["stages"] = sampler_stage(wk.sampler, wk.data, dev)           # stage-level number for the neighbour lookup
         out["stages"].update(metrics_stage(dev))
         out["stages"].update(per_call_stage(wk))
@@ -1015,6 +1043,7 @@ def main():
                     out["secondary"][name] = {"error": f"{type(e).__name__}: {e}"}
                     failed = True
                 torch.cuda.empty_cache()
+    if solo:
         out["wall_s"] = round(time.perf_counter() - T_START, 1)
     if dist is not None:
         dist.destroy_process_group()

@@ -1,5 +1,6 @@
 #!/bin/bash
-# end-of-round run: GPU tests, smoke(), the driver's bench command (-> r03_bench_end_of_round.json), bench.py with no flags, the LastFM workload stand-alone
+# end-of-round run: GPU tests, smoke(), the driver's bench command (-> r03_bench_end_of_round.json), bench.py at default sizes, the LastFM workload stand-alone;
+# every bench run with --full (CPU baseline, parity, stages, secondary workloads)
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$ROOT"
@@ -7,9 +8,9 @@ O=gpurun_out/final; mkdir -p $O
 timeout -k 10 700 python3 -m pytest tests -m gpu -x -q > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
 timeout -k 10 200 python3 __graft_entry__.py smoke 2>&1 | tail -2
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/r03_bench_end_of_round.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
-timeout -k 10 300 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
-timeout -k 10 300 python3 bench.py --workload lastfm --steps 16 --warmup 8 --fuse-steps 8 --secondary none > $O/bench_lastfm.json 2> $O/bench_lastfm.err || { tail -20 $O/bench_lastfm.err; exit 1; }
+timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r03_bench_end_of_round.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
+timeout -k 10 300 python3 bench.py --workload lastfm --steps 16 --warmup 8 --fuse-steps 8 --secondary none --full > $O/bench_lastfm.json 2> $O/bench_lastfm.err || { tail -20 $O/bench_lastfm.err; exit 1; }
 python3 - <<'P'
 import json
 for f in ("r03_bench_end_of_round","bench_default","bench_lastfm"):
