@@ -538,7 +538,7 @@ static TgatPlan make_tgat_plan(const dygnn_tgat_config& c, int64_t B) {
     return p;
 }
 
-static int check_tgat(const dygnn_tgat_config* c) {
+int check_tgat(const dygnn_tgat_config* c) {      // (also the training path's check, tgat_train.hip)
     DYGNN_REQUIRE(c != nullptr, "tgat: config is NULL");
     DYGNN_REQUIRE(c->node_feat_dim > 0 && c->edge_feat_dim > 0 && c->time_feat_dim > 0, "tgat: feature dims must be positive");
     DYGNN_REQUIRE(c->node_feat_dim % 4 == 0 && c->edge_feat_dim % 4 == 0 && c->time_feat_dim % 4 == 0, "tgat: feature dims must be multiples of 4");
@@ -551,6 +551,21 @@ static int check_tgat(const dygnn_tgat_config* c) {
     DYGNN_REQUIRE(c->num_neighbors <= 64, "tgat: num_neighbors > 64 not supported");
     DYGNN_REQUIRE(c->node_feat_dim + c->time_feat_dim <= 16 * 17, "tgat: node_feat_dim + time_feat_dim > 272 not supported");
     DYGNN_REQUIRE(((c->node_feat_dim + c->time_feat_dim) / c->num_heads) % 4 == 0, "tgat: head dim must be a multiple of 4");
+    return DYGNN_OK;
+}
+
+// The level sets of one call WITHOUT de-duplication, into caller-owned arrays (the training path, tgat_train.hip): level L = [src ; dst] at
+// the batch times, level l-1 = [level l ; its k most recent neighbours].  ids / tms [l] for l = 0..L-1, eid / dt [l] for l = 1..L.
+int tgat_expand_levels(hipStream_t s, const dygnn_csr* csr, const int64_t* src, const int64_t* dst, const double* times, int64_t B, int L, int k,
+                       int32_t* const* ids, double* const* tms, int32_t* const* eid, float* const* dt) {
+    int64_t n = 2 * B;
+    for (int l = L; l >= 1; --l, n *= 1 + k) {
+        const bool top = l == L;
+        hipLaunchKernelGGL(k_tgat_expand, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, s, csr->indptr, csr->nbr, csr->eid, csr->ts, csr->num_nodes,
+                           top ? nullptr : ids[l], top ? nullptr : tms[l], n, k, ids[l - 1], tms[l - 1], eid[l], dt[l], (const int32_t*)nullptr,
+                           top ? src : nullptr, top ? dst : nullptr, top ? times : nullptr, B, TgnTouch{}, 0);
+        DYGNN_LAUNCH_CHECK();
+    }
     return DYGNN_OK;
 }
 

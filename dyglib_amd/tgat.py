@@ -1,11 +1,18 @@
 """Drop-in for the reference `TGAT` backbone (models/TGAT.py:9-147): same constructor, same
 `compute_src_dst_node_temporal_embeddings(src_node_ids, dst_node_ids, node_interact_times, num_neighbors)` /
 `compute_node_temporal_embeddings` / `set_neighbor_sampler` signatures, same parameter names (state_dict
-compatible); the forward runs in libdygnn_hip.so (`dygnn_tgat_forward`).  Inference only, `recent` sampling."""
+compatible); the forward runs in libdygnn_hip.so (`dygnn_tgat_forward`, or `dygnn_tgat_forward_levels` for the random sampling
+strategies, whose draws are replayed on the host).
+
+Inference (no_grad) runs the de-duplicated level-set forward.  In training mode with autograd recording the call goes through
+`_TgatTrainFunction`: the training forward of tgat_train.hip (every level entry its own row, dropout from a counter-based generator,
+activations kept in a per-call workspace) and its hand-written backward pass, so `loss.backward()` / `optimizer.step()` of
+train_link_prediction.py:170-185, :242-257 work unchanged.  Eval mode with autograd recording raises NotImplementedError (the result
+would have no graph)."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -14,6 +21,55 @@ import torch.nn as nn
 from . import _capi
 from .modules import MergeLayer, TimeEncoder
 from .neighbor_sampler import NeighborSampler
+
+
+class _TgatTrainFunction(torch.autograd.Function):
+    """compute_src_dst_node_temporal_embeddings with gradients: forward = dygnn_tgat_train_forward, backward = dygnn_tgat_backward.  The
+    parameters are passed as inputs only so that autograd routes their gradients; the workspace belongs to this one call (a training step
+    issues a positive and a negative call before one backward())."""
+
+    @staticmethod
+    def forward(ctx, model, src, dst, tms, num_neighbors, dropout_p, seed, levels, *params):
+        dev = src.device
+        B = src.numel()
+        lib = model._lib
+        cfg, w = model._config_and_weights(num_neighbors)
+        nbytes = lib.dygnn_tgat_train_workspace_bytes(C.byref(cfg), B)
+        if nbytes == 0:
+            _capi.check(-3)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)          # lives until this call's backward
+        out = (torch.empty((B, model.node_feat_dim), dtype=torch.float32, device=dev), torch.empty((B, model.node_feat_dim), dtype=torch.float32, device=dev))
+        lv = C.byref(levels[0]) if levels is not None else None
+        csr = None if levels is not None else model.neighbor_sampler.csr.on_device(dev)
+        _capi.check(lib.dygnn_tgat_train_forward(C.byref(cfg), C.byref(w), csr, lv, model.node_raw_features.data_ptr(),
+                                                 model.edge_raw_features.data_ptr(), src.data_ptr(), dst.data_ptr(), tms.data_ptr(), B,
+                                                 float(dropout_p), int(seed), out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), nbytes,
+                                                 _capi.current_stream_ptr()))
+        ctx.model, ctx.cfg, ctx.w, ctx.ws, ctx.B, ctx.dropout_p, ctx.seed = model, cfg, w, ws, B, float(dropout_p), int(seed)
+        ctx.feats = (model.node_raw_features, model.edge_raw_features)        # read again by the backward pass
+        ctx.levels = levels                                                    # the level tensors outlive the asynchronous copies
+        ctx.param_versions = [(p.data_ptr(), p._version) for p in params]
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_src, g_dst):
+        model = ctx.model
+        dev = ctx.ws.device
+        g_src = (g_src if g_src is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
+        g_dst = (g_dst if g_dst is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
+        params = model._param_list()
+        # the backward pass re-reads the CURRENT parameter values: they must be the ones the forward used
+        if [(p.data_ptr(), p._version) for p in params] != ctx.param_versions:
+            raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
+                               "a TGAT parameter changed between this call's forward and its backward")
+        sizes = [p.numel() for p in params]
+        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)       # one fill for all gradient buffers
+        grads = [g.view_as(p) for g, p in zip(flat.split(sizes), params)]
+        gstruct = model._weights_struct({id(p): g for p, g in zip(params, grads)})
+        _capi.check(model._lib.dygnn_tgat_backward(C.byref(ctx.cfg), C.byref(ctx.w), C.byref(gstruct), g_src.data_ptr(), g_dst.data_ptr(), ctx.B,
+                                                   ctx.dropout_p, ctx.seed, ctx.ws.data_ptr(), ctx.ws.numel(), _capi.current_stream_ptr()))
+        ctx.ws = ctx.levels = ctx.feats = None
+        return (None,) * 8 + tuple(grads)
 
 
 class MultiHeadAttention(nn.Module):
@@ -66,11 +122,13 @@ class TGAT(nn.Module):
 
     def compute_src_dst_node_temporal_embeddings(self, src_node_ids, dst_node_ids, node_interact_times,
                                                  num_neighbors: int = 20) -> Tuple[torch.Tensor, torch.Tensor]:
-        """models/TGAT.py:48-64: two float32 tensors [B, node_feat_dim] on the model's device."""
-        if torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters())):
+        """models/TGAT.py:48-64: two float32 tensors [B, node_feat_dim] on the model's device.  With autograd recording in training
+        mode the call is differentiable (_TgatTrainFunction; dropout `self.dropout`)."""
+        train = torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters()))
+        if train and not self.training:
             # eval mode with autograd recording would return tensors without a graph: loss.backward() would silently do nothing
-            raise NotImplementedError("TGAT forward with autograd recording (training) is not built on the HIP path (SURVEY.md §8f-1): "
-                                      "call it under torch.no_grad()")
+            raise NotImplementedError("TGAT forward with autograd recording in eval mode is not built on the HIP path: call it under "
+                                      "torch.no_grad(), or use model.train() (with model.dropout = 0.0 for dropout-free gradients)")
         random_strategy = self.neighbor_sampler.sample_neighbor_strategy != "recent"
         self.neighbor_sampler._check_strategy()
         dev = self.merge_layers[0].fc1.weight.device
@@ -90,6 +148,12 @@ class TGAT(nn.Module):
         src, dst, tms = to_dev(src_node_ids, torch.int64), to_dev(dst_node_ids, torch.int64), to_dev(node_interact_times, torch.float64)
         B = src.numel()
         assert dst.numel() == B and tms.numel() == B
+        if train and B > 0:
+            p_drop, seed = self._dropout_and_seed()
+            levels = None
+            if random_strategy:       # the RandomState is consumed exactly as by an inference call
+                levels = self._sample_levels_host(src.cpu().numpy(), dst.cpu().numpy(), tms.cpu().numpy(), int(num_neighbors), dev)
+            return _TgatTrainFunction.apply(self, src, dst, tms, int(num_neighbors), p_drop, seed, levels, *self._param_list())
         out = torch.empty((2, B, self.node_feat_dim), dtype=torch.float32, device=dev)      # one block: the library writes it in place
         out_src, out_dst = out[0], out[1]
         if B == 0:
@@ -127,8 +191,9 @@ class TGAT(nn.Module):
         if self.neighbor_sampler.sample_neighbor_strategy != "recent":
             raise NotImplementedError("compute_step_embeddings: `recent` sampling only; issue the two calls of the reference for the random strategies")
         if torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("TGAT forward with autograd recording (training) is not built on the HIP path (SURVEY.md §8f-1): "
-                                      "call it under torch.no_grad()")
+            # inference only: sharing the source rows would share their dropout masks, which the reference's two training calls do not
+            raise NotImplementedError("compute_step_embeddings is inference-only: call it under torch.no_grad(), or issue the two "
+                                      "compute_src_dst_node_temporal_embeddings calls of the reference for training")
         dev = self.merge_layers[0].fc1.weight.device
         if dev.type != "cuda":
             raise _capi.DygnnError("dyglib_amd.TGAT runs on an MI355X only; there is no CPU fallback")
@@ -172,15 +237,33 @@ class TGAT(nn.Module):
 
     def _config_and_weights(self, num_neighbors: int):
         cfg = _capi.TgatConfig(self.node_feat_dim, self.edge_feat_dim, self.time_feat_dim, self.num_layers, self.num_heads, int(num_neighbors))
+        return cfg, self._weights_struct()
+
+    def _weights_struct(self, replace: Optional[dict] = None) -> "_capi.TgatWeights":
+        """ctypes view of the parameters of the first self.num_layers layers; `replace` maps id(parameter) to another tensor of the same shape
+        (the gradient buffers of the backward pass)."""
+        p = (lambda t: t.data_ptr()) if replace is None else (lambda t: replace[id(t)].data_ptr())
         w = _capi.TgatWeights()
-        w.time_w, w.time_b = self.time_encoder.w.weight.data_ptr(), self.time_encoder.w.bias.data_ptr()
+        w.time_w, w.time_b = p(self.time_encoder.w.weight), p(self.time_encoder.w.bias)
         for l in range(self.num_layers):
             a, m, L = self.temporal_conv_layers[l], self.merge_layers[l], w.layers[l]
-            L.query_w, L.key_w, L.value_w = a.query_projection.weight.data_ptr(), a.key_projection.weight.data_ptr(), a.value_projection.weight.data_ptr()
-            L.ln_w, L.ln_b = a.layer_norm.weight.data_ptr(), a.layer_norm.bias.data_ptr()
-            L.res_w, L.res_b = a.residual_fc.weight.data_ptr(), a.residual_fc.bias.data_ptr()
-            L.fc1_w, L.fc1_b, L.fc2_w, L.fc2_b = m.fc1.weight.data_ptr(), m.fc1.bias.data_ptr(), m.fc2.weight.data_ptr(), m.fc2.bias.data_ptr()
-        return cfg, w
+            L.query_w, L.key_w, L.value_w = p(a.query_projection.weight), p(a.key_projection.weight), p(a.value_projection.weight)
+            L.ln_w, L.ln_b = p(a.layer_norm.weight), p(a.layer_norm.bias)
+            L.res_w, L.res_b = p(a.residual_fc.weight), p(a.residual_fc.bias)
+            L.fc1_w, L.fc1_b, L.fc2_w, L.fc2_b = p(m.fc1.weight), p(m.fc1.bias), p(m.fc2.weight), p(m.fc2.bias)
+        return w
+
+    def _param_list(self):
+        return list(self.parameters())
+
+    def _dropout_and_seed(self):
+        for p in self._param_list():
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise _capi.DygnnError("parameters must be contiguous float32")
+        seed = getattr(self, "_fixed_dropout_seed", None)             # tests pin the masks; normally torch.manual_seed governs them
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        return (float(self.dropout) if self.training else 0.0), seed
 
     def compute_node_temporal_embeddings(self, node_ids, node_interact_times, current_layer_num: int, num_neighbors: int = 20) -> torch.Tensor:
         """models/TGAT.py:66-136: the embedding of `node_ids` at `node_interact_times` after `current_layer_num` layers ([n, node_feat_dim]).

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """End-to-end miniature of the reference's train_link_prediction.py on the HIP path, with synthetic dataset files in the
 reference's on-disk format: load (`get_link_prediction_data`), build the two samplers (train graph / full graph,
-train_link_prediction.py:40-45), train DyGFormer + MergeLayer with Adam on BCE (:229-257), evaluate AP / AUC on the
+train_link_prediction.py:40-45), train DyGFormer (or TGAT, --model TGAT) + MergeLayer with Adam on BCE (:229-257), evaluate AP / AUC on the
 validation split with the fused inference kernel (evaluate_models_utils.py:49-152).  One process per GPU under
 torch.distributed.run averages gradients with one flat RCCL all-reduce per step.
 
@@ -18,7 +18,7 @@ import torch
 import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dyglib_amd import DyGFormer, MergeLayer, get_link_prediction_data, get_neighbor_sampler, synthetic as syn  # noqa: E402
+from dyglib_amd import TGAT, DyGFormer, MergeLayer, get_link_prediction_data, get_neighbor_sampler, synthetic as syn  # noqa: E402
 from dyglib_amd import distributed as D  # noqa: E402
 
 
@@ -42,6 +42,8 @@ def main():
     ap.add_argument("--items", type=int, default=60)
     ap.add_argument("--edges", type=int, default=20000)
     ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--model", choices=("DyGFormer", "TGAT"), default="DyGFormer")
+    ap.add_argument("--num-neighbors", type=int, default=20, help="TGAT: neighbours sampled per node and layer")
     args = ap.parse_args()
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -56,8 +58,24 @@ def main():
     node_feat, edge_feat, full, train, val, test, nn_val, nn_test = get_link_prediction_data("toy", 0.15, 0.15, root=root)
     train_sampler = get_neighbor_sampler(train, "recent", seed=0, device=dev)
     full_sampler = get_neighbor_sampler(full, "recent", seed=1, device=dev)
-    model = DyGFormer(node_feat, edge_feat, train_sampler, time_feat_dim=100, channel_embedding_dim=50, patch_size=1, num_layers=2,
-                      num_heads=2, dropout=0.1, max_input_sequence_length=32, device=dev).to(dev)
+    if args.model == "TGAT":
+        model = TGAT(node_feat, edge_feat, train_sampler, time_feat_dim=100, num_layers=2, num_heads=2, dropout=0.1, device=dev).to(dev)
+    else:
+        model = DyGFormer(node_feat, edge_feat, train_sampler, time_feat_dim=100, channel_embedding_dim=50, patch_size=1, num_layers=2,
+                          num_heads=2, dropout=0.1, max_input_sequence_length=32, device=dev).to(dev)
+
+    def embed_pairs(src, dst, neg, t):
+        """(src, dst) and (src, neg) embeddings of a step: DyGFormer's two calls as one set; TGAT issues the reference's two calls
+        (train_link_prediction.py:170-185) -- in evaluation as one call whose source rows serve both (compute_step_embeddings)"""
+        if args.model == "TGAT":
+            if not torch.is_grad_enabled():
+                es, ed, en = model.compute_step_embeddings(src, dst, neg, t, num_neighbors=args.num_neighbors)
+                return es, ed, es, en
+            ps, pd = model.compute_src_dst_node_temporal_embeddings(src, dst, t, num_neighbors=args.num_neighbors)
+            ns, nd = model.compute_src_dst_node_temporal_embeddings(src, neg, t, num_neighbors=args.num_neighbors)
+            return ps, pd, ns, nd
+        s2, d2 = model.compute_src_dst_node_temporal_embeddings_many(np.stack([src, src]), np.stack([dst, neg]), np.stack([t, t]))
+        return s2[0], d2[0], s2[1], d2[1]
     merge = MergeLayer(172, 172, 172, 1).to(dev)
     params = list(model.parameters()) + list(merge.parameters())
     opt = torch.optim.Adam(params, lr=args.lr)
@@ -76,8 +94,8 @@ def main():
             src, dst, t = split.src_node_ids[sl], split.dst_node_ids[sl], split.node_interact_times[sl]
             neg = ers.choice(items, size=len(src))
             with torch.no_grad():
-                es, ed = model.compute_src_dst_node_temporal_embeddings_many(np.stack([src, src]), np.stack([dst, neg]), np.stack([t, t]))
-                prob = merge.link_probabilities(es.flatten(0, 1), ed.flatten(0, 1))
+                ps, pd, ns, nd = embed_pairs(src, dst, neg, t)
+                prob = merge.link_probabilities(torch.cat([ps, ns]), torch.cat([pd, nd]))
             return prob[:len(src)], prob[len(src):]
         return D.evaluate_sharded(step, nb, rank, world, device=dev)
 
@@ -92,8 +110,7 @@ def main():
             src, dst, t = train.src_node_ids[sl], train.dst_node_ids[sl], train.node_interact_times[sl]
             neg = rs.choice(train_items, size=len(src))
             # the positive and the negative call of the step (train_link_prediction.py:229-239) as one set: one dense pass when they pad alike
-            s2, d2 = model.compute_src_dst_node_temporal_embeddings_many(np.stack([src, src]), np.stack([dst, neg]), np.stack([t, t]))
-            ps, pd, ns, nd = s2[0], d2[0], s2[1], d2[1]
+            ps, pd, ns, nd = embed_pairs(src, dst, neg, t)
             pos, ng = merge(ps, pd).squeeze(-1).sigmoid(), merge(ns, nd).squeeze(-1).sigmoid()
             return torch.nn.functional.binary_cross_entropy(torch.cat([pos, ng]), torch.cat([torch.ones_like(pos), torch.zeros_like(ng)]))
         # every rank takes ceil(nb / world) optimizer steps; a rank without a batch joins the gradient all-reduce with zeros

@@ -350,6 +350,27 @@ int dygnn_dygformer_backward(const dygnn_dygformer_config* cfg_host, const dygnn
                              int64_t batch, float dropout_p, uint64_t seed, const int32_t* seq_lens_host,
                              void* workspace, size_t workspace_bytes, const void* packed, dygnn_stream_t stream);
 
+/* TGAT training (models/TGAT.py:48-136 in TRAIN mode, trained by train_link_prediction.py:170-185, :242-257).
+ * dygnn_tgat_train_forward: the forward of dygnn_tgat_forward (`levels` == NULL: `recent` sampling on csr from src / dst / times) or of
+ * dygnn_tgat_forward_levels (`levels` given: host-replayed random draws; csr / src / dst / times may be NULL), with dropout (probability
+ * dropout_p) on the attention probabilities and on the residual_fc output (models/modules.py:187, :196), masks drawn from a counter-based
+ * generator keyed by `seed` (dropout_p = 0 reproduces the eval forward).  Every level entry is computed as its own row (the reference's
+ * recursion, no de-duplication).  `workspace` (size from dygnn_tgat_train_workspace_bytes) holds every activation the backward pass reads
+ * and belongs to ONE call: it, node_feat and edge_feat must stay untouched until dygnn_tgat_backward of the same call returns.
+ * dygnn_tgat_backward: `grads` has the layout of dygnn_tgat_weights, its pointers are WRITABLE device buffers of the parameter shapes that
+ * MUST BE ZERO on entry (the reductions accumulate into them); on return each holds
+ * d(sum(out_src*grad_out_src) + sum(out_dst*grad_out_dst))/dparam.  The feature tables receive no gradient (constants in the reference,
+ * models/TGAT.py:26-27).  Configurations: those dygnn_tgat_forward takes with node_feat_dim + edge_feat_dim + time_feat_dim <= 1024
+ * (else DYGNN_E_UNSUPPORTED). */
+size_t dygnn_tgat_train_workspace_bytes(const dygnn_tgat_config* cfg_host, int64_t batch);
+int dygnn_tgat_train_forward(const dygnn_tgat_config* cfg_host, const dygnn_tgat_weights* w_host, const dygnn_csr* csr_host,
+                             const dygnn_tgat_levels* levels_host, const float* node_feat, const float* edge_feat,
+                             const int64_t* src, const int64_t* dst, const double* times, int64_t batch, float dropout_p, uint64_t seed,
+                             float* out_src, float* out_dst, void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
+int dygnn_tgat_backward(const dygnn_tgat_config* cfg_host, const dygnn_tgat_weights* w_host, const dygnn_tgat_weights* grads_host,
+                        const float* grad_out_src, const float* grad_out_dst, int64_t batch, float dropout_p, uint64_t seed,
+                        void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
+
 /* Caller-side link predictor, fused: sigmoid(MergeLayer(a,b)) with
  * MergeLayer = fc2(relu(fc1(cat(a,b)))) (models/modules.py:57-68; evaluate_models_utils.py:140-141).
  * a,b [n,dim]; fc1 [hidden, 2*dim]; fc2 [1,hidden]; out [n]. */
