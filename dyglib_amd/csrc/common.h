@@ -17,6 +17,25 @@ constexpr int kWave = 64;   // CDNA4 wavefront
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// First index p in [lo, hi) with ts[p] >= t, or hi (np.searchsorted side='left' on an ascending CSR row).  A 64-ary search: every step the
+// wave probes 64 evenly spaced timestamps and one ballot+popcount picks the sub-range.  All 64 lanes must call (uniform lo/hi/t).
+__device__ __forceinline__ int64_t wave_lower_bound(const double* __restrict__ ts, int64_t lo, int64_t hi, double t, int lane) {
+    while (hi - lo > kWave) {
+        const int64_t step = (hi - lo + kWave - 1) / kWave;
+        const int64_t p = lo + (int64_t)lane * step;
+        const bool pred = (p < hi) && (ts[p] < t);
+        const int c = __popcll(__ballot(pred));      // rows ascend => pred is true exactly for lanes < c
+        if (c == 0) return lo;
+        const int64_t nlo = lo + (int64_t)(c - 1) * step + 1;
+        const int64_t nhi = lo + (int64_t)c * step;
+        hi = nhi < hi ? nhi : hi;
+        lo = nlo;
+    }
+    const int64_t p = lo + lane;
+    const bool pred = (p < hi) && (ts[p] < t);
+    return lo + __popcll(__ballot(pred));
+}
+
 }  // namespace dygnn
 
 #define DYGNN_REQUIRE(cond, ...)                                  \

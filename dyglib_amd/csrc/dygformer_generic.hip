@@ -71,24 +71,6 @@ __global__ void k_call_dims(CallDims* cds, int P, int64_t ngroups) {
 
 struct CsrView2 { const int64_t* indptr; const int32_t* nbr; const int32_t* eid; const double* ts; int64_t num_nodes; };
 
-// 64-ary wave search, see sampler.hip
-__device__ __forceinline__ int64_t wave_lower_bound2(const double* __restrict__ ts, int64_t lo, int64_t hi, double t, int lane) {
-    while (hi - lo > kWave) {
-        const int64_t step = (hi - lo + kWave - 1) / kWave;
-        const int64_t p = lo + (int64_t)lane * step;
-        const bool pred = (p < hi) && (ts[p] < t);
-        const int c = __popcll(__ballot(pred));
-        if (c == 0) return lo;
-        const int64_t nlo = lo + (int64_t)(c - 1) * step + 1;
-        const int64_t nhi = lo + (int64_t)c * step;
-        hi = nhi < hi ? nhi : hi;
-        lo = nlo;
-    }
-    const int64_t p = lo + lane;
-    const bool pred = (p < hi) && (ts[p] < t);
-    return lo + __popcll(__ballot(pred));
-}
-
 // queries 0..B-1 = src side, B..2B-1 = dst side
 __global__ __launch_bounds__(256) void k_window_lengths2(CsrView2 g, const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
                                                            const double* __restrict__ times, int64_t B, int64_t G, int32_t L,
@@ -101,7 +83,7 @@ __global__ __launch_bounds__(256) void k_window_lengths2(CsrView2 g, const int64
     int64_t node = is_dst ? dst[r] : src[r];
     if (node < 0 || node >= g.num_nodes) node = 0;
     const int64_t lo = g.indptr[node], hi = g.indptr[node + 1];
-    const int64_t i = wave_lower_bound2(g.ts, lo, hi, times[r], lane);
+    const int64_t i = wave_lower_bound(g.ts, lo, hi, times[r], lane);
     if (lane == 0) {
         const int32_t len = (int32_t)(i - lo);
         hist_len[q] = len;

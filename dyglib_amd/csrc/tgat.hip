@@ -13,29 +13,12 @@
 #include "gemm.h"
 #include "tgat_chain.h"
 #include "tgat_attn.h"
+#include "tgat_levels.h"
 
 namespace dygnn {
 
 using f4 = __attribute__((ext_vector_type(4))) float;
 __device__ __forceinline__ f4 tmfma(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// sampler kernel shared with sampler.hip (one wave per query, 64-ary search)
-__device__ __forceinline__ int64_t wave_lower_bound3(const double* __restrict__ ts, int64_t lo, int64_t hi, double t, int lane) {
-    while (hi - lo > kWave) {
-        const int64_t step = (hi - lo + kWave - 1) / kWave;
-        const int64_t p = lo + (int64_t)lane * step;
-        const bool pred = (p < hi) && (ts[p] < t);
-        const int c = __popcll(__ballot(pred));
-        if (c == 0) return lo;
-        const int64_t nlo = lo + (int64_t)(c - 1) * step + 1;
-        const int64_t nhi = lo + (int64_t)c * step;
-        hi = nhi < hi ? nhi : hi;
-        lo = nlo;
-    }
-    const int64_t p = lo + lane;
-    const bool pred = (p < hi) && (ts[p] < t);
-    return lo + __popcll(__ballot(pred));
-}
 
 // level expansion: for the n nodes of a level (ids/times), sample the k most recent neighbours (utils/utils.py:200-209)
 // and append them to the next-lower level: lower = [this level ; neighbours (row-major n x k)].
@@ -64,7 +47,7 @@ __global__ __launch_bounds__(256) void k_tgat_expand(const int64_t* __restrict__
     if (node < 0 || node >= num_nodes) node = 0;
     const double t = src ? tq[(per_root || q < B) ? q : q - B] : times[q];
     const int64_t lo = indptr[node], hi = indptr[node + 1];
-    const int64_t i = wave_lower_bound3(cts, lo, hi, t, lane);
+    const int64_t i = wave_lower_bound(cts, lo, hi, t, lane);
     const int64_t len = i - lo;
     const int m = (int)(len < k ? len : k), pad = k - m;
     if (lane == 0) {
@@ -554,17 +537,57 @@ int check_tgat(const dygnn_tgat_config* c) {      // (also the training path's c
     return DYGNN_OK;
 }
 
-// The level sets of one call WITHOUT de-duplication, into caller-owned arrays (the training path, tgat_train.hip): level L = [src ; dst] at
-// the batch times, level l-1 = [level l ; its k most recent neighbours].  ids / tms [l] for l = 0..L-1, eid / dt [l] for l = 1..L.
-int tgat_expand_levels(hipStream_t s, const dygnn_csr* csr, const int64_t* src, const int64_t* dst, const double* times, int64_t B, int L, int k,
-                       int32_t* const* ids, double* const* tms, int32_t* const* eid, float* const* dt) {
-    int64_t n = 2 * B;
+int check_layer_weights(const dygnn_tgat_weights* w, int L, const char* what) {
+    for (int l = 0; l < L; ++l) {
+        const dygnn_tgat_layer_weights& Lw = w->layers[l];
+        DYGNN_REQUIRE(Lw.query_w && Lw.key_w && Lw.value_w && Lw.ln_w && Lw.ln_b && Lw.res_w && Lw.res_b && Lw.fc1_w && Lw.fc1_b && Lw.fc2_w && Lw.fc2_b,
+                      "%s (layer %d)", what, l);
+    }
+    return DYGNN_OK;
+}
+
+int copy_levels(hipStream_t s, const dygnn_tgat_levels* lv, int L, int k, const int64_t* n, int id_levels, const LevelBufs& to, const char* what) {
+    for (int l = 0; l <= L; ++l)
+        DYGNN_REQUIRE((l >= id_levels || lv->ids[l]) && (l == 0 || (lv->nbr_eid[l] && lv->nbr_dt[l])), "%s: null level array (level %d)", what, l);
+    for (int l = 0; l <= L; ++l) {
+        if (l < id_levels) DYGNN_HIP(hipMemcpyAsync(to.ids[l], lv->ids[l], (size_t)n[l] * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        if (l >= 1) {
+            DYGNN_HIP(hipMemcpyAsync(to.eid[l], lv->nbr_eid[l], (size_t)n[l] * k * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+            DYGNN_HIP(hipMemcpyAsync(to.dt[l], lv->nbr_dt[l], (size_t)n[l] * k * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
+    }
+    return DYGNN_OK;
+}
+
+// the de-duplication of level 1 (see k_dedup_insert): hash slots, representative / compact index / map per entry, the compact level
+struct DedupBufs {
+    int32_t *slots, *canon, *cidx, *map, *count, *ids;
+    double* times;
+    uint32_t cap;
+};
+
+int expand_levels(hipStream_t s, const dygnn_csr* csr, const TgatRoots& r, int L, int k, const LevelBufs& to, const DedupBufs* dd, const TgnTouch* touch) {
+    int64_t n = 2 * r.B;
     for (int l = L; l >= 1; --l, n *= 1 + k) {
         const bool top = l == L;
+        const bool d1 = dd && l == 1;             // level 1 is expanded from its distinct entries only
         hipLaunchKernelGGL(k_tgat_expand, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, s, csr->indptr, csr->nbr, csr->eid, csr->ts, csr->num_nodes,
-                           top ? nullptr : ids[l], top ? nullptr : tms[l], n, k, ids[l - 1], tms[l - 1], eid[l], dt[l], (const int32_t*)nullptr,
-                           top ? src : nullptr, top ? dst : nullptr, top ? times : nullptr, B, TgnTouch{}, 0);
+                           d1 ? dd->ids : to.ids[l], d1 ? dd->times : to.times[l], n, k, to.ids[l - 1], to.times[l - 1], to.eid[l], to.dt[l],
+                           d1 ? dd->count : (const int32_t*)nullptr, top ? r.src : nullptr, top ? r.dst : nullptr, top ? r.times : nullptr, r.B,
+                           touch && l == 1 ? *touch : TgnTouch{}, r.per_root ? 1 : 0);
         DYGNN_LAUNCH_CHECK();
+        if (dd && l == 2) {                       // level 1 is complete: find its distinct (node, time) entries
+            const int64_t n1 = n * (1 + k);
+            DYGNN_HIP(hipMemsetAsync(dd->slots, 0xFF, (size_t)dd->cap * sizeof(int32_t), s));
+            DYGNN_HIP(hipMemsetAsync(dd->count, 0, sizeof(int32_t), s));
+            hipLaunchKernelGGL(k_dedup_insert, dim3((unsigned)ceil_div(n1, 256)), dim3(256), 0, s, to.ids[1], to.times[1], n1, dd->slots, dd->cap - 1, dd->canon);
+            DYGNN_LAUNCH_CHECK();
+            hipLaunchKernelGGL(k_dedup_number, dim3((unsigned)ceil_div(n1, 1024)), dim3(1024), 0, s, to.ids[1], to.times[1], dd->canon, n1, dd->count, dd->cidx,
+                               dd->ids, dd->times);
+            DYGNN_LAUNCH_CHECK();
+            hipLaunchKernelGGL(k_dedup_map, dim3((unsigned)ceil_div(n1, 256)), dim3(256), 0, s, dd->canon, dd->cidx, n1, dd->map);
+            DYGNN_LAUNCH_CHECK();
+        }
     }
     return DYGNN_OK;
 }
@@ -588,80 +611,76 @@ extern "C" size_t dygnn_tgat_workspace_bytes(const dygnn_tgat_config* cfg, int64
 }
 
 namespace dygnn {
+// Distinct entries of level 1 are computed once (see k_dedup_insert): only when the library samples itself (`recent` is a function of
+// (node, time); pre-sampled random levels draw independently per entry) and the pair attention kernel, which knows the row map, applies.
+// Decided once per library call, by its entry point.
 static bool tgat_dedup_active(const TgatPlan& p, bool presampled) {
     const char* dd_env = getenv("DYGNN_TGAT_DEDUP");                 // "0" switches it off (read per call: the A/B switch of tests/test_tgat.py)
     const bool dedup_on = !(dd_env && dd_env[0] == '0');
     return dedup_on && !presampled && p.L == 2 && p.k <= 20 && p.H <= 2 && p.Dkv <= 512;
 }
-static int tgat_forward_impl(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_csr* csr, const float* node_feat,
-                             const float* edge_feat, const int64_t* src, const int64_t* dst, const double* times, int64_t batch,
-                             float* out_src, float* out_dst, void* workspace, size_t workspace_bytes, dygnn_stream_t stream,
-                             const dygnn_tgat_levels* levels = nullptr, bool levels_in_workspace = false, bool expand_only = false,
-                             const TgnTouch* touch = nullptr, bool packed = false, bool times_per_root = false, bool presampled = false) {
+// The argument checks of a TGAT / TGN inference call.  `levels` given: the caller's pre-sampled levels (copy_levels checks them), csr and the
+// roots are not read.
+static int check_tgat_args(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_csr* csr, const dygnn_tgat_levels* levels,
+                           const float* node_feat, const float* edge_feat, const TgatRoots& r, const float* out_src, const float* out_dst,
+                           const void* workspace, size_t workspace_bytes) {
     if (int rc = check_tgat(cfg)) return rc;
     DYGNN_REQUIRE(w && w->time_w && w->time_b, "tgat: null weights");
-    DYGNN_REQUIRE(levels || levels_in_workspace || (csr && csr->indptr && csr->num_nodes >= 1), "tgat: bad csr");
-    DYGNN_REQUIRE(batch >= 0 && node_feat && edge_feat, "tgat: bad arguments");
-    if (batch == 0) return DYGNN_OK;
-    DYGNN_REQUIRE((levels || levels_in_workspace || (src && dst && times)) && out_src && out_dst && workspace, "tgat: null pointer");
-    const TgatPlan p = make_tgat_plan(*cfg, batch);
-    if (workspace_bytes < p.total) {
-        set_error("tgat: workspace too small (%zu < %zu bytes)", workspace_bytes, p.total);
+    DYGNN_REQUIRE(levels || (csr && csr->indptr && csr->num_nodes >= 1), "tgat: bad csr");
+    DYGNN_REQUIRE(r.B >= 0 && node_feat && edge_feat, "tgat: bad arguments");
+    if (r.B == 0) return DYGNN_OK;
+    DYGNN_REQUIRE((levels || (r.src && r.dst && r.times)) && out_src && out_dst && workspace, "tgat: null pointer");
+    const size_t need = make_tgat_plan(*cfg, r.B).total;
+    if (workspace_bytes < need) {
+        set_error("tgat: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
         return DYGNN_E_WORKSPACE;
     }
-    for (int l = 0; l < p.L; ++l) {
-        const dygnn_tgat_layer_weights& Lw = w->layers[l];
-        DYGNN_REQUIRE(Lw.query_w && Lw.key_w && Lw.value_w && Lw.ln_w && Lw.ln_b && Lw.res_w && Lw.res_b && Lw.fc1_w && Lw.fc1_b && Lw.fc2_w && Lw.fc2_b,
-                      "tgat: null layer weights (layer %d)", l);
-    }
-    hipStream_t s = as_stream(stream);
-    char* ws = static_cast<char*>(workspace);
-    auto I32 = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
-    auto F64 = [&](size_t off) { return reinterpret_cast<double*>(ws + off); };
-    auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    // Distinct entries of level 1 are computed once (see k_dedup_insert): only when the library samples itself (`recent` is a function of
-    // (node, time); pre-sampled random levels draw independently per entry) and the pair attention kernel, which knows the row map, applies.
-    const bool dedup = tgat_dedup_active(p, levels != nullptr || presampled);
+    return check_layer_weights(w, cfg->num_layers, "tgat: null layer weights");
+}
 
-    if (levels_in_workspace) {
-        // the caller ran this function's own expansion on this workspace already (TGN: it needs the level-0 node set before the features exist)
-    } else if (levels) {
-        // pre-sampled levels (random strategies): copy them where the sampling kernels would have written them
-        for (int l = 0; l <= p.L; ++l) {
-            DYGNN_REQUIRE(levels->ids[l] && (l == 0 || (levels->nbr_eid[l] && levels->nbr_dt[l])), "tgat: null level array (level %d)", l);
-            DYGNN_HIP(hipMemcpyAsync(I32(p.ids[l]), levels->ids[l], (size_t)p.n[l] * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-            if (l >= 1) {
-                DYGNN_HIP(hipMemcpyAsync(I32(p.eid[l]), levels->nbr_eid[l], (size_t)p.n[l] * p.k * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-                DYGNN_HIP(hipMemcpyAsync(F32(p.dt[l]), levels->nbr_dt[l], (size_t)p.n[l] * p.k * sizeof(float), hipMemcpyDeviceToDevice, s));
-            }
-        }
-    } else {
-    // top-down: sample neighbours of every level, building the level below; level L = [src ; dst] is read from the caller's arrays
-    for (int l = p.L; l >= 1; --l) {
-        const bool dd = dedup && l == 1;          // level 1 is expanded from its distinct entries only
-        const bool top = l == p.L;
-        const bool tch = touch && l == 1;
-        hipLaunchKernelGGL(k_tgat_expand, dim3((unsigned)ceil_div(p.n[l], 4)), dim3(256), 0, s, csr->indptr, csr->nbr, csr->eid, csr->ts, csr->num_nodes,
-                           dd ? I32(p.dd_ids) : I32(p.ids[l]), dd ? F64(p.dd_times) : F64(p.times[l]), p.n[l], p.k, I32(p.ids[l - 1]), F64(p.times[l - 1]),
-                           I32(p.eid[l]), F32(p.dt[l]), dd ? I32(p.dd_count) : (const int32_t*)nullptr, top ? src : nullptr, top ? dst : nullptr,
-                           top ? times : nullptr, batch, tch ? *touch : TgnTouch{}, times_per_root ? 1 : 0);
+// What the level stage and the layer stage of one call share
+struct TgatStages {
+    const TgatPlan& p;
+    char* ws;             // the call's TgatPlan workspace
+    hipStream_t s;
+    bool dedup;           // tgat_dedup_active
+};
+
+// Level stage: the level arrays of the call in its workspace, sampled from the graph (`recent`) or copied from the caller's `levels`.
+// touch (TGN): every level-0 slot names itself owner of its node.
+static int tgat_levels(const TgatStages& c, const dygnn_csr* csr, const TgatRoots& roots, const dygnn_tgat_levels* levels, const TgnTouch* touch) {
+    const TgatPlan& p = c.p;
+    auto I32 = [&](size_t off) { return reinterpret_cast<int32_t*>(c.ws + off); };
+    auto F64 = [&](size_t off) { return reinterpret_cast<double*>(c.ws + off); };
+    auto F32 = [&](size_t off) { return reinterpret_cast<float*>(c.ws + off); };
+    LevelBufs to{};
+    for (int l = 0; l <= p.L; ++l) {
+        to.ids[l] = I32(p.ids[l]); to.times[l] = F64(p.times[l]);
+        if (l >= 1) { to.eid[l] = I32(p.eid[l]); to.dt[l] = F32(p.dt[l]); }
+    }
+    if (!levels) {
+        const DedupBufs dd{I32(p.dd_slots), I32(p.dd_canon), I32(p.dd_cidx), I32(p.dd_map), I32(p.dd_count), I32(p.dd_ids), F64(p.dd_times), p.dd_cap};
+        return expand_levels(c.s, csr, roots, p.L, p.k, to, c.dedup ? &dd : nullptr, touch);
+    }
+    // pre-sampled levels (random strategies): copied where the sampling kernels would have written them
+    if (int rc = copy_levels(c.s, levels, p.L, p.k, p.n, p.L + 1, to, "tgat")) return rc;
+    if (touch) {
+        hipLaunchKernelGGL(k_tgn_touch_levels, dim3((unsigned)ceil_div(p.n[0], 256)), dim3(256), 0, c.s, to.ids[0], p.n[1], p.k, *touch);
         DYGNN_LAUNCH_CHECK();
-        if (dedup && l == 2) {                    // level 1 is complete: find its distinct (node, time) entries
-            const int64_t n1 = p.n[1];
-            DYGNN_HIP(hipMemsetAsync(I32(p.dd_slots), 0xFF, (size_t)p.dd_cap * sizeof(int32_t), s));
-            DYGNN_HIP(hipMemsetAsync(I32(p.dd_count), 0, sizeof(int32_t), s));
-            hipLaunchKernelGGL(k_dedup_insert, dim3((unsigned)ceil_div(n1, 256)), dim3(256), 0, s, I32(p.ids[1]), F64(p.times[1]), n1, I32(p.dd_slots), p.dd_cap - 1,
-                               I32(p.dd_canon));
-            DYGNN_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_dedup_number, dim3((unsigned)ceil_div(n1, 1024)), dim3(1024), 0, s, I32(p.ids[1]), F64(p.times[1]), I32(p.dd_canon), n1, I32(p.dd_count),
-                               I32(p.dd_cidx), I32(p.dd_ids), F64(p.dd_times));
-            DYGNN_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_dedup_map, dim3((unsigned)ceil_div(n1, 256)), dim3(256), 0, s, I32(p.dd_canon), I32(p.dd_cidx), n1, I32(p.dd_map));
-            DYGNN_LAUNCH_CHECK();
-        }
     }
-    }
-    if (expand_only) return DYGNN_OK;
+    return DYGNN_OK;
+}
+
+// Layer stage: layers 1..L, bottom-up, on the levels in the workspace, into out_src / out_dst.  packed (TGN): the caller has packed the layer
+// weights into the workspace's row-block fragments, and the layers run as chains.
+static int tgat_layers(const TgatStages& c, const dygnn_tgat_weights* w, const float* node_feat, const float* edge_feat, float* out_src, float* out_dst,
+                       bool packed) {
+    const TgatPlan& p = c.p;
+    const hipStream_t s = c.s;
+    const bool dedup = c.dedup;
+    const int64_t B = p.n[p.L] / 2;
+    auto I32 = [&](size_t off) { return reinterpret_cast<int32_t*>(c.ws + off); };
+    auto F32 = [&](size_t off) { return reinterpret_cast<float*>(c.ws + off); };
     // bottom-up: layer l turns level-(l-1) embeddings (raw features for l = 1) into level-l embeddings
     const float scale = (float)pow((double)p.hd, -0.5);
     // Two forms of a layer.  Row-block chains (tgat_chain.hip; three launches, intermediates in LDS): every workgroup streams the layer's
@@ -686,7 +705,7 @@ static int tgat_forward_impl(const dygnn_tgat_config* cfg, const dygnn_tgat_weig
         const int32_t* nl = dedup && l == 1 ? I32(p.dd_count) : nullptr;       // layer 1 runs over the distinct level-1 entries (count on the device)
         const int32_t* lmap = dedup && l == 2 ? I32(p.dd_map) : nullptr;       // layer 2 finds an entry's layer-1 row through the map
         // the top level is [src rows ; dst rows]: when the caller's two outputs are one [2B, Fn] block it is written in place
-        const bool direct = l == p.L && out_dst == out_src + (size_t)batch * p.Fn;
+        const bool direct = l == p.L && out_dst == out_src + (size_t)B * p.Fn;
         float* h_out = direct ? out_src : F32(p.h[l]);
         float* cq = F32(p.cq) + (size_t)(l - 1) * (p.Dq + p.Ft);
         float* ct = cq + p.Dq;
@@ -762,9 +781,21 @@ static int tgat_forward_impl(const dygnn_tgat_config* cfg, const dygnn_tgat_weig
         if (int rc = gemm_nt<false>(F32(p.hid), Lw.fc2_w, Lw.fc2_b, h_out, n, p.Fn, p.Fn, p.Fn, s, nl)) return rc;
         if (direct) return DYGNN_OK;
     }
-    hipLaunchKernelGGL(k_split_out, dim3((unsigned)ceil_div(2 * batch * p.Fn, 256)), dim3(256), 0, s, F32(p.h[p.L]), batch, p.Fn, out_src, out_dst);
+    hipLaunchKernelGGL(k_split_out, dim3((unsigned)ceil_div(2 * B * p.Fn, 256)), dim3(256), 0, s, F32(p.h[p.L]), B, p.Fn, out_src, out_dst);
     DYGNN_LAUNCH_CHECK();
     return DYGNN_OK;
+}
+
+// dygnn_tgat_forward, _forward_roots and _forward_levels
+static int tgat_forward(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_csr* csr, const dygnn_tgat_levels* levels,
+                        const float* node_feat, const float* edge_feat, const TgatRoots& roots, float* out_src, float* out_dst, void* workspace,
+                        size_t workspace_bytes, dygnn_stream_t stream) {
+    if (int rc = check_tgat_args(cfg, w, csr, levels, node_feat, edge_feat, roots, out_src, out_dst, workspace, workspace_bytes)) return rc;
+    if (roots.B == 0) return DYGNN_OK;
+    const TgatPlan p = make_tgat_plan(*cfg, roots.B);
+    const TgatStages c{p, static_cast<char*>(workspace), as_stream(stream), tgat_dedup_active(p, levels != nullptr)};
+    if (int rc = tgat_levels(c, csr, roots, levels, nullptr)) return rc;
+    return tgat_layers(c, w, node_feat, edge_feat, out_src, out_dst, false);
 }
 
 // ================================================================================================
@@ -853,7 +884,8 @@ extern "C" int dygnn_tgat_forward_levels(const dygnn_tgat_config* cfg, const dyg
                                          const float* edge_feat, int64_t batch, float* out_src, float* out_dst, void* workspace, size_t workspace_bytes,
                                          dygnn_stream_t stream) {
     DYGNN_REQUIRE(levels != nullptr, "tgat_forward_levels: levels is NULL");
-    return tgat_forward_impl(cfg, w, nullptr, node_feat, edge_feat, nullptr, nullptr, nullptr, batch, out_src, out_dst, workspace, workspace_bytes, stream, levels);
+    return tgat_forward(cfg, w, nullptr, levels, node_feat, edge_feat, TgatRoots{nullptr, nullptr, nullptr, batch, false}, out_src, out_dst, workspace,
+                        workspace_bytes, stream);
 }
 
 extern "C" int dygnn_tgat_level_entries(const dygnn_tgat_config* cfg, int64_t batch, const void* workspace, int64_t* total, int64_t* computed,
@@ -876,7 +908,8 @@ extern "C" int dygnn_tgat_level_entries(const dygnn_tgat_config* cfg, int64_t ba
 extern "C" int dygnn_tgat_forward(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_csr* csr, const float* node_feat,
                                   const float* edge_feat, const int64_t* src, const int64_t* dst, const double* times, int64_t batch,
                                   float* out_src, float* out_dst, void* workspace, size_t workspace_bytes, dygnn_stream_t stream) {
-    return tgat_forward_impl(cfg, w, csr, node_feat, edge_feat, src, dst, times, batch, out_src, out_dst, workspace, workspace_bytes, stream);
+    return tgat_forward(cfg, w, csr, nullptr, node_feat, edge_feat, TgatRoots{src, dst, times, batch, false}, out_src, out_dst, workspace, workspace_bytes,
+                        stream);
 }
 
 // Embeddings of a LIST of (node, time) roots [n_roots] (n_roots even: the roots are the level [first half ; second half] of n_roots / 2
@@ -888,8 +921,8 @@ extern "C" int dygnn_tgat_forward_roots(const dygnn_tgat_config* cfg, const dygn
     DYGNN_REQUIRE(n_roots >= 0 && n_roots % 2 == 0, "tgat_forward_roots: n_roots must be even (pad with a repeated root)");
     DYGNN_REQUIRE(n_roots == 0 || (ids && times && out && cfg), "tgat_forward_roots: null pointer");
     const int64_t b = n_roots / 2;
-    return tgat_forward_impl(cfg, w, csr, node_feat, edge_feat, ids, ids + b, times, b, out, out + (size_t)b * (cfg ? cfg->node_feat_dim : 0), workspace, workspace_bytes,
-                             stream, nullptr, false, false, nullptr, false, true);
+    return tgat_forward(cfg, w, csr, nullptr, node_feat, edge_feat, TgatRoots{ids, ids + b, times, b, true}, out, out + (size_t)b * (cfg ? cfg->node_feat_dim : 0),
+                        workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t dygnn_tgn_workspace_bytes(const dygnn_tgat_config* cfg, int64_t num_nodes, int64_t batch) {
@@ -924,34 +957,30 @@ static int tgn_forward_impl(const dygnn_tgat_config* cfg, const dygnn_tgat_weigh
     int32_t* count = reinterpret_cast<int32_t*>(ws + p.count);
     int32_t* list2 = reinterpret_cast<int32_t*>(ws + p.list2);
     int32_t* count2 = reinterpret_cast<int32_t*>(ws + p.count2);
-    // 0. the levels of this call (they depend on the graph only).  Their level-0 set is what the call reads: every slot of it names itself
-    //    owner of its node (k_tgat_expand)
     char* wt = ws + p.tgat;
-    const size_t wt_bytes = p.total - p.tgat;
-    const TgnTouch touch{owner, count, N};
+    const TgatRoots roots{src, dst, times, batch, false};
+    if (int rc = check_tgat_args(cfg, w, csr, levels, feat0, edge_feat, roots, out_src, out_dst, wt, p.total - p.tgat)) return rc;
     const TgatPlan tp = make_tgat_plan(*cfg, batch);
-    if (levels) {
-        // pre-sampled levels (`uniform` / `time_interval_aware`: the caller replayed the sampler's RandomState, MemoryModel.py:626-629): copied to
-        // where the expansion would have written them, then every level-0 slot names itself owner of its node
-        if (int rc = tgat_forward_impl(cfg, w, nullptr, feat0, edge_feat, nullptr, nullptr, nullptr, batch, out_src, out_dst, wt, wt_bytes, stream, levels, false, true)) return rc;
-        hipLaunchKernelGGL(k_tgn_touch_levels, dim3((unsigned)ceil_div(tp.n[0], 256)), dim3(256), 0, s, reinterpret_cast<const int32_t*>(wt + tp.ids[0]), tp.n[1], tp.k, touch);
-        DYGNN_LAUNCH_CHECK();
-    } else if (int rc = tgat_forward_impl(cfg, w, csr, feat0, edge_feat, src, dst, times, batch, out_src, out_dst, wt, wt_bytes, stream, nullptr, false, true, &touch)) return rc;
+    DYGNN_REQUIRE(chain::fits(tp.Fn, tp.Ft, tp.Dkv, tp.H), "tgn: feature dims do not fit the row-block kernels");
+    const TgatStages c{tp, wt, s, tgat_dedup_active(tp, levels != nullptr)};
+    // 0. the levels of this call (they depend on the graph only).  Their level-0 set is what the call reads: every slot of it names itself
+    //    owner of its node.  Pre-sampled levels: `uniform` / `time_interval_aware`, the caller replayed the sampler's RandomState
+    //    (MemoryModel.py:626-629)
+    const TgnTouch touch{owner, count, N};
+    if (int rc = tgat_levels(c, csr, roots, levels, &touch)) return rc;
     // 1. one launch: the owners list their nodes -- pending message: GRU rows; none: feat0 = memory + raw (MemoryModel.py:609) -- and the weights
     //    of the GRU and of the layers are packed into operand fragments (tgat_chain.h); then the updated memories of the listed nodes (the
     //    reference updates all nodes, MemoryModel.py:108-109): one launch, row count on the device
-    DYGNN_REQUIRE(chain::fits(tp.Fn, tp.Ft, tp.Dkv, tp.H), "tgn: feature dims do not fit the row-block kernels");
     const chain::PackPlan pp = chain::plan_pack(tp.L, tp.Fn, tp.Ft, tp.Dkv, tp.H, Dm);
     float* pk = reinterpret_cast<float*>(wt + tp.pack);
-    const int32_t* live = tgat_dedup_active(tp, levels != nullptr) ? reinterpret_cast<const int32_t*>(wt + tp.dd_count) : nullptr;
+    const int32_t* live = c.dedup ? reinterpret_cast<const int32_t*>(wt + tp.dd_count) : nullptr;
     const chain::ListArgs la{reinterpret_cast<const int32_t*>(wt + tp.ids[0]), live, owner, st->has_msg, pendf, count, list, count2, list2, tp.n[1], N, tp.k};
     if (int rc = chain::pack(s, pp, tp.L, tp.Fn, tp.Ft, tp.Dkv, tp.H, w, gru, Dm, pk, &la)) return rc;
     const int64_t ub = N < tp.n[0] ? N : tp.n[0];              // the list cannot be longer than the level-0 set
     const chain::GruArgs ga{list, count, list2, count2, st->msg, st->memory, node_feat, pk, pp.ih, pp.hh, gru->bias_ih, gru->bias_hh, Mnew, feat0, ub, Dm, Fn};
     if (int rc = chain::launch_gru(s, ga)) return rc;
     // 2. temporal graph attention over (memory + raw) features (GraphAttentionEmbedding, MemoryModel.py:548-664) on the levels built above
-    if (int rc = tgat_forward_impl(cfg, w, csr, feat0, edge_feat, src, dst, times, batch, out_src, out_dst, wt, wt_bytes, stream, nullptr, true, false, nullptr,
-                                   true, false, levels != nullptr)) return rc;
+    if (int rc = tgat_layers(c, w, feat0, edge_feat, out_src, out_dst, true)) return rc;
     if (!edges_are_positive) return DYGNN_OK;
     // 3. persist the updated memories of the batch nodes and store their new raw messages (MemoryModel.py:142-161)
     hipLaunchKernelGGL(k_tgn_commit, dim3((unsigned)(2 * n_pos)), dim3(256), 0, s, src, dst, times, edge_ids, n_pos, Mnew, pendf, st->memory, st->last_update, edge_feat,

@@ -1,7 +1,7 @@
 // TGAT training (SURVEY.md §8f-1 for BASELINE config 3): the forward of tgat.hip in TRAIN mode and its hand-written backward pass, so that
 // train_link_prediction.py:170-185, :242-257 (two calls, MergeLayer + BCE, loss.backward(), Adam) runs on the HIP path.
 //
-// Differences from the inference forward (tgat.hip: tgat_forward_impl):
+// Differences from the inference forward (tgat.hip: its level and layer stages, tgat_levels / tgat_layers):
 //   * no de-duplication of level 1 and no row-block chains: every level entry is its own row, as in the reference recursion
 //     (models/TGAT.py:92-110), so each occurrence draws its own dropout mask and each level-(l-1) row has exactly ONE consumer
 //     (level l-1 = [level-l self rows ; their neighbour rows]).  The backward pass therefore WRITES the lower level's row gradients:
@@ -17,14 +17,9 @@
 #include "dropout.h"
 #include "gemm.h"
 #include "tgat_attn.h"
+#include "tgat_levels.h"
 
 namespace dygnn {
-
-// tgat.hip
-int check_tgat(const dygnn_tgat_config* c);
-int tgat_expand_levels(hipStream_t s, const dygnn_csr* csr, const int64_t* src, const int64_t* dst, const double* times, int64_t B, int L, int k,
-                       int32_t* const* ids, double* const* tms, int32_t* const* eid, float* const* dt);
-
 namespace tgt {
 
 using f4 = __attribute__((ext_vector_type(4))) float;
@@ -467,34 +462,18 @@ extern "C" int dygnn_tgat_train_forward(const dygnn_tgat_config* cfg, const dygn
     DYGNN_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "tgat_train_forward: dropout must be in [0, 1)");
     const TrainPlan p = make_plan(*cfg, batch);
     if (workspace_bytes < p.total) { set_error("tgat_train_forward: workspace too small (%zu < %zu bytes)", workspace_bytes, p.total); return DYGNN_E_WORKSPACE; }
-    for (int l = 0; l < p.L; ++l) {
-        const dygnn_tgat_layer_weights& Lw = w->layers[l];
-        DYGNN_REQUIRE(Lw.query_w && Lw.key_w && Lw.value_w && Lw.ln_w && Lw.ln_b && Lw.res_w && Lw.res_b && Lw.fc1_w && Lw.fc1_b && Lw.fc2_w && Lw.fc2_b,
-                      "tgat_train_forward: null layer weights (layer %d)", l);
-    }
+    if (int rc = check_layer_weights(w, p.L, "tgat_train_forward: null layer weights")) return rc;
     hipStream_t s = as_stream(stream);
     char* ws = static_cast<char*>(workspace);
     auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     auto I32 = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
-    // levels: sampled here (`recent`) or copied from the caller's host-replayed draws (random strategies, as dygnn_tgat_forward_levels)
-    if (levels) {
-        for (int l = 0; l < p.L; ++l) {
-            DYGNN_REQUIRE(levels->ids[l], "tgat_train_forward: null level array (level %d)", l);
-            DYGNN_HIP(hipMemcpyAsync(I32(p.ids[l]), levels->ids[l], (size_t)p.n[l] * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        }
-        for (int l = 1; l <= p.L; ++l) {
-            DYGNN_REQUIRE(levels->nbr_eid[l] && levels->nbr_dt[l], "tgat_train_forward: null level array (level %d)", l);
-            DYGNN_HIP(hipMemcpyAsync(I32(p.eid[l]), levels->nbr_eid[l], (size_t)p.n[l] * p.k * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-            DYGNN_HIP(hipMemcpyAsync(F32(p.dt[l]), levels->nbr_dt[l], (size_t)p.n[l] * p.k * sizeof(float), hipMemcpyDeviceToDevice, s));
-        }
-    } else {
-        int32_t* ids[DYGNN_MAX_LAYERS + 1]; double* tms[DYGNN_MAX_LAYERS + 1]; int32_t* eid[DYGNN_MAX_LAYERS + 1]; float* dt[DYGNN_MAX_LAYERS + 1];
-        for (int l = 0; l <= p.L; ++l) {
-            ids[l] = I32(p.ids[l]); tms[l] = reinterpret_cast<double*>(ws + p.tms[l]);
-            eid[l] = l ? I32(p.eid[l]) : nullptr; dt[l] = l ? F32(p.dt[l]) : nullptr;
-        }
-        if (int rc = tgat_expand_levels(s, csr, src, dst, times, batch, p.L, p.k, ids, tms, eid, dt)) return rc;
-    }
+    // levels: sampled here (`recent`) or copied from the caller's host-replayed draws (random strategies, as dygnn_tgat_forward_levels); both
+    // write ids[0..L-1] (level L is read from src / dst)
+    LevelBufs to{};
+    for (int l = 0; l < p.L; ++l) { to.ids[l] = I32(p.ids[l]); to.times[l] = reinterpret_cast<double*>(ws + p.tms[l]); }
+    for (int l = 1; l <= p.L; ++l) { to.eid[l] = I32(p.eid[l]); to.dt[l] = F32(p.dt[l]); }
+    if (int rc = levels ? copy_levels(s, levels, p.L, p.k, p.n, p.L, to, "tgat_train_forward")
+                        : expand_levels(s, csr, TgatRoots{src, dst, times, batch, false}, p.L, p.k, to)) return rc;
     hipLaunchKernelGGL(k_tt_tabs, dim3(1), dim3(1), 0, s, reinterpret_cast<const float**>(ws + p.tabs), node_feat, edge_feat);
     DYGNN_LAUNCH_CHECK();
     const train::Drop dr = train::make_drop(dropout_p, seed);
@@ -536,15 +515,13 @@ extern "C" int dygnn_tgat_backward(const dygnn_tgat_config* cfg, const dygnn_tga
                                    const float* grad_out_dst, int64_t batch, float dropout_p, uint64_t seed, void* workspace, size_t workspace_bytes,
                                    dygnn_stream_t stream) {
     if (int rc = check_train(cfg)) return rc;
-    DYGNN_REQUIRE(w && grads && grads->time_w && grads->time_b && grad_out_src && grad_out_dst && workspace && batch > 0, "tgat_backward: bad arguments");
+    DYGNN_REQUIRE(w && w->time_w && w->time_b && grads && grads->time_w && grads->time_b && grad_out_src && grad_out_dst && workspace && batch > 0,
+                  "tgat_backward: bad arguments");
     DYGNN_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "tgat_backward: dropout must be in [0, 1)");
     const TrainPlan p = make_plan(*cfg, batch);
     if (workspace_bytes < p.total) { set_error("tgat_backward: workspace too small (%zu < %zu bytes)", workspace_bytes, p.total); return DYGNN_E_WORKSPACE; }
-    for (int l = 0; l < p.L; ++l) {
-        const dygnn_tgat_layer_weights& G = grads->layers[l];
-        DYGNN_REQUIRE(G.query_w && G.key_w && G.value_w && G.ln_w && G.ln_b && G.res_w && G.res_b && G.fc1_w && G.fc1_b && G.fc2_w && G.fc2_b,
-                      "tgat_backward: null gradient buffer (layer %d)", l);
-    }
+    if (int rc = check_layer_weights(w, p.L, "tgat_backward: null layer weights")) return rc;
+    if (int rc = check_layer_weights(grads, p.L, "tgat_backward: null gradient buffer")) return rc;
     hipStream_t s = as_stream(stream);
     char* ws = static_cast<char*>(workspace);
     auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };

@@ -15,7 +15,7 @@ import torch.nn as nn
 from . import _capi
 from .modules import MergeLayer, TimeEncoder
 from .neighbor_sampler import NeighborSampler
-from .tgat import MultiHeadAttention
+from .tgat import MultiHeadAttention, _tgat_levels, _tgat_weights, _to_dev, _workspace
 
 
 class MemoryBank(nn.Module):
@@ -167,8 +167,6 @@ class MemoryModel(nn.Module):
         if self.node_raw_features.device != dev:
             self.node_raw_features, self.edge_raw_features = self.node_raw_features.to(dev), self.edge_raw_features.to(dev)
         self.memory_bank._alloc()
-        to_dev = lambda x, dt: (x.to(device=dev, dtype=dt).contiguous() if isinstance(x, torch.Tensor)
-                                else torch.from_numpy(np.ascontiguousarray(x, dtype={torch.int64: np.int64, torch.float64: np.float64}[dt])).to(dev))
         csr = sampler.csr
         if getattr(self, "_validated_csr", None) is not csr:          # once per sampler: graph ids inside the tables and the memory bank
             csr.check_tables(min(self.node_raw_features.shape[0], self.num_nodes), self.edge_raw_features.shape[0])
@@ -179,40 +177,25 @@ class MemoryModel(nn.Module):
             e = np.asarray(edge_ids)
             if int(e.min()) < 0 or int(e.max()) >= self.edge_raw_features.shape[0]:
                 raise IndexError(f"edge id out of bounds for edge_raw_features with {self.edge_raw_features.shape[0]} rows")
-        src, dst, tms = to_dev(src_node_ids, torch.int64), to_dev(dst_node_ids, torch.int64), to_dev(node_interact_times, torch.float64)
+        src, dst, tms = _to_dev(src_node_ids, torch.int64, dev), _to_dev(dst_node_ids, torch.int64, dev), _to_dev(node_interact_times, torch.float64, dev)
         B = src.numel()
         assert dst.numel() == B and tms.numel() == B
         if edges_are_positive:
             assert edge_ids is not None                                                        # MemoryModel.py:140
-        eids = to_dev(edge_ids, torch.int64) if edge_ids is not None else None
+        eids = _to_dev(edge_ids, torch.int64, dev) if edge_ids is not None else None
         out = torch.empty((2, B, self.node_feat_dim), dtype=torch.float32, device=dev)      # one block: the library writes it in place
         out_src, out_dst = out[0], out[1]
         if B == 0:
             return out_src, out_dst
         cfg = _capi.TgatConfig(self.node_feat_dim, self.edge_feat_dim, self.time_feat_dim, self.num_layers, self.num_heads, int(num_neighbors))
-        w = _capi.TgatWeights()
-        w.time_w, w.time_b = self.time_encoder.w.weight.data_ptr(), self.time_encoder.w.bias.data_ptr()
         em = self.embedding_module
-        for l in range(self.num_layers):
-            a, m, L = em.temporal_conv_layers[l], em.merge_layers[l], w.layers[l]
-            L.query_w, L.key_w, L.value_w = a.query_projection.weight.data_ptr(), a.key_projection.weight.data_ptr(), a.value_projection.weight.data_ptr()
-            L.ln_w, L.ln_b = a.layer_norm.weight.data_ptr(), a.layer_norm.bias.data_ptr()
-            L.res_w, L.res_b = a.residual_fc.weight.data_ptr(), a.residual_fc.bias.data_ptr()
-            L.fc1_w, L.fc1_b, L.fc2_w, L.fc2_b = m.fc1.weight.data_ptr(), m.fc1.bias.data_ptr(), m.fc2.weight.data_ptr(), m.fc2.bias.data_ptr()
+        w = _tgat_weights(self.time_encoder, em.temporal_conv_layers, em.merge_layers, self.num_layers)
         cell = self.memory_updater.memory_updater
         gru = _capi.GruWeights(cell.weight_ih.data_ptr(), cell.weight_hh.data_ptr(), cell.bias_ih.data_ptr(), cell.bias_hh.data_ptr())
         mb = self.memory_bank
         st = _capi.TgnState(self.num_nodes, mb.node_memories.data_ptr(), mb.node_last_updated_times.data_ptr(), mb.msg.data_ptr(),
                             mb.msg_time.data_ptr(), mb.has_msg.data_ptr())
-        nbytes = self._lib.dygnn_tgn_workspace_bytes(C.byref(cfg), self.num_nodes, B)
-        if nbytes == 0:
-            _capi.check(-1)
-        key = (B, int(num_neighbors), torch.cuda.current_stream(dev).cuda_stream)
-        ws = self._workspace.get(key)
-        if ws is None or ws.numel() < nbytes or ws.device != dev:
-            if len(self._workspace) > 8:
-                self._workspace.clear()
-            ws = self._workspace[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _workspace(self._workspace, self._lib.dygnn_tgn_workspace_bytes(C.byref(cfg), self.num_nodes, B), B, num_neighbors, dev)
         n_pos = (B if edges_are_positive else 0) if _n_positive is None else int(_n_positive)
         if eids is not None and eids.numel() < n_pos:
             raise AssertionError("edge_ids must cover the positive edges")
@@ -261,14 +244,4 @@ class MemoryModel(nn.Module):
         ids[L - 1] = np.concatenate([nodes, top[0].reshape(-1)])
         if L == 2:
             ids[0] = np.concatenate([ids[1], own[0].reshape(-1), nbr[0].reshape(-1)])
-        lv, keep = _capi.TgatLevels(), []
-        for l in range(L + 1):
-            a = torch.from_numpy(np.ascontiguousarray(ids[l], dtype=np.int32)).to(dev)
-            keep.append(a)
-            lv.ids[l] = a.data_ptr()
-            if l >= 1:
-                b = torch.from_numpy(np.ascontiguousarray(eid[l], dtype=np.int32)).to(dev)
-                c = torch.from_numpy(np.ascontiguousarray(dts[l], dtype=np.float32)).to(dev)
-                keep += [b, c]
-                lv.nbr_eid[l], lv.nbr_dt[l] = b.data_ptr(), c.data_ptr()
-        return lv, keep
+        return _tgat_levels(ids, eid, dts, dev)
