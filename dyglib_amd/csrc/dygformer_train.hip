@@ -433,6 +433,12 @@ static void launch_mm_dma(hipStream_t s, const MM& p, bool tA, bool tB, int batc
 
 static int colsum(hipStream_t s, const float* A, int lda, int64_t M, int N, float* out, bool accumulate = false);
 
+bool mm_gathers_rows(const float* A, int lda, const float* B, int ldb, int M, int N, int K) {
+    const char* dma_env = getenv("DYGNN_MM_DMA");
+    return M >= 48 && N >= 48 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && lda % 4 == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0 && ldb % 4 == 0 &&
+           K % 4 == 0 && !(dma_env && dma_env[0] == '0');
+}
+
 int mm(hipStream_t s, const float* A, int lda, bool tA, const float* B, int ldb, bool tB, float* C, int ldc, int M, int N, int K, const float* bias, float alpha,
        float beta, int batch, int H, int64_t sAb, int64_t sAh, int64_t sBb, int64_t sBh, int64_t sCb, int64_t sCh, bool relu, bool c_is_zero, float* colsum_out, const int32_t* m_dev, bool a_kpad,
        const int32_t* a_rows) {

@@ -14,6 +14,9 @@ int mm(hipStream_t s, const float* A, int lda, bool tA, const float* B, int ldb,
        const int32_t* m_dev = nullptr,    // device-side count of live rows (<= M): row tiles beyond it are skipped on the device
        bool a_kpad = false,               // A [M][lda] has zeros behind its K columns up to a multiple of 4 (K itself need not be one)
        const int32_t* a_rows = nullptr);  // !tA only: row m of the product's A is A[a_rows[m]] (device table; the product gathers its rows: no staging copy)
+// Whether mm(s, A, lda, false, B, ldb, true, C, ldc, M, N, K, ...) takes the LDS-DMA kernel, the only one that accepts a row table `a_rows`
+// (C's alignment is not a precondition).  DYGNN_MM_DMA=0 (read per call) makes it false.
+bool mm_gathers_rows(const float* A, int lda, const float* B, int ldb, int M, int N, int K);
 // Weight-gradient-shaped products in one grouped split-K launch (k_dw_grouped): C_p[m][n] += sum_k A_p[k][m] * B_p[k][n] for every problem p, all
 // over the same K rows; colsum_p[m] += sum_k A_p[k][m] where given.  C and colsum ACCUMULATE (atomics): zero them first.  A, B 16-byte aligned,
 // lda, ldb, M, N multiples of 4.

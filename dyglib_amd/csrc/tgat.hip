@@ -162,10 +162,12 @@ __global__ __launch_bounds__(256) void k_gemm_nt(const float* __restrict__ A, co
 //     score_ijh = q_ih . (W_k,h x_ij) = (W_k,h^T q_ih) . x_ij          and          o_ih = sum_j p_ijh (W_v,h x_ij) = W_v,h (sum_j p_ijh x_ij)
 // with x_ij = [h(nbr) | edge | cos(w dt + b)] the neighbour's input row: the two [n*k, 444] x [444, 272] products (81 GFLOP per
 // layer-1 pass at Reddit size) become two [n, 136] x [136, 444] products per head (4 GFLOP) around this kernel, which is
-// bound by gathering the input rows twice.  One wave per node; lanes sweep a row as float4 (Dkv/4 <= 128 columns).
+// bound by gathering the input rows twice.  One wave per node; lanes sweep a row as float4, NCOL per lane (Dkv/4 <= 64 NCOL columns).
 // qk [n][H][Dkv] = W_k,h^T q_ih ; z [n][H][Dkv] = sum_j p_ijh x_ij.
 // ------------------------------------------------------------------------------------------------
-template <int KCACHE>      // > 0: the k <= KCACHE input rows stay in registers between the score pass and the weighted sum (one gather)
+// KCACHE > 0: the k <= KCACHE input rows stay in registers between the score pass and the weighted sum (one gather).  NCOL = 2: Dkv <= 512,
+// NCOL = 4: Dkv <= 1024 (check_tgat's bound, the training path's).
+template <int KCACHE, int NCOL>
 __global__ __launch_bounds__(256) void k_tgat_attn_lin(const float* __restrict__ qk, const float* __restrict__ h_lower, const float* __restrict__ node_feat,
                                                          const float* __restrict__ edge_feat, const int32_t* __restrict__ lower_ids,
                                                          const int32_t* __restrict__ nbr_eid, const float* __restrict__ nbr_dt, const float* __restrict__ tw,
@@ -177,8 +179,9 @@ __global__ __launch_bounds__(256) void k_tgat_attn_lin(const float* __restrict__
     if (i >= n) return;
     float* pw = reinterpret_cast<float*>(smem) + wave * H * k;       // [H][k] scores -> probabilities
     const int Dkv = Fn + Fe + Ft, D4 = Dkv >> 2;
-    const int x0 = lane, x1 = lane + 64;
-    const bool v0 = x0 < D4, v1 = x1 < D4;
+    bool vc[NCOL];                                                   // float4 column lane + 64 c of the row exists
+#pragma unroll
+    for (int c = 0; c < NCOL; ++c) vc[c] = lane + 64 * c < D4;
     auto fetch = [&](int64_t r, int x) -> f4 {                       // float4 column x of the input row of neighbour entry r
         const int kk = 4 * x;
         if (kk < Fn) {
@@ -194,7 +197,7 @@ __global__ __launch_bounds__(256) void k_tgat_attn_lin(const float* __restrict__
     };
     auto dot4 = [](const f4 a, const f4 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w))); };
     const f4 zero = f4{0.f, 0.f, 0.f, 0.f};
-    f4 xs[KCACHE > 0 ? KCACHE : 1][2];
+    f4 xs[KCACHE > 0 ? KCACHE : 1][NCOL];
     if (KCACHE > 0) {
         // all k rows are requested back to back (one memory latency for the whole neighbourhood), then every (row, head)
         // score is reduced: 2*k independent butterfly chains that pipeline instead of one chain per loop iteration
@@ -202,9 +205,9 @@ __global__ __launch_bounds__(256) void k_tgat_attn_lin(const float* __restrict__
         // issues exactly one unconditional float4 load per row and pass (lanes of the time columns and beyond read row 0 of
         // the edge table and discard it); the row indices are wave-uniform scalars.  The cosines are filled in afterwards.
         const float* ntab = h_lower ? h_lower : node_feat;
-        const float* bp[2]; size_t st[2]; int cls[2];
+        const float* bp[NCOL]; size_t st[NCOL]; int cls[NCOL];
 #pragma unroll
-        for (int ps = 0; ps < 2; ++ps) {
+        for (int ps = 0; ps < NCOL; ++ps) {
             const int kk = 4 * (lane + 64 * ps);
             cls[ps] = kk < Fn ? 0 : kk < Fn + Fe ? 1 : kk < Dkv ? 2 : 3;
             bp[ps] = cls[ps] == 0 ? ntab + kk : cls[ps] == 1 ? edge_feat + (kk - Fn) : edge_feat;
@@ -216,13 +219,13 @@ __global__ __launch_bounds__(256) void k_tgat_attn_lin(const float* __restrict__
             const int64_t nrow = h_lower ? n + r : (int64_t)lower_ids[n + r];
             const int64_t erow = nbr_eid[r];
 #pragma unroll
-            for (int ps = 0; ps < 2; ++ps) xs[j][ps] = *reinterpret_cast<const f4*>(bp[ps] + (cls[ps] == 0 ? nrow : erow) * st[ps]);
+            for (int ps = 0; ps < NCOL; ++ps) xs[j][ps] = *reinterpret_cast<const f4*>(bp[ps] + (cls[ps] == 0 ? nrow : erow) * st[ps]);
         }
         // time encoding: computed in a ROLLED loop into LDS (the cosine code exists once; unrolled over 20 rows it alone was
         // 100 KB of straight-line code, more than the instruction cache, executed once per wave), then read back per row
         float* tf = reinterpret_cast<float*>(smem) + 4 * H * k + (size_t)wave * KCACHE * Ft;          // [KCACHE][Ft]
 #pragma unroll
-        for (int ps = 0; ps < 2; ++ps) {
+        for (int ps = 0; ps < NCOL; ++ps) {
             if (cls[ps] == 2) {
                 const int f = 4 * (lane + 64 * ps) - Fn - Fe;
                 const f4 w = *reinterpret_cast<const f4*>(tw + f), b = *reinterpret_cast<const f4*>(tb + f);
@@ -237,7 +240,7 @@ __global__ __launch_bounds__(256) void k_tgat_attn_lin(const float* __restrict__
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int ps = 0; ps < 2; ++ps) {
+        for (int ps = 0; ps < NCOL; ++ps) {
             if (cls[ps] == 2) {
                 const int f = 4 * (lane + 64 * ps) - Fn - Fe;
 #pragma unroll
@@ -249,13 +252,21 @@ __global__ __launch_bounds__(256) void k_tgat_attn_lin(const float* __restrict__
         }
 #pragma unroll
         for (int j = 0; j < KCACHE; ++j)
-            if (j >= k) { xs[j][0] = zero; xs[j][1] = zero; }
+            if (j >= k)
+#pragma unroll
+                for (int ps = 0; ps < NCOL; ++ps) xs[j][ps] = zero;
         for (int h = 0; h < H; ++h) {
             const f4* qh = reinterpret_cast<const f4*>(qk + ((size_t)i * H + h) * Dkv);
-            const f4 qa = v0 ? qh[x0] : zero, qb = v1 ? qh[x1] : zero;
+            f4 qv[NCOL];
+#pragma unroll
+            for (int c = 0; c < NCOL; ++c) qv[c] = vc[c] ? qh[lane + 64 * c] : zero;
             float sc[KCACHE > 0 ? KCACHE : 1];
 #pragma unroll
-            for (int j = 0; j < KCACHE; ++j) sc[j] = dot4(qa, xs[j][0]) + dot4(qb, xs[j][1]);
+            for (int j = 0; j < KCACHE; ++j) {
+                sc[j] = dot4(qv[0], xs[j][0]);
+#pragma unroll
+                for (int c = 1; c < NCOL; ++c) sc[j] += dot4(qv[c], xs[j][c]);
+            }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1)
 #pragma unroll
@@ -269,10 +280,14 @@ __global__ __launch_bounds__(256) void k_tgat_attn_lin(const float* __restrict__
     for (int j = 0; j < (KCACHE > 0 ? 0 : 1 << 30); ++j) {
         if (j >= k) break;
         const int64_t r = i * k + j;
-        const f4 xa = v0 ? fetch(r, x0) : zero, xb = v1 ? fetch(r, x1) : zero;
+        f4 xv[NCOL];
+#pragma unroll
+        for (int c = 0; c < NCOL; ++c) xv[c] = vc[c] ? fetch(r, lane + 64 * c) : zero;
         for (int h = 0; h < H; ++h) {
             const f4* qh = reinterpret_cast<const f4*>(qk + ((size_t)i * H + h) * Dkv);
-            float sc = (v0 ? dot4(qh[x0], xa) : 0.f) + (v1 ? dot4(qh[x1], xb) : 0.f);
+            float sc = vc[0] ? dot4(qh[lane], xv[0]) : 0.f;
+#pragma unroll
+            for (int c = 1; c < NCOL; ++c) sc += vc[c] ? dot4(qh[lane + 64 * c], xv[c]) : 0.f;
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) sc += __shfl_xor(sc, o, 64);
             if (lane == 0) {
@@ -284,35 +299,36 @@ __global__ __launch_bounds__(256) void k_tgat_attn_lin(const float* __restrict__
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if (lane < H) {
+    for (int hh = lane; hh < H; hh += kWave) {                       // H may exceed the wave (up to 68 heads of 4 at Dq = 272)
         float mx = -INFINITY;
-        for (int j = 0; j < k; ++j) mx = fmaxf(mx, pw[lane * k + j]);
+        for (int j = 0; j < k; ++j) mx = fmaxf(mx, pw[hh * k + j]);
         float sum = 0.f;
-        for (int j = 0; j < k; ++j) { const float e = expf(pw[lane * k + j] - mx); pw[lane * k + j] = e; sum += e; }
+        for (int j = 0; j < k; ++j) { const float e = expf(pw[hh * k + j] - mx); pw[hh * k + j] = e; sum += e; }
         const float inv = 1.0f / sum;
-        for (int j = 0; j < k; ++j) pw[lane * k + j] *= inv;
+        for (int j = 0; j < k; ++j) pw[hh * k + j] *= inv;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     for (int h = 0; h < H; ++h) {
-        f4 za = zero, zb = zero;
+        f4 za[NCOL];
+#pragma unroll
+        for (int c = 0; c < NCOL; ++c) za[c] = zero;
 #pragma unroll
         for (int j = 0; j < (KCACHE > 0 ? KCACHE : 1 << 30); ++j) {
             if (j >= k) break;
             const int64_t r = i * k + j;
             const float p = pw[h * k + j];
-            if (KCACHE > 0) {
-                const f4 xa = xs[j][0], xb = xs[j][1];
-                za.x = fmaf(p, xa.x, za.x); za.y = fmaf(p, xa.y, za.y); za.z = fmaf(p, xa.z, za.z); za.w = fmaf(p, xa.w, za.w);
-                zb.x = fmaf(p, xb.x, zb.x); zb.y = fmaf(p, xb.y, zb.y); zb.z = fmaf(p, xb.z, zb.z); zb.w = fmaf(p, xb.w, zb.w);
-                continue;
+#pragma unroll
+            for (int c = 0; c < NCOL; ++c) {
+                if (KCACHE == 0 && !vc[c]) continue;
+                const f4 xv = KCACHE > 0 ? xs[j][c] : fetch(r, lane + 64 * c);
+                za[c].x = fmaf(p, xv.x, za[c].x); za[c].y = fmaf(p, xv.y, za[c].y); za[c].z = fmaf(p, xv.z, za[c].z); za[c].w = fmaf(p, xv.w, za[c].w);
             }
-            if (v0) { const f4 xv = fetch(r, x0); za.x = fmaf(p, xv.x, za.x); za.y = fmaf(p, xv.y, za.y); za.z = fmaf(p, xv.z, za.z); za.w = fmaf(p, xv.w, za.w); }
-            if (v1) { const f4 xv = fetch(r, x1); zb.x = fmaf(p, xv.x, zb.x); zb.y = fmaf(p, xv.y, zb.y); zb.z = fmaf(p, xv.z, zb.z); zb.w = fmaf(p, xv.w, zb.w); }
         }
         f4* zo = reinterpret_cast<f4*>(z + ((size_t)i * H + h) * Dkv);
-        if (v0) zo[x0] = za;
-        if (v1) zo[x1] = zb;
+#pragma unroll
+        for (int c = 0; c < NCOL; ++c)
+            if (vc[c]) zo[lane + 64 * c] = za[c];
     }
 }
 
@@ -534,6 +550,8 @@ int check_tgat(const dygnn_tgat_config* c) {      // (also the training path's c
     DYGNN_REQUIRE(c->num_neighbors <= 64, "tgat: num_neighbors > 64 not supported");
     DYGNN_REQUIRE(c->node_feat_dim + c->time_feat_dim <= 16 * 17, "tgat: node_feat_dim + time_feat_dim > 272 not supported");
     DYGNN_REQUIRE(((c->node_feat_dim + c->time_feat_dim) / c->num_heads) % 4 == 0, "tgat: head dim must be a multiple of 4");
+    // the attention kernels hold an input row [h | edge | time] as at most four float4 columns per lane (k_tgat_attn_lin, tgat_train.hip: NC)
+    DYGNN_REQUIRE((int64_t)c->node_feat_dim + c->edge_feat_dim + c->time_feat_dim <= 1024, "tgat: node_feat_dim + edge_feat_dim + time_feat_dim > 1024 not supported");
     return DYGNN_OK;
 }
 
@@ -671,6 +689,29 @@ static int tgat_levels(const TgatStages& c, const dygnn_csr* csr, const TgatRoot
     return DYGNN_OK;
 }
 
+// The one-wave-per-node attention (k_tgat_attn_lin) for what the two-wave kernel does not take: more than 20 neighbours (row slots in LDS),
+// more than two heads (k <= 20: rows in registers), Dkv > 512 (four float4 columns per lane; rows re-gathered).  Its LDS ([4][H][k] scores,
+// plus [4][20][Ft] time encodings with rows in registers) exceeds the default 64 KiB for many heads or time features (H = 68 at k = 64:
+// 68 KiB; H = 4, Ft = 268: 85 KiB); check_tgat's bounds keep it under 160 KiB.
+template <int KC, int NCOL>
+static int launch_attn_lin_t(hipStream_t s, const TgatPlan& p, size_t lds, const float* qk, const float* h_lower, const float* node_feat,
+                             const float* edge_feat, const int32_t* ids, const int32_t* eid, const float* dt, const float* tw, const float* tb, int64_t n,
+                             float scale, float* z) {
+    if (lds > 64 * 1024) DYGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tgat_attn_lin<KC, NCOL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_tgat_attn_lin<KC, NCOL>), dim3((unsigned)ceil_div(n, 4)), dim3(256), lds, s, qk, h_lower, node_feat, edge_feat, ids, eid, dt, tw, tb, n,
+                       p.k, p.Fn, p.Fe, p.Ft, p.H, scale, z);
+    DYGNN_LAUNCH_CHECK();
+    return DYGNN_OK;
+}
+static int launch_attn_lin(hipStream_t s, const TgatPlan& p, const float* qk, const float* h_lower, const float* node_feat, const float* edge_feat,
+                           const int32_t* ids, const int32_t* eid, const float* dt, const float* tw, const float* tb, int64_t n, float scale, float* z) {
+    const size_t lds = (size_t)4 * p.H * p.k * sizeof(float);
+    if (p.Dkv > 4 * 64 * 2) return launch_attn_lin_t<0, 4>(s, p, lds, qk, h_lower, node_feat, edge_feat, ids, eid, dt, tw, tb, n, scale, z);
+    if (p.k <= 20)
+        return launch_attn_lin_t<20, 2>(s, p, lds + (size_t)4 * 20 * p.Ft * sizeof(float), qk, h_lower, node_feat, edge_feat, ids, eid, dt, tw, tb, n, scale, z);
+    return launch_attn_lin_t<0, 2>(s, p, lds, qk, h_lower, node_feat, edge_feat, ids, eid, dt, tw, tb, n, scale, z);
+}
+
 // Layer stage: layers 1..L, bottom-up, on the levels in the workspace, into out_src / out_dst.  packed (TGN): the caller has packed the layer
 // weights into the workspace's row-block fragments, and the layers run as chains.
 static int tgat_layers(const TgatStages& c, const dygnn_tgat_weights* w, const float* node_feat, const float* edge_feat, float* out_src, float* out_dst,
@@ -718,10 +759,12 @@ static int tgat_layers(const TgatStages& c, const dygnn_tgat_weights* w, const f
         // q = W_q[:, :Fn] h + cq (see k_tgat_const_q): the product gathers the feature rows itself
         hipLaunchKernelGGL(k_tgat_const_q, dim3((unsigned)ceil_div(p.Dq, 4)), dim3(256), 0, s, Lw.query_w, w->time_w, w->time_b, p.Dq, p.Fn, p.Ft, cq, ct);
         DYGNN_LAUNCH_CHECK();
-        if (n >= 48) {
-            if (int rc = train::mm(s, h_lower ? h_lower : node_feat, p.Fn, false, Lw.query_w, p.Dq, true, F32(p.q), p.Dq, (int)n, p.Dq, p.Fn, cq, 1.f, 0.f, 1, 1, 0, 0, 0, 0,
+        const float* qa = h_lower ? h_lower : node_feat;
+        if (n >= 48 && train::mm_gathers_rows(qa, p.Fn, Lw.query_w, p.Dq, (int)n, p.Dq, p.Fn)) {
+            if (int rc = train::mm(s, qa, p.Fn, false, Lw.query_w, p.Dq, true, F32(p.q), p.Dq, (int)n, p.Dq, p.Fn, cq, 1.f, 0.f, 1, 1, 0, 0, 0, 0,
                                    0, 0, false, false, nullptr, nl, false, h_lower ? lmap : I32(p.ids[l - 1]))) return rc;
-        } else {      // a handful of rows: the feature rows are staged ([n][Fn], Ft = 0: no time columns), then the small-M kernel
+        } else {      // a handful of rows, or a product the row-gathering kernel cannot take (Dq < 48, DYGNN_MM_DMA=0, unaligned feature table): the
+                      // feature rows are staged ([n][Fn], Ft = 0: no time columns), then the small-M kernel
             hipLaunchKernelGGL(k_tgat_qrows, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, s, h_lower, node_feat, I32(p.ids[l - 1]), w->time_w, w->time_b, n, p.Fn, 0,
                                F32(p.q_in), nl, lmap);
             DYGNN_LAUNCH_CHECK();
@@ -733,8 +776,6 @@ static int tgat_layers(const TgatStages& c, const dygnn_tgat_weights* w, const f
         if (int rc = train::mm(s, F32(p.q), p.Dq, false, Lw.key_w, p.Dkv, false, F32(p.qk), p.H * p.Dkv, (int)n, p.Dkv, p.hd, nullptr, 1.f, 0.f, p.H, p.H, 0, p.hd,
                                0, (int64_t)p.hd * p.Dkv, 0, p.Dkv, false, false, nullptr, nl)) return rc;
         }
-        const dim3 grid((unsigned)ceil_div(n, 4));
-        const size_t lds = (size_t)4 * p.H * p.k * sizeof(float);
         const bool attn_in_post = chain && chain::post_fuses_attention(n, p.Fn, p.Ft, p.Dkv, p.H, p.k);      // the chain's last kernel runs it on its own rows
         if (attn_in_post) {
         } else if (p.k <= 20 && p.H <= 2 && p.Dkv <= 512) {
@@ -750,12 +791,8 @@ static int tgat_layers(const TgatStages& c, const dygnn_tgat_weights* w, const f
             if (KC == 10) { if (p.k == 10) DYGNN_ATTN_LAUNCH(10, true); else DYGNN_ATTN_LAUNCH(10, false); }
             else { if (p.k == 20) DYGNN_ATTN_LAUNCH(20, true); else DYGNN_ATTN_LAUNCH(20, false); }
 #undef DYGNN_ATTN_LAUNCH
-        } else if (p.k <= 20)
-            hipLaunchKernelGGL((k_tgat_attn_lin<20>), grid, dim3(256), lds + (size_t)4 * 20 * p.Ft * sizeof(float), s, F32(p.qk), h_lower, node_feat, edge_feat, I32(p.ids[l - 1]), I32(p.eid[l]), F32(p.dt[l]),
-                               w->time_w, w->time_b, n, p.k, p.Fn, p.Fe, p.Ft, p.H, scale, F32(p.z));
-        else
-            hipLaunchKernelGGL((k_tgat_attn_lin<0>), grid, dim3(256), lds, s, F32(p.qk), h_lower, node_feat, edge_feat, I32(p.ids[l - 1]), I32(p.eid[l]), F32(p.dt[l]),
-                               w->time_w, w->time_b, n, p.k, p.Fn, p.Fe, p.Ft, p.H, scale, F32(p.z));
+        } else if (int rc = launch_attn_lin(s, p, F32(p.qk), h_lower, node_feat, edge_feat, I32(p.ids[l - 1]), I32(p.eid[l]), F32(p.dt[l]), w->time_w, w->time_b, n,
+                                            scale, F32(p.z))) return rc;
         DYGNN_LAUNCH_CHECK();
         if (chain) {
             // W_v z -> residual_fc + q_in -> LayerNorm -> MergeLayer, one workgroup per 16 / 32 rows

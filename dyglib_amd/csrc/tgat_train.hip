@@ -421,13 +421,8 @@ static TrainPlan make_plan(const dygnn_tgat_config& c, int64_t B) {
 }
 
 static int check_train(const dygnn_tgat_config* cfg) {
-    if (int rc = check_tgat(cfg)) return rc;
-    const int Dkv = cfg->node_feat_dim + cfg->edge_feat_dim + cfg->time_feat_dim;
-    if (Dkv > 4 * 64 * NC) {
-        set_error("tgat training: node_feat_dim + edge_feat_dim + time_feat_dim > %d is not supported", 4 * 64 * NC);
-        return DYGNN_E_UNSUPPORTED;
-    }
-    return DYGNN_OK;
+    static_assert(4 * 64 * NC == 1024, "check_tgat bounds Dkv by the columns a lane holds");
+    return check_tgat(cfg);
 }
 
 static int colsum(hipStream_t s, const float* A, int lda, int64_t rows, int cols, float* part, float* out) {

@@ -234,6 +234,14 @@ def test_tgat_inference_validates_before_any_hip_call(lib):
     roots = lambda w, nbytes: lib.dygnn_tgat_forward_roots(C.byref(cfg), C.byref(w), C.byref(csr), D, D, D, D, 2 * B, D, D, nbytes, None)
     _expect(lib, roots(_weights(L, (1, "key_w")), need), -1, "tgat: null layer weights (layer 1)")
     _expect(lib, roots(_weights(L), need - 1), -4, "tgat: workspace too small")
+    # node + edge + time dims above 1024 (four float4 columns per lane in the attention kernels, the training path's bound too)
+    wide, edge = _capi.TgatConfig(172, 756, 100, L, 2, 4), _capi.TgatConfig(172, 752, 100, L, 2, 4)
+    assert lib.dygnn_tgat_workspace_bytes(C.byref(wide), B) == 0 and lib.dygnn_tgat_workspace_bytes(C.byref(edge), B) > 0
+    assert lib.dygnn_tgat_train_workspace_bytes(C.byref(wide), B) == 0 and lib.dygnn_tgat_train_workspace_bytes(C.byref(edge), B) > 0
+    too_wide = "tgat: node_feat_dim + edge_feat_dim + time_feat_dim > 1024 not supported"
+    _expect(lib, lib.dygnn_tgat_forward(C.byref(wide), C.byref(_weights(L)), C.byref(csr), D, D, D, D, D, B, D, D, D, 1 << 40, None), -1, too_wide)
+    _expect(lib, lib.dygnn_tgat_forward_levels(C.byref(wide), C.byref(_weights(L)), C.byref(_levels(L)), D, D, B, D, D, D, 1 << 40, None), -1, too_wide)
+    _expect(lib, lib.dygnn_tgat_forward_roots(C.byref(wide), C.byref(_weights(L)), C.byref(csr), D, D, D, D, 2 * B, D, D, 1 << 40, None), -1, too_wide)
 
 
 @cpu_only
