@@ -16,7 +16,7 @@ import torch  # noqa: F401  (must be imported first: see module docstring)
 from . import _build
 
 DYGNN_MAX_LAYERS = 8
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 c_i32p = C.POINTER(C.c_int32)
 c_i64p = C.POINTER(C.c_int64)
@@ -71,6 +71,10 @@ class TgatLevels(C.Structure):
 
 class GruWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+
+
+class GruGrads(GruWeights):
+    """dygnn_gru_grads: the layout of GruWeights, its pointers writable gradient buffers (zero on entry)."""
 
 
 class TgnState(C.Structure):
@@ -141,6 +145,12 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dygnn_tgat_backward": (C.c_int, [C.POINTER(TgatConfig), C.POINTER(TgatWeights), C.POINTER(TgatWeights), C.c_void_p, C.c_void_p, C.c_int64,
                                       C.c_float, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dygnn_tgn_train_workspace_bytes": (C.c_size_t, [C.POINTER(TgatConfig), C.c_int64, C.c_int64]),
+    "dygnn_tgn_train_forward": (C.c_int, [C.POINTER(TgatConfig), C.POINTER(TgatWeights), C.POINTER(GruWeights), C.POINTER(Csr), C.POINTER(TgatLevels),
+                                          C.c_void_p, C.c_void_p, C.POINTER(TgnState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_int64, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dygnn_tgn_backward": (C.c_int, [C.POINTER(TgatConfig), C.POINTER(TgatWeights), C.POINTER(GruWeights), C.POINTER(TgatWeights), C.POINTER(GruGrads),
+                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dygnn_merge_layer_sigmoid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dygnn_merge_layer_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,

@@ -26,11 +26,7 @@ __device__ __forceinline__ f4 tmfma(float a, float b, f4 c) { return __builtin_a
 // TGN (MemoryModel.py:108-109, :609): the level-0 set of a call is what it reads.  Every level-0 slot (entry q, position j) stores
 // owner[id] = slot -- plain stores, some slot of a node wins; chain::pack's list blocks (tgat_chain.h: ListArgs) let the winner list its
 // node.  (Flags claimed with returning atomics cost 25 us per step here: 8,800 device-scope atomics on a 28-KB array.)
-struct TgnTouch {
-    int32_t* owner;                // [N]; entries of nodes outside this call's level-0 set are stale and never read
-    int32_t* counts;               // the two list lengths, zeroed here for the list pass of the next launch
-    int64_t N;
-};
+// (struct TgnTouch: tgat_levels.h)
 // `src` given: this is the top level [src ; dst] read straight from the caller's int64 / float64 arrays (B pairs)
 __global__ __launch_bounds__(256) void k_tgat_expand(const int64_t* __restrict__ indptr, const int32_t* __restrict__ cnbr,
                                                        const int32_t* __restrict__ ceid, const double* __restrict__ cts, int64_t num_nodes,
@@ -683,8 +679,7 @@ static int tgat_levels(const TgatStages& c, const dygnn_csr* csr, const TgatRoot
     // pre-sampled levels (random strategies): copied where the sampling kernels would have written them
     if (int rc = copy_levels(c.s, levels, p.L, p.k, p.n, p.L + 1, to, "tgat")) return rc;
     if (touch) {
-        hipLaunchKernelGGL(k_tgn_touch_levels, dim3((unsigned)ceil_div(p.n[0], 256)), dim3(256), 0, c.s, to.ids[0], p.n[1], p.k, *touch);
-        DYGNN_LAUNCH_CHECK();
+        if (int rc = tgn_touch_levels(c.s, to.ids[0], p.n[1], p.k, *touch)) return rc;
     }
     return DYGNN_OK;
 }
@@ -915,6 +910,20 @@ static TgnPlan make_tgn_plan(const dygnn_tgat_config& c, int64_t N, int64_t B) {
     p.total = o;
     return p;
 }
+
+int tgn_touch_levels(hipStream_t s, const int32_t* ids0, int64_t n1, int k, const TgnTouch& touch) {
+    hipLaunchKernelGGL(k_tgn_touch_levels, dim3((unsigned)ceil_div(n1 * (k + 1), 256)), dim3(256), 0, s, ids0, n1, k, touch);
+    DYGNN_LAUNCH_CHECK();
+    return DYGNN_OK;
+}
+
+int tgn_commit(hipStream_t s, const int64_t* src, const int64_t* dst, const double* times, const int64_t* edge_ids, int64_t n_pos, const float* Mnew,
+               const int32_t* pendf, const dygnn_tgn_state* st, const float* edge_feat, const float* tw, const float* tb, int Fn, int Fe, int Ft) {
+    hipLaunchKernelGGL(k_tgn_commit, dim3((unsigned)(2 * n_pos)), dim3(256), 0, s, src, dst, times, edge_ids, n_pos, Mnew, pendf, st->memory, st->last_update, edge_feat,
+                       tw, tb, Fn, Fe, Ft, st->msg, st->msg_time, st->has_msg, st->num_nodes);
+    DYGNN_LAUNCH_CHECK();
+    return DYGNN_OK;
+}
 }  // namespace dygnn
 
 extern "C" int dygnn_tgat_forward_levels(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_tgat_levels* levels, const float* node_feat,
@@ -1020,10 +1029,7 @@ static int tgn_forward_impl(const dygnn_tgat_config* cfg, const dygnn_tgat_weigh
     if (int rc = tgat_layers(c, w, feat0, edge_feat, out_src, out_dst, true)) return rc;
     if (!edges_are_positive) return DYGNN_OK;
     // 3. persist the updated memories of the batch nodes and store their new raw messages (MemoryModel.py:142-161)
-    hipLaunchKernelGGL(k_tgn_commit, dim3((unsigned)(2 * n_pos)), dim3(256), 0, s, src, dst, times, edge_ids, n_pos, Mnew, pendf, st->memory, st->last_update, edge_feat,
-                       w->time_w, w->time_b, Fn, Fe, Ft, st->msg, st->msg_time, st->has_msg, N);
-    DYGNN_LAUNCH_CHECK();
-    return DYGNN_OK;
+    return tgn_commit(s, src, dst, times, edge_ids, n_pos, Mnew, pendf, st, edge_feat, w->time_w, w->time_b, Fn, Fe, Ft);
 }
 
 extern "C" int dygnn_tgn_forward(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_gru_weights* gru, const dygnn_csr* csr,

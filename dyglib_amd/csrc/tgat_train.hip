@@ -18,6 +18,7 @@
 #include "gemm.h"
 #include "tgat_attn.h"
 #include "tgat_levels.h"
+#include "tgat_train.h"
 
 namespace dygnn {
 namespace tgt {
@@ -29,6 +30,12 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+// TGN: the gradient row of a level-0 node, or NULL where the node passes no gradient on (no pending message; id 0, the padding, never has one)
+__device__ __forceinline__ float* feat0_row(const Feat0Grad& fg, int32_t node, int Fn) {
+    if (!fg.d || node < 0 || node >= fg.N) return nullptr;
+    const int32_t r = fg.pos[node];
+    return r < 0 ? nullptr : fg.d + (size_t)r * Fn;
 }
 __device__ __forceinline__ float dot4(const f4 a, const f4 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w))); }
 
@@ -228,12 +235,13 @@ __global__ __launch_bounds__(256) void k_tt_ln_bwd(const float* __restrict__ dy,
 //   dp~_ijh = dz_ih . x_ij ; dp = dp~ * mask (dropout of :187) ; ds_ijh = p (dp - sum_j p dp), zero where the slot is masked (the -1e10 fill
 //   cuts the score off; the probability of a masked slot is still used, so padded slots do get dx) ;
 //   d(W_k,h^T q_ih) = scale sum_j ds_ijh x_ij ;  dx_ij = sum_h p~_ijh dz_ih + scale ds_ijh (W_k,h^T q_ih).
-// dx's h_lower columns are the gradient of the neighbour's level-(l-1) row (its only consumer: written, not added); its time columns give
+// dx's h_lower columns are the gradient of the neighbour's level-(l-1) row (its only consumer: written, not added; TGN's level 0: added to
+// the node's row of fg, one float atomic per element, skipped for nodes without a pending message); its time columns give
 // the time encoder's per-row partial sums (tdw, tdb [n][Ft]: -sin(pre) dt g, -sin(pre) g with the forward's pre = fma(dt, w, b)); the edge
 // columns are dropped (constants).  LDS: scale * ds [H][k], p~ [H][k].
 __global__ __launch_bounds__(64) void k_tt_attn_bwd(XRows X, const float* const* __restrict__ tabs, const float* __restrict__ qk, const float* __restrict__ P, const float* __restrict__ dz,
                                                       int H, float scale, train::Drop dr, uint32_t site, float* __restrict__ dqk, float* __restrict__ dh_lower,
-                                                      float* __restrict__ tdw, float* __restrict__ tdb) {
+                                                      float* __restrict__ tdw, float* __restrict__ tdb, const Feat0Grad fg) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x;
     const int64_t i = blockIdx.x;
@@ -302,10 +310,11 @@ __global__ __launch_bounds__(64) void k_tt_attn_bwd(XRows X, const float* const*
     for (int j = 0; j < k; ++j) {
         const int64_t r = i * k + j;
         const float d = X.dt[r];
+        float* frow = dh_lower ? nullptr : feat0_row(fg, X.ids_lower[X.n + r], Fn);      // wave-uniform
 #pragma unroll
         for (int u = 0; u < NC; ++u) {
             const int c4 = lane + 64 * u, kk = 4 * c4;
-            if (c4 >= D4 || (kk >= Fn && kk < Fn + Fe) || (kk < Fn && !dh_lower)) continue;
+            if (c4 >= D4 || (kk >= Fn && kk < Fn + Fe) || (kk < Fn && !dh_lower && !frow)) continue;
             f4 g = f4{0.f, 0.f, 0.f, 0.f};
             for (int h = 0; h < H; ++h) {
                 const f4 zv = reinterpret_cast<const f4*>(dz + ((size_t)i * H + h) * Dkv)[c4];
@@ -315,7 +324,11 @@ __global__ __launch_bounds__(64) void k_tt_attn_bwd(XRows X, const float* const*
                 g.z = fmaf(pt, zv.z, fmaf(ds, qv.z, g.z)); g.w = fmaf(pt, zv.w, fmaf(ds, qv.w, g.w));
             }
             if (kk < Fn) {
-                *reinterpret_cast<f4*>(dh_lower + (X.n + r) * Fn + kk) = g;
+                if (dh_lower) *reinterpret_cast<f4*>(dh_lower + (X.n + r) * Fn + kk) = g;
+                else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) atomicAdd(frow + kk + e, g[e]);
+                }
             } else {
                 const int f = kk - Fn - Fe;
 #pragma unroll
@@ -339,9 +352,10 @@ __global__ __launch_bounds__(64) void k_tt_attn_bwd(XRows X, const float* const*
 }
 
 // The query input's gradient dqin = [dh(self) | d cos(b)]: the h part is the self row's gradient at level l-1 (rows 0..n-1, its only
-// consumer), the time part adds -sin(b) g to the time encoder's bias partial sums (dt = 0: no weight term).  One thread per element.
+// consumer; TGN's level 0: added to the node's row of fg), the time part adds -sin(b) g to the time encoder's bias partial sums (dt = 0: no
+// weight term).  One thread per element.
 __global__ void k_tt_qin_bwd(const float* __restrict__ dqin, int64_t n, int Fn, int Ft, const float* __restrict__ tw, const float* __restrict__ tb,
-                             float* __restrict__ dh_lower, float* __restrict__ tdb) {
+                             float* __restrict__ dh_lower, float* __restrict__ tdb, const int32_t* __restrict__ ids_lower, const Feat0Grad fg) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int Dq = Fn + Ft;
     if (e >= n * Dq) return;
@@ -349,10 +363,20 @@ __global__ void k_tt_qin_bwd(const float* __restrict__ dqin, int64_t n, int Fn, 
     const int f = (int)(e - i * Dq);
     if (f < Fn) {
         if (dh_lower) dh_lower[i * Fn + f] = dqin[e];
+        else if (float* frow = feat0_row(fg, ids_lower[i], Fn)) atomicAdd(frow + f, dqin[e]);
     } else {
         const int t = f - Fn;
         tdb[i * Ft + t] = fmaf(-sinf(fmaf(0.0f, tw[t], tb[t])), dqin[e], tdb[i * Ft + t]);
     }
+}
+
+// TGN: rows g [n][Fn] (the MergeLayer's gradient with respect to its second input, feat0[ids[i]]) added to the nodes' rows of fg.
+// One thread per element.
+__global__ void k_tt_feat0_rows(const float* __restrict__ g, const int32_t* __restrict__ ids, int64_t n, int Fn, const Feat0Grad fg) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * Fn) return;
+    const int64_t i = e / Fn;
+    if (float* frow = feat0_row(fg, ids[i], Fn)) atomicAdd(frow + (e - i * Fn), g[e]);
 }
 
 // Column sums in a fixed order: out[c] += sum_r A[r][c].  Stage 1: one workgroup per 32 rows -> part[blk][c]; stage 2: the partials in
@@ -435,30 +459,16 @@ static int colsum(hipStream_t s, const float* A, int lda, int64_t rows, int cols
     return DYGNN_OK;
 }
 
-}  // namespace tgt
-}  // namespace dygnn
+size_t train_plan_bytes(const dygnn_tgat_config& cfg, int64_t batch) { return make_plan(cfg, batch).total; }
 
-using namespace dygnn;
-using namespace dygnn::tgt;
-
-extern "C" size_t dygnn_tgat_train_workspace_bytes(const dygnn_tgat_config* cfg, int64_t batch) {
-    if (check_train(cfg) != DYGNN_OK || batch < 1) return 0;
-    return make_plan(*cfg, batch).total;
+TrainLevel0 train_level0(const dygnn_tgat_config& cfg, int64_t batch, void* workspace) {
+    const TrainPlan p = make_plan(cfg, batch);
+    return TrainLevel0{reinterpret_cast<const int32_t*>(static_cast<char*>(workspace) + p.ids[0]), p.n[0], p.n[1]};
 }
 
-extern "C" int dygnn_tgat_train_forward(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_csr* csr, const dygnn_tgat_levels* levels,
-                                        const float* node_feat, const float* edge_feat, const int64_t* src, const int64_t* dst, const double* times,
-                                        int64_t batch, float dropout_p, uint64_t seed, float* out_src, float* out_dst, void* workspace,
-                                        size_t workspace_bytes, dygnn_stream_t stream) {
-    if (int rc = check_train(cfg)) return rc;
-    DYGNN_REQUIRE(w && w->time_w && w->time_b && node_feat && edge_feat, "tgat_train_forward: null pointer");
-    DYGNN_REQUIRE(batch > 0 && out_src && out_dst && workspace, "tgat_train_forward: bad arguments");
-    DYGNN_REQUIRE(levels || (csr && csr->indptr && csr->num_nodes >= 1 && src && dst && times), "tgat_train_forward: need levels or csr + src / dst / times");
-    DYGNN_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "tgat_train_forward: dropout must be in [0, 1)");
-    const TrainPlan p = make_plan(*cfg, batch);
-    if (workspace_bytes < p.total) { set_error("tgat_train_forward: workspace too small (%zu < %zu bytes)", workspace_bytes, p.total); return DYGNN_E_WORKSPACE; }
-    if (int rc = check_layer_weights(w, p.L, "tgat_train_forward: null layer weights")) return rc;
-    hipStream_t s = as_stream(stream);
+int train_levels(hipStream_t s, const dygnn_tgat_config& cfg, const dygnn_csr* csr, const dygnn_tgat_levels* levels, const int64_t* src, const int64_t* dst,
+                 const double* times, int64_t batch, void* workspace, const char* what) {
+    const TrainPlan p = make_plan(cfg, batch);
     char* ws = static_cast<char*>(workspace);
     auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     auto I32 = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
@@ -467,8 +477,15 @@ extern "C" int dygnn_tgat_train_forward(const dygnn_tgat_config* cfg, const dygn
     LevelBufs to{};
     for (int l = 0; l < p.L; ++l) { to.ids[l] = I32(p.ids[l]); to.times[l] = reinterpret_cast<double*>(ws + p.tms[l]); }
     for (int l = 1; l <= p.L; ++l) { to.eid[l] = I32(p.eid[l]); to.dt[l] = F32(p.dt[l]); }
-    if (int rc = levels ? copy_levels(s, levels, p.L, p.k, p.n, p.L, to, "tgat_train_forward")
-                        : expand_levels(s, csr, TgatRoots{src, dst, times, batch, false}, p.L, p.k, to)) return rc;
+    return levels ? copy_levels(s, levels, p.L, p.k, p.n, p.L, to, what) : expand_levels(s, csr, TgatRoots{src, dst, times, batch, false}, p.L, p.k, to);
+}
+
+int train_forward(hipStream_t s, const dygnn_tgat_config& cfg, const dygnn_tgat_weights* w, const float* node_feat, const float* edge_feat, int64_t batch,
+                  float dropout_p, uint64_t seed, float* out_src, float* out_dst, void* workspace) {
+    const TrainPlan p = make_plan(cfg, batch);
+    char* ws = static_cast<char*>(workspace);
+    auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    auto I32 = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
     hipLaunchKernelGGL(k_tt_tabs, dim3(1), dim3(1), 0, s, reinterpret_cast<const float**>(ws + p.tabs), node_feat, edge_feat);
     DYGNN_LAUNCH_CHECK();
     const train::Drop dr = train::make_drop(dropout_p, seed);
@@ -506,18 +523,10 @@ extern "C" int dygnn_tgat_train_forward(const dygnn_tgat_config* cfg, const dygn
     return DYGNN_OK;
 }
 
-extern "C" int dygnn_tgat_backward(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_tgat_weights* grads, const float* grad_out_src,
-                                   const float* grad_out_dst, int64_t batch, float dropout_p, uint64_t seed, void* workspace, size_t workspace_bytes,
-                                   dygnn_stream_t stream) {
-    if (int rc = check_train(cfg)) return rc;
-    DYGNN_REQUIRE(w && w->time_w && w->time_b && grads && grads->time_w && grads->time_b && grad_out_src && grad_out_dst && workspace && batch > 0,
-                  "tgat_backward: bad arguments");
-    DYGNN_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "tgat_backward: dropout must be in [0, 1)");
-    const TrainPlan p = make_plan(*cfg, batch);
-    if (workspace_bytes < p.total) { set_error("tgat_backward: workspace too small (%zu < %zu bytes)", workspace_bytes, p.total); return DYGNN_E_WORKSPACE; }
-    if (int rc = check_layer_weights(w, p.L, "tgat_backward: null layer weights")) return rc;
-    if (int rc = check_layer_weights(grads, p.L, "tgat_backward: null gradient buffer")) return rc;
-    hipStream_t s = as_stream(stream);
+int train_backward(hipStream_t s, const dygnn_tgat_config& cfg, const dygnn_tgat_weights* w, const dygnn_tgat_weights* grads, const float* grad_out_src,
+                   const float* grad_out_dst, int64_t batch, float dropout_p, uint64_t seed, void* workspace, const Feat0Grad* feat0) {
+    const TrainPlan p = make_plan(cfg, batch);
+    const Feat0Grad fg = feat0 ? *feat0 : Feat0Grad{nullptr, nullptr, 0};
     char* ws = static_cast<char*>(workspace);
     auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     auto I32 = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
@@ -538,13 +547,20 @@ extern "C" int dygnn_tgat_backward(const dygnn_tgat_config* cfg, const dygnn_tga
         const int64_t n = p.n[l];
         const int ni = (int)n;
         const float* h_lower = l >= 2 ? F32(p.lv[l - 1].h) : nullptr;
-        float* dlow = l >= 2 ? dh_low : nullptr;         // level 0 = raw features: no gradient
+        float* dlow = l >= 2 ? dh_low : nullptr;         // level 0: TGAT's raw features get no gradient, TGN's feat0 rows are summed per node (fg)
+        const int32_t* ids_lower = I32(p.ids[l - 1]);
         const uint32_t site_p = (uint32_t)(2 * (l - 1)), site_o = site_p + 1;
-        // 1. MergeLayer: fc2 -> ReLU -> fc1 (the raw-feature half of the merge input gets no gradient)
+        // 1. MergeLayer: fc2 -> ReLU -> fc1 (the second half of the merge input: TGAT's raw features get no gradient; TGN's feat0[ids[i]] does, at
+        //    every layer -- through p.datt, which step 3 writes only later)
         if (int rc = train::mm(s, dh, Fn, false, Lw.fc2_w, Fn, false, F32(p.dhid), Fn, ni, Fn, Fn)) return rc;
         hipLaunchKernelGGL(k_tt_relu_bwd, dim3((unsigned)ceil_div(n * Fn, 256)), dim3(256), 0, s, F32(p.dhid), F32(v.hid), n * Fn);
         DYGNN_LAUNCH_CHECK();
         if (int rc = train::mm(s, F32(p.dhid), Fn, false, Lw.fc1_w, Dq + Fn, false, F32(p.dy), Dq, ni, Dq, Fn)) return rc;
+        if (fg.d) {
+            if (int rc = train::mm(s, F32(p.dhid), Fn, false, Lw.fc1_w + Dq, Dq + Fn, false, F32(p.datt), Fn, ni, Fn, Fn)) return rc;
+            hipLaunchKernelGGL(k_tt_feat0_rows, dim3((unsigned)ceil_div(n * Fn, 256)), dim3(256), 0, s, F32(p.datt), ids_lower, n, Fn, fg);
+            DYGNN_LAUNCH_CHECK();
+        }
         // 2. LayerNorm + residual + residual_fc dropout
         hipLaunchKernelGGL(k_tt_ln_bwd, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, s, F32(p.dy), F32(v.pre), F32(v.mean), F32(v.rstd), Lw.ln_w, n, Dq, dr, site_o,
                            F32(p.dfc), F32(p.dqin), F32(p.dyx));
@@ -556,15 +572,15 @@ extern "C" int dygnn_tgat_backward(const dygnn_tgat_config* cfg, const dygnn_tga
         if (int rc = train::mm(s, F32(p.datt), Dq, false, Lw.value_w, Dkv, false, F32(p.dz), H * Dkv, ni, Dkv, hd, nullptr, 1.f, 0.f, H, H, 0, hd, 0,
                                (int64_t)hd * Dkv, 0, Dkv)) return rc;
         // 4. attention
-        const XRows X{h_lower, nullptr, nullptr, I32(p.ids[l - 1]), I32(p.eid[l]), F32(p.dt[l]), w->time_w, w->time_b, n, p.k, Fn, p.Fe, Ft, Dkv};
+        const XRows X{h_lower, nullptr, nullptr, ids_lower, I32(p.eid[l]), F32(p.dt[l]), w->time_w, w->time_b, n, p.k, Fn, p.Fe, Ft, Dkv};
         hipLaunchKernelGGL(k_tt_attn_bwd, dim3((unsigned)n), dim3(64), attn_lds, s, X, reinterpret_cast<const float* const*>(ws + p.tabs), F32(v.qk), F32(v.P),
-                           F32(p.dz), H, scale, dr, site_p, F32(p.dqk), dlow, F32(p.tdw), F32(p.tdb));
+                           F32(p.dz), H, scale, dr, site_p, F32(p.dqk), dlow, F32(p.tdw), F32(p.tdb), fg);
         DYGNN_LAUNCH_CHECK();
         // 5. W_k, W_q: dq_ih = W_k,h d(W_k,h^T q_ih); dqin += dq W_q
         if (int rc = train::mm(s, F32(p.dqk), H * Dkv, false, Lw.key_w, Dkv, true, F32(p.dq), Dq, ni, hd, Dkv, nullptr, 1.f, 0.f, H, H, 0, Dkv, 0,
                                (int64_t)hd * Dkv, 0, hd)) return rc;
         if (int rc = train::mm(s, F32(p.dq), Dq, false, Lw.query_w, Dq, false, F32(p.dqin), Dq, ni, Dq, Dq, nullptr, 1.f, 1.f)) return rc;
-        hipLaunchKernelGGL(k_tt_qin_bwd, dim3((unsigned)ceil_div(n * Dq, 256)), dim3(256), 0, s, F32(p.dqin), n, Fn, Ft, w->time_w, w->time_b, dlow, F32(p.tdb));
+        hipLaunchKernelGGL(k_tt_qin_bwd, dim3((unsigned)ceil_div(n * Dq, 256)), dim3(256), 0, s, F32(p.dqin), n, Fn, Ft, w->time_w, w->time_b, dlow, F32(p.tdb), ids_lower, fg);
         DYGNN_LAUNCH_CHECK();
         // 7. time encoder (shared by all layers and the query's cos(b)): per-row partials -> fixed-order column sums
         if (int rc = colsum(s, F32(p.tdw), Ft, n, Ft, F32(p.part), W(grads->time_w))) return rc;
@@ -585,4 +601,46 @@ extern "C" int dygnn_tgat_backward(const dygnn_tgat_config* cfg, const dygnn_tga
         float* t = dh; dh = dh_low; dh_low = t;
     }
     return DYGNN_OK;
+}
+
+}  // namespace tgt
+}  // namespace dygnn
+
+using namespace dygnn;
+using namespace dygnn::tgt;
+
+extern "C" size_t dygnn_tgat_train_workspace_bytes(const dygnn_tgat_config* cfg, int64_t batch) {
+    if (check_train(cfg) != DYGNN_OK || batch < 1) return 0;
+    return make_plan(*cfg, batch).total;
+}
+
+extern "C" int dygnn_tgat_train_forward(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_csr* csr, const dygnn_tgat_levels* levels,
+                                        const float* node_feat, const float* edge_feat, const int64_t* src, const int64_t* dst, const double* times,
+                                        int64_t batch, float dropout_p, uint64_t seed, float* out_src, float* out_dst, void* workspace,
+                                        size_t workspace_bytes, dygnn_stream_t stream) {
+    if (int rc = check_train(cfg)) return rc;
+    DYGNN_REQUIRE(w && w->time_w && w->time_b && node_feat && edge_feat, "tgat_train_forward: null pointer");
+    DYGNN_REQUIRE(batch > 0 && out_src && out_dst && workspace, "tgat_train_forward: bad arguments");
+    DYGNN_REQUIRE(levels || (csr && csr->indptr && csr->num_nodes >= 1 && src && dst && times), "tgat_train_forward: need levels or csr + src / dst / times");
+    DYGNN_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "tgat_train_forward: dropout must be in [0, 1)");
+    const size_t need = train_plan_bytes(*cfg, batch);
+    if (workspace_bytes < need) { set_error("tgat_train_forward: workspace too small (%zu < %zu bytes)", workspace_bytes, need); return DYGNN_E_WORKSPACE; }
+    if (int rc = check_layer_weights(w, cfg->num_layers, "tgat_train_forward: null layer weights")) return rc;
+    hipStream_t s = as_stream(stream);
+    if (int rc = train_levels(s, *cfg, csr, levels, src, dst, times, batch, workspace, "tgat_train_forward")) return rc;
+    return train_forward(s, *cfg, w, node_feat, edge_feat, batch, dropout_p, seed, out_src, out_dst, workspace);
+}
+
+extern "C" int dygnn_tgat_backward(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_tgat_weights* grads, const float* grad_out_src,
+                                   const float* grad_out_dst, int64_t batch, float dropout_p, uint64_t seed, void* workspace, size_t workspace_bytes,
+                                   dygnn_stream_t stream) {
+    if (int rc = check_train(cfg)) return rc;
+    DYGNN_REQUIRE(w && w->time_w && w->time_b && grads && grads->time_w && grads->time_b && grad_out_src && grad_out_dst && workspace && batch > 0,
+                  "tgat_backward: bad arguments");
+    DYGNN_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "tgat_backward: dropout must be in [0, 1)");
+    const size_t need = train_plan_bytes(*cfg, batch);
+    if (workspace_bytes < need) { set_error("tgat_backward: workspace too small (%zu < %zu bytes)", workspace_bytes, need); return DYGNN_E_WORKSPACE; }
+    if (int rc = check_layer_weights(w, cfg->num_layers, "tgat_backward: null layer weights")) return rc;
+    if (int rc = check_layer_weights(grads, cfg->num_layers, "tgat_backward: null gradient buffer")) return rc;
+    return train_backward(as_stream(stream), *cfg, w, grads, grad_out_src, grad_out_dst, batch, dropout_p, seed, workspace, nullptr);
 }

@@ -2,7 +2,8 @@
 `compute_src_dst_node_temporal_embeddings(src_node_ids, dst_node_ids, node_interact_times, edge_ids,
 edges_are_positive, num_neighbors)`, `set_neighbor_sampler`, `memory_bank.__init_memory_bank__ / backup_memory_bank /
 reload_memory_bank`, and the same state_dict keys.  The forward, the GRU memory update and the raw-message bookkeeping run
-in libdygnn_hip.so (`dygnn_tgn_forward`).  JODIE / DyRep are not built (not in BASELINE.json's configs)."""
+in libdygnn_hip.so (`dygnn_tgn_forward`).  In training mode with autograd recording the call is differentiable
+(`_TgnTrainFunction`: `dygnn_tgn_train_forward` / `dygnn_tgn_backward`).  JODIE / DyRep are not built (not in BASELINE.json's configs)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -57,10 +58,72 @@ class MemoryBank(nn.Module):
         self.msg, self.msg_time, self.has_msg = (x.clone() for x in backup_memory_bank[2])
 
     def detach_memory_bank(self):
-        """MemoryModel.py:368-378: nothing to detach, the HIP path builds no autograd graph."""
+        """MemoryModel.py:368-378.  The reference has to cut the graph here: its positive call writes GRU outputs and time encodings that
+        carry `grad_fn` into the memories and the raw-message lists.  On the HIP path that cannot happen, by construction and not by
+        omission: a training call (`_TgnTrainFunction`) hands the memory bank to the library as plain device buffers, the state commit is
+        outside the differentiated function (no loss of the current batch reads it, and the reference detaches it before the next one
+        does), and `node_memories` / `node_last_updated_times` stay `requires_grad=False` leaves.  So nothing here carries a graph from
+        batch to batch and the call is a no-op, kept so that the reference's training loop runs unchanged."""
 
     def get_memories(self, node_ids: np.ndarray):
         return self.node_memories[torch.from_numpy(np.asarray(node_ids))]
+
+
+class _TgnTrainFunction(torch.autograd.Function):
+    """compute_src_dst_node_temporal_embeddings with gradients: forward = dygnn_tgn_train_forward (which also commits the state of the
+    positive pairs, with the inference path's code), backward = dygnn_tgn_backward.  The parameters are passed as inputs only so that
+    autograd routes their gradients; the workspace belongs to this one call (a training step issues a negative and a positive call before
+    one backward(), and the negative call's backward runs after the positive call has rewritten the memory bank: the workspace holds
+    copies of what the GRU read)."""
+
+    @staticmethod
+    def forward(ctx, model, src, dst, tms, eids, n_pos, num_neighbors, dropout_p, seed, levels, *params):
+        dev = src.device
+        B = src.numel()
+        lib = model._lib
+        cfg, w, gru = model._config_and_weights(num_neighbors)
+        nbytes = lib.dygnn_tgn_train_workspace_bytes(C.byref(cfg), model.num_nodes, B)
+        if nbytes == 0:
+            _capi.check(-3)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)          # lives until this call's backward
+        out = (torch.empty((B, model.node_feat_dim), dtype=torch.float32, device=dev), torch.empty((B, model.node_feat_dim), dtype=torch.float32, device=dev))
+        lv = C.byref(levels[0]) if levels is not None else None
+        csr = None if levels is not None else model.embedding_module.neighbor_sampler.csr.on_device(dev)
+        st = model._state()
+        _capi.check(lib.dygnn_tgn_train_forward(C.byref(cfg), C.byref(w), C.byref(gru), csr, lv, model.node_raw_features.data_ptr(),
+                                                model.edge_raw_features.data_ptr(), C.byref(st), src.data_ptr(), dst.data_ptr(), tms.data_ptr(),
+                                                eids.data_ptr() if eids is not None else None, B, int(n_pos), float(dropout_p), int(seed),
+                                                out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), nbytes, _capi.current_stream_ptr()))
+        if levels is not None:
+            torch.cuda.current_stream(dev).synchronize()          # the level tensors may be freed afterwards
+        ctx.model, ctx.cfg, ctx.w, ctx.gru, ctx.ws, ctx.B, ctx.dropout_p, ctx.seed = model, cfg, w, gru, ws, B, float(dropout_p), int(seed)
+        ctx.feats = model.edge_raw_features                                   # read again by the backward pass
+        ctx.param_versions = [(p.data_ptr(), p._version) for p in params]
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_src, g_dst):
+        model = ctx.model
+        dev = ctx.ws.device
+        g_src = (g_src if g_src is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
+        g_dst = (g_dst if g_dst is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
+        params = model._param_list()
+        # the backward pass re-reads the CURRENT parameter values: they must be the ones the forward used
+        if [(p.data_ptr(), p._version) for p in params] != ctx.param_versions:
+            raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
+                               "a TGN parameter changed between this call's forward and its backward")
+        sizes = [p.numel() for p in params]
+        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)       # one fill for all gradient buffers
+        grads = [g.view_as(p) for g, p in zip(flat.split(sizes), params)]
+        by_id = {id(p): g for p, g in zip(params, grads)}
+        em, cell = model.embedding_module, model.memory_updater.memory_updater
+        gstruct = _tgat_weights(model.time_encoder, em.temporal_conv_layers, em.merge_layers, model.num_layers, by_id)
+        ggru = _capi.GruGrads(*(by_id[id(p)].data_ptr() for p in (cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh)))
+        _capi.check(model._lib.dygnn_tgn_backward(C.byref(ctx.cfg), C.byref(ctx.w), C.byref(ctx.gru), C.byref(gstruct), C.byref(ggru), g_src.data_ptr(),
+                                                  g_dst.data_ptr(), model.num_nodes, ctx.B, ctx.dropout_p, ctx.seed, ctx.ws.data_ptr(), ctx.ws.numel(),
+                                                  _capi.current_stream_ptr()))
+        ctx.ws = ctx.feats = None
+        return (None,) * 10 + tuple(grads)
 
 
 class GRUMemoryUpdater(nn.Module):
@@ -125,7 +188,9 @@ class MemoryModel(nn.Module):
         """The negative call and the positive call of one batch (evaluate_models_utils.py:85-107) as ONE library call: both read the
         same state and only the positive call writes it, at its end, so [positives ; negatives] is one batch whose first half updates the
         memory bank (dygnn_tgn_forward_step).  Returns (src_emb, dst_emb, neg_src_emb, neg_dst_emb), bit-identical to
-        compute_src_dst_node_temporal_embeddings(neg..., edges_are_positive=False) followed by (...pos..., edges_are_positive=True)."""
+        compute_src_dst_node_temporal_embeddings(neg..., edges_are_positive=False) followed by (...pos..., edges_are_positive=True).
+        In training mode with autograd recording it is one differentiable call: the training forward computes every level entry as its own
+        row, so each of the 2B rows still draws its own dropout masks, as in the reference's two calls."""
         cat = lambda a, b: (torch.cat([a, b]) if isinstance(a, torch.Tensor) else np.concatenate([np.asarray(a), np.asarray(b)]))
         n_pos = len(src_node_ids)
         if self.embedding_module.neighbor_sampler.sample_neighbor_strategy != "recent":
@@ -152,11 +217,14 @@ class MemoryModel(nn.Module):
     def compute_src_dst_node_temporal_embeddings(self, src_node_ids, dst_node_ids, node_interact_times, edge_ids,
                                                  edges_are_positive: bool = True, num_neighbors: int = 20, _n_positive: int = None
                                                  ) -> Tuple[torch.Tensor, torch.Tensor]:
-        """MemoryModel.py:87-168 (TGN).  Positive calls mutate the memory bank: issue batches in chronological order."""
-        if torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters())):
+        """MemoryModel.py:87-168 (TGN).  Positive calls mutate the memory bank: issue batches in chronological order.  With autograd
+        recording in training mode the call is differentiable (_TgnTrainFunction; dropout `self.dropout`): the attention, merge-layer,
+        time-encoder and GRUCell parameters receive gradients, the memory bank never does."""
+        train = torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters()))
+        if train and not self.training:
             # eval mode with autograd recording would return tensors without a graph: loss.backward() would silently do nothing
-            raise NotImplementedError("MemoryModel forward with autograd recording (training) is not built on the HIP path (SURVEY.md §8f-1): "
-                                      "call it under torch.no_grad()")
+            raise NotImplementedError("MemoryModel forward with autograd recording in eval mode is not built on the HIP path: call it under "
+                                      "torch.no_grad(), or use model.train() (with model.dropout = 0.0 for dropout-free gradients)")
         sampler = self.embedding_module.neighbor_sampler
         random_strategy = sampler.sample_neighbor_strategy != "recent"
         if random_strategy and _n_positive is not None:
@@ -183,22 +251,24 @@ class MemoryModel(nn.Module):
         if edges_are_positive:
             assert edge_ids is not None                                                        # MemoryModel.py:140
         eids = _to_dev(edge_ids, torch.int64, dev) if edge_ids is not None else None
+        n_pos = (B if edges_are_positive else 0) if _n_positive is None else int(_n_positive)
+        if eids is not None and eids.numel() < n_pos:
+            raise AssertionError("edge_ids must cover the positive edges")
+        if train and B > 0:
+            p_drop, seed = self._dropout_and_seed()
+            levels = None
+            if random_strategy:       # the RandomState is consumed exactly as by an inference call
+                h = lambda x: x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+                levels = self._sample_levels_host(h(src_node_ids).astype(np.int64), h(dst_node_ids).astype(np.int64),
+                                                  h(node_interact_times).astype(np.float64), int(num_neighbors), dev)
+            return _TgnTrainFunction.apply(self, src, dst, tms, eids, n_pos, int(num_neighbors), p_drop, seed, levels, *self._param_list())
         out = torch.empty((2, B, self.node_feat_dim), dtype=torch.float32, device=dev)      # one block: the library writes it in place
         out_src, out_dst = out[0], out[1]
         if B == 0:
             return out_src, out_dst
-        cfg = _capi.TgatConfig(self.node_feat_dim, self.edge_feat_dim, self.time_feat_dim, self.num_layers, self.num_heads, int(num_neighbors))
-        em = self.embedding_module
-        w = _tgat_weights(self.time_encoder, em.temporal_conv_layers, em.merge_layers, self.num_layers)
-        cell = self.memory_updater.memory_updater
-        gru = _capi.GruWeights(cell.weight_ih.data_ptr(), cell.weight_hh.data_ptr(), cell.bias_ih.data_ptr(), cell.bias_hh.data_ptr())
-        mb = self.memory_bank
-        st = _capi.TgnState(self.num_nodes, mb.node_memories.data_ptr(), mb.node_last_updated_times.data_ptr(), mb.msg.data_ptr(),
-                            mb.msg_time.data_ptr(), mb.has_msg.data_ptr())
+        cfg, w, gru = self._config_and_weights(num_neighbors)
+        st = self._state()
         ws = _workspace(self._workspace, self._lib.dygnn_tgn_workspace_bytes(C.byref(cfg), self.num_nodes, B), B, num_neighbors, dev)
-        n_pos = (B if edges_are_positive else 0) if _n_positive is None else int(_n_positive)
-        if eids is not None and eids.numel() < n_pos:
-            raise AssertionError("edge_ids must cover the positive edges")
         if random_strategy:
             # MemoryModel.py:626-629 with `uniform` / `time_interval_aware`: the draws are replayed on the host in the reference's order and the
             # library runs on the pre-sampled levels (dygnn_tgn_forward_levels)
@@ -217,6 +287,33 @@ class MemoryModel(nn.Module):
                                                      B, n_pos, out_src.data_ptr(), out_dst.data_ptr(),
                                                      ws.data_ptr(), ws.numel(), _capi.current_stream_ptr()))
         return out_src, out_dst
+
+    def _config_and_weights(self, num_neighbors: int):
+        cfg = _capi.TgatConfig(self.node_feat_dim, self.edge_feat_dim, self.time_feat_dim, self.num_layers, self.num_heads, int(num_neighbors))
+        em = self.embedding_module
+        w = _tgat_weights(self.time_encoder, em.temporal_conv_layers, em.merge_layers, self.num_layers)
+        cell = self.memory_updater.memory_updater
+        gru = _capi.GruWeights(cell.weight_ih.data_ptr(), cell.weight_hh.data_ptr(), cell.bias_ih.data_ptr(), cell.bias_hh.data_ptr())
+        return cfg, w, gru
+
+    def _state(self) -> "_capi.TgnState":
+        mb = self.memory_bank
+        return _capi.TgnState(self.num_nodes, mb.node_memories.data_ptr(), mb.node_last_updated_times.data_ptr(), mb.msg.data_ptr(),
+                              mb.msg_time.data_ptr(), mb.has_msg.data_ptr())
+
+    def _param_list(self):
+        """The tensors the reference's loss.backward() gives a gradient to: everything but the memory bank."""
+        bank = {id(p) for p in self.memory_bank.parameters()}
+        return [p for p in self.parameters() if id(p) not in bank]
+
+    def _dropout_and_seed(self):
+        for p in self._param_list():
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise _capi.DygnnError("parameters must be contiguous float32")
+        seed = getattr(self, "_fixed_dropout_seed", None)             # tests pin the masks; normally torch.manual_seed governs them
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        return (float(self.dropout) if self.training else 0.0), seed
 
     # ---- random sampling strategies: the draws are replayed on the host in the reference's recursion order -------------------------------
     def _sample_levels_host(self, src: np.ndarray, dst: np.ndarray, t: np.ndarray, k: int, dev):

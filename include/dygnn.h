@@ -371,6 +371,38 @@ int dygnn_tgat_backward(const dygnn_tgat_config* cfg_host, const dygnn_tgat_weig
                         const float* grad_out_src, const float* grad_out_dst, int64_t batch, float dropout_p, uint64_t seed,
                         void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
 
+/* TGN training (models/MemoryModel.py:87-168 in TRAIN mode, trained by train_link_prediction.py:186-207, :242-264).
+ * dygnn_tgn_train_forward: the forward of dygnn_tgn_forward_step (`levels` == NULL: `recent` sampling on csr) or of dygnn_tgn_forward_levels
+ * (`levels` given: host-replayed random draws), its layers in train mode as dygnn_tgat_train_forward runs them (dropout on the attention
+ * probabilities and on the residual_fc output, masks keyed by `seed`, every level entry its own row) over feat0 = updated memory + raw
+ * features.  The first n_positive pairs are positive edges: their nodes' updated memories are persisted and their new raw messages stored by
+ * the code of the inference call, so the state a call leaves is bit-identical to the one dygnn_tgn_forward_step leaves, whatever dropout_p is.
+ * `workspace` (size from dygnn_tgn_train_workspace_bytes; 0 for configurations the call refuses) belongs to ONE call and holds everything the
+ * backward pass reads, including copies of the pending messages and stored memories the GRU consumed: dygnn_tgn_backward reads nothing of
+ * `state`, which a positive call (this one or a later one) has overwritten by then.  edge_feat must stay untouched until it returns.
+ * dygnn_tgn_backward (num_nodes = state->num_nodes of the forward call): `grads` as for dygnn_tgat_backward, `gru_grads` the four GRUCell
+ * tensors; all WRITABLE device buffers of the parameter shapes that MUST BE ZERO on entry.  On return each holds
+ * d(sum(out_src*grad_out_src) + sum(out_dst*grad_out_dst))/dparam: the layers and the time encoder through the attention, the GRUCell through
+ * the updated memories of the nodes that had a pending message (their message and stored memory are constants, MemoryModel.py:374-387,
+ * :461-487).  The gradient of a node's feat0 row is the sum over every place the call read it, accumulated with float atomics: parameter
+ * gradients are not bit-reproducible run to run; the forward outputs and the committed state are.  Nothing flows through the state commit
+ * or from call to call.  Configurations: those dygnn_tgn_forward_step and dygnn_tgat_train_forward both take. */
+typedef struct dygnn_gru_grads {            /* layout of dygnn_gru_weights, writable                                           */
+    float *weight_ih, *weight_hh;
+    float *bias_ih, *bias_hh;
+} dygnn_gru_grads;
+size_t dygnn_tgn_train_workspace_bytes(const dygnn_tgat_config* cfg_host, int64_t num_nodes, int64_t batch);
+int dygnn_tgn_train_forward(const dygnn_tgat_config* cfg_host, const dygnn_tgat_weights* w_host, const dygnn_gru_weights* gru_host,
+                            const dygnn_csr* csr_host, const dygnn_tgat_levels* levels_host /* NULL: recent */, const float* node_feat,
+                            const float* edge_feat, const dygnn_tgn_state* state_host, const int64_t* src, const int64_t* dst,
+                            const double* times, const int64_t* edge_ids /* [n_positive] */, int64_t batch, int64_t n_positive,
+                            float dropout_p, uint64_t seed, float* out_src, float* out_dst, void* workspace, size_t workspace_bytes,
+                            dygnn_stream_t stream);
+int dygnn_tgn_backward(const dygnn_tgat_config* cfg_host, const dygnn_tgat_weights* w_host, const dygnn_gru_weights* gru_host,
+                       const dygnn_tgat_weights* grads_host, const dygnn_gru_grads* gru_grads_host, const float* grad_out_src,
+                       const float* grad_out_dst, int64_t num_nodes, int64_t batch, float dropout_p, uint64_t seed,
+                       void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
+
 /* Caller-side link predictor, fused: sigmoid(MergeLayer(a,b)) with
  * MergeLayer = fc2(relu(fc1(cat(a,b)))) (models/modules.py:57-68; evaluate_models_utils.py:140-141).
  * a,b [n,dim]; fc1 [hidden, 2*dim]; fc2 [1,hidden]; out [n]. */
