@@ -16,7 +16,7 @@ import torch  # noqa: F401  (must be imported first: see module docstring)
 from . import _build
 
 DYGNN_MAX_LAYERS = 8
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 c_i32p = C.POINTER(C.c_int32)
 c_i64p = C.POINTER(C.c_int64)
@@ -79,6 +79,26 @@ class GruGrads(GruWeights):
 
 class TgnState(C.Structure):
     _fields_ = [("num_nodes", C.c_int64)] + [(n, C.c_void_p) for n in ("memory", "last_update", "msg", "msg_time", "has_msg")]
+
+
+class GraphmixerConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("node_feat_dim", "edge_feat_dim", "time_feat_dim", "num_tokens", "num_layers", "token_hidden_dim",
+                                         "channel_hidden_dim", "num_neighbors", "time_gap", "num_node_rows")]
+
+
+class MixerLayerWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("token_norm_w", "token_norm_b", "token_fc0_w", "token_fc0_b", "token_fc1_w", "token_fc1_b",
+                                          "channel_norm_w", "channel_norm_b", "channel_fc0_w", "channel_fc0_b", "channel_fc1_w", "channel_fc1_b")]
+
+
+class GraphmixerWeights(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("time_w", "time_b", "proj_w", "proj_b")] + [("layers", MixerLayerWeights * DYGNN_MAX_LAYERS)]
+                + [("output_w", C.c_void_p), ("output_b", C.c_void_p)])
+
+
+class GraphmixerTaps(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("projection", C.c_void_p), ("layer_out", C.c_void_p * DYGNN_MAX_LAYERS), ("token_mean", C.c_void_p),
+                ("node_term", C.c_void_p)]
 
 
 class DygformerTaps(C.Structure):
@@ -151,6 +171,10 @@ SIGNATURES = {
                                           C.c_int64, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dygnn_tgn_backward": (C.c_int, [C.POINTER(TgatConfig), C.POINTER(TgatWeights), C.POINTER(GruWeights), C.POINTER(TgatWeights), C.POINTER(GruGrads),
                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dygnn_graphmixer_check": (C.c_int, [C.POINTER(GraphmixerConfig)]),
+    "dygnn_graphmixer_workspace_bytes": (C.c_size_t, [C.POINTER(GraphmixerConfig), C.c_int64]),
+    "dygnn_graphmixer_forward": (C.c_int, [C.POINTER(GraphmixerConfig), C.POINTER(GraphmixerWeights), C.POINTER(Csr), C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(GraphmixerTaps), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dygnn_merge_layer_sigmoid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dygnn_merge_layer_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,

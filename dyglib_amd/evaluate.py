@@ -65,15 +65,16 @@ def evaluate_model_link_prediction(model_name: str, model: nn.Module, neighbor_s
                                    evaluate_neg_edge_sampler: NegativeEdgeSampler, evaluate_data, loss_func: nn.Module,
                                    num_neighbors: int = 20, time_gap: int = 2000, fuse_batches: int = 32, tgat_fuse_batches: int = 128
                                    ) -> Tuple[List[float], List[dict]]:
-    """evaluate_models_utils.py:18-153 for the models of this package (DyGFormer, TGAT, TGN): `model` is
+    """evaluate_models_utils.py:18-153 for the models of this package (DyGFormer, TGAT, TGN, GraphMixer): `model` is
     nn.Sequential(backbone, MergeLayer); returns (evaluate_losses, evaluate_metrics) = one float and one
     {'average_precision', 'roc_auc'} dict per batch, like the reference.
+    `time_gap` is GraphMixer's (the node encoder's window); the other models ignore it.
     `fuse_batches` batches form one launch; TGAT with `recent` sampling takes `tgat_fuse_batches`: its rows do not depend on the batch they are in,
     and the more batches a call holds the more of its level-1 (node, time) entries repeat and are computed once (128 batches per call: 1.4x the
     rate of 32; ~23 GB of level arrays and layer buffers at the Reddit shape — lower it on a smaller device)."""
     assert evaluate_neg_edge_sampler.seed is not None                           # evaluate_models_utils.py:35
     evaluate_neg_edge_sampler.reset_random_state()
-    if model_name not in ("DyGFormer", "TGAT", "TGN"):
+    if model_name not in ("DyGFormer", "TGAT", "TGN", "GraphMixer"):
         raise ValueError(f"Wrong value for model_name {model_name}!")
     model[0].set_neighbor_sampler(neighbor_sampler)
     model.eval()
@@ -98,6 +99,13 @@ def evaluate_model_link_prediction(model_name: str, model: nn.Module, neighbor_s
             # the positive call's (evaluate_models_utils.py:62-63), and level de-duplication (tgat.hip) computes every other repeated entry once
             catp = lambda c: np.concatenate([g[c] for g in groups_pos])
             se, de, ne = backbone.compute_step_embeddings(catp(0), catp(1), np.concatenate([g[1] for g in groups_neg]), catp(2), num_neighbors=num_neighbors)
+            prob = merge.link_probabilities(torch.cat([se, se]), torch.cat([de, ne])).reshape(2, n, B)
+        elif model_name == "GraphMixer":
+            # rows do not depend on the batch they are in: the n batches are ONE call on the roots [sources ; destinations ; negative destinations]
+            # (evaluate_models_utils.py:126-136 with time_gap; the negative call's sources are the positive call's)
+            catp = lambda c: np.concatenate([g[c] for g in groups_pos])
+            se, de, ne = backbone.compute_step_embeddings(catp(0), catp(1), np.concatenate([g[1] for g in groups_neg]), catp(2),
+                                                          num_neighbors=num_neighbors, time_gap=time_gap)
             prob = merge.link_probabilities(torch.cat([se, se]), torch.cat([de, ne])).reshape(2, n, B)
         elif model_name == "TGAT":      # random strategies consume the sampler's RandomState call by call: keep the reference's call order
             probs = []

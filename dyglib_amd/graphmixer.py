@@ -1,0 +1,187 @@
+"""Drop-in for the reference `GraphMixer` backbone (models/GraphMixer.py:9-160): same constructor, same
+`compute_src_dst_node_temporal_embeddings(src_node_ids, dst_node_ids, node_interact_times, num_neighbors, time_gap)` /
+`compute_node_temporal_embeddings` / `set_neighbor_sampler` signatures, same parameter names and shapes (a reference checkpoint
+loads with strict=True); the forward runs in libdygnn_hip.so (`dygnn_graphmixer_forward`, dyglib_amd/csrc/graphmixer.hip).
+
+Inference only (eval or train mode under torch.no_grad()) with `recent` neighbour sampling: with autograd recording the calls raise
+NotImplementedError (the training path: backward, dropout, autograd, is not built yet), and so does a sampler with a random strategy
+(the reference's evaluation forces `recent` for GraphMixer, evaluate_models_utils.py, and its training default is `recent`).
+
+The node encoder's `time_gap` most recent neighbours are read straight from the temporal CSR inside the kernel: no [n, time_gap] array
+exists on the host or on the device, and the call's workspace (n (K C + F_n) floats) does not depend on time_gap."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _capi
+from .modules import TimeEncoder
+from .neighbor_sampler import NeighborSampler
+from .tgat import _to_dev, _workspace
+
+
+class FeedForwardNet(nn.Module):
+    """Parameters of models/GraphMixer.py:163-191: ffn.0 = Linear(d, int(factor * d)), ffn.3 = Linear(int(factor * d), d)."""
+
+    def __init__(self, input_dim: int, dim_expansion_factor: float, dropout: float = 0.0):
+        super().__init__()
+        self.input_dim, self.dim_expansion_factor, self.dropout = input_dim, dim_expansion_factor, dropout
+        hidden = int(dim_expansion_factor * input_dim)
+        self.ffn = nn.Sequential(nn.Linear(input_dim, hidden), nn.GELU(), nn.Dropout(dropout), nn.Linear(hidden, input_dim), nn.Dropout(dropout))
+
+
+class MLPMixer(nn.Module):
+    """Parameters of models/GraphMixer.py:194-244."""
+
+    def __init__(self, num_tokens: int, num_channels: int, token_dim_expansion_factor: float = 0.5, channel_dim_expansion_factor: float = 4.0,
+                 dropout: float = 0.0):
+        super().__init__()
+        self.token_norm = nn.LayerNorm(num_tokens)
+        self.token_feedforward = FeedForwardNet(num_tokens, token_dim_expansion_factor, dropout)
+        self.channel_norm = nn.LayerNorm(num_channels)
+        self.channel_feedforward = FeedForwardNet(num_channels, channel_dim_expansion_factor, dropout)
+
+
+class GraphMixer(nn.Module):
+
+    def __init__(self, node_raw_features: np.ndarray, edge_raw_features: np.ndarray, neighbor_sampler: NeighborSampler,
+                 time_feat_dim: int, num_tokens: int, num_layers: int = 2, token_dim_expansion_factor: float = 0.5,
+                 channel_dim_expansion_factor: float = 4.0, dropout: float = 0.1, device: str = "cpu"):
+        super().__init__()
+        self.node_raw_features = torch.from_numpy(np.ascontiguousarray(node_raw_features, dtype=np.float32)).to(device)
+        self.edge_raw_features = torch.from_numpy(np.ascontiguousarray(edge_raw_features, dtype=np.float32)).to(device)
+        self.neighbor_sampler = neighbor_sampler
+        self.node_feat_dim = self.node_raw_features.shape[1]
+        self.edge_feat_dim = self.edge_raw_features.shape[1]
+        self.time_feat_dim = time_feat_dim
+        self.num_tokens = num_tokens
+        self.num_layers = num_layers
+        self.token_dim_expansion_factor = token_dim_expansion_factor
+        self.channel_dim_expansion_factor = channel_dim_expansion_factor
+        self.dropout = dropout
+        self.device = device
+        self.num_channels = self.edge_feat_dim
+        self.time_encoder = TimeEncoder(time_dim=time_feat_dim, parameter_requires_grad=False)      # frozen, but part of the state_dict
+        self.projection_layer = nn.Linear(self.edge_feat_dim + time_feat_dim, self.num_channels)
+        self.mlp_mixers = nn.ModuleList([MLPMixer(self.num_tokens, self.num_channels, token_dim_expansion_factor, channel_dim_expansion_factor, dropout)
+                                         for _ in range(num_layers)])
+        self.output_layer = nn.Linear(self.num_channels + self.node_feat_dim, self.node_feat_dim, bias=True)
+        self._lib = _capi.load()
+        self._workspace: Dict[tuple, torch.Tensor] = {}
+
+    def set_neighbor_sampler(self, neighbor_sampler: NeighborSampler):
+        """models/GraphMixer.py:152-160."""
+        self.neighbor_sampler = neighbor_sampler
+        if self.neighbor_sampler.sample_neighbor_strategy in ["uniform", "time_interval_aware"]:
+            assert self.neighbor_sampler.seed is not None
+            self.neighbor_sampler.reset_random_state()
+
+    # ---- the reference's entry points ------------------------------------------------------------------------------------------
+    def compute_src_dst_node_temporal_embeddings(self, src_node_ids, dst_node_ids, node_interact_times, num_neighbors: int = 20,
+                                                 time_gap: int = 2000) -> Tuple[torch.Tensor, torch.Tensor]:
+        """models/GraphMixer.py:52-68: two float32 tensors [B, node_feat_dim]; ONE library call on the roots [src ; dst]."""
+        (src, dst), tms = self._inputs((src_node_ids, dst_node_ids), node_interact_times)
+        B = src.numel()
+        out = self._forward(torch.cat([src, dst]), torch.cat([tms, tms]), num_neighbors, time_gap)
+        return out[:B], out[B:]
+
+    def compute_node_temporal_embeddings(self, node_ids, node_interact_times, num_neighbors: int = 20, time_gap: int = 2000,
+                                         taps: Optional[int] = None):
+        """models/GraphMixer.py:70-150: [n, node_feat_dim].  `taps` = r (not in the reference): also return the intermediates of the first r
+        roots, (embeddings, dict(projection, layer_out, token_mean, node_term)), for the parity tests."""
+        (nodes,), tms = self._inputs((node_ids,), node_interact_times)
+        return self._forward(nodes, tms, num_neighbors, time_gap, taps)
+
+    def compute_step_embeddings(self, src_node_ids, dst_node_ids, neg_dst_node_ids, node_interact_times, num_neighbors: int = 20,
+                                time_gap: int = 2000) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The positive and the negative call of an evaluation step (evaluate_models_utils.py:126-136) as ONE library call on the roots
+        [sources ; destinations ; negative destinations] at the batch times: the negative call's sources are the positive call's (:62-63), and a
+        root's row does not depend on the other roots of the call, so the three results are bit-identical to those of the two reference calls."""
+        (src, dst, neg), tms = self._inputs((src_node_ids, dst_node_ids, neg_dst_node_ids), node_interact_times)
+        B = src.numel()
+        out = self._forward(torch.cat([src, dst, neg]), torch.cat([tms, tms, tms]), num_neighbors, time_gap)
+        return out[:B], out[B:2 * B], out[2 * B:]
+
+    # ---- glue ------------------------------------------------------------------------------------------------------------------------
+    def _inputs(self, id_arrays, node_interact_times):
+        """Refuse what is not built (autograd recording, random sampling, a CPU model), validate host ids like the reference (IndexError),
+        and move ids (int64) and times (float64) to the model's device."""
+        if torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("GraphMixer is inference-only on the HIP path: call it under torch.no_grad().  Training (backward, dropout, "
+                                      "autograd) is the follow-up to this forward and is not built yet")
+        self.neighbor_sampler._check_strategy()
+        if self.neighbor_sampler.sample_neighbor_strategy != "recent":
+            raise NotImplementedError(f"GraphMixer on the HIP path samples on the device and supports sample_neighbor_strategy 'recent' only, not "
+                                      f"'{self.neighbor_sampler.sample_neighbor_strategy}'")
+        dev = self.output_layer.weight.device
+        if dev.type != "cuda":
+            raise _capi.DygnnError("dyglib_amd.GraphMixer runs on an MI355X only; there is no CPU fallback")
+        if self.node_raw_features.device != dev:
+            self.node_raw_features = self.node_raw_features.to(dev)
+            self.edge_raw_features = self.edge_raw_features.to(dev)
+        csr = self.neighbor_sampler.csr
+        if getattr(self, "_validated_csr", None) is not csr:
+            csr.check_tables(self.node_raw_features.shape[0], self.edge_raw_features.shape[0])
+            self._validated_csr = csr
+        for ids in id_arrays:
+            csr.check_query_ids(ids, limit=self.node_raw_features.shape[0])
+        parts = [_to_dev(ids, torch.int64, dev).reshape(-1) for ids in id_arrays]
+        tms = _to_dev(node_interact_times, torch.float64, dev).reshape(-1)
+        assert all(p.numel() == tms.numel() for p in parts)
+        return parts, tms
+
+    def _config(self, num_neighbors: int, time_gap: int) -> "_capi.GraphmixerConfig":
+        K, Cc = self.num_tokens, self.num_channels
+        return _capi.GraphmixerConfig(self.node_feat_dim, self.edge_feat_dim, self.time_feat_dim, K, self.num_layers,
+                                      int(self.token_dim_expansion_factor * K), int(self.channel_dim_expansion_factor * Cc),      # as FeedForwardNet
+                                      int(num_neighbors), int(time_gap), self.node_raw_features.shape[0])
+
+    def _weights(self) -> "_capi.GraphmixerWeights":
+        for p in self.parameters():
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise _capi.DygnnError("parameters must be contiguous float32")
+        w = _capi.GraphmixerWeights()
+        p = lambda t: t.data_ptr()
+        w.time_w, w.time_b = p(self.time_encoder.w.weight), p(self.time_encoder.w.bias)
+        w.proj_w, w.proj_b = p(self.projection_layer.weight), p(self.projection_layer.bias)
+        for l, m in enumerate(self.mlp_mixers):
+            L, tf, cf = w.layers[l], m.token_feedforward.ffn, m.channel_feedforward.ffn
+            L.token_norm_w, L.token_norm_b = p(m.token_norm.weight), p(m.token_norm.bias)
+            L.token_fc0_w, L.token_fc0_b, L.token_fc1_w, L.token_fc1_b = p(tf[0].weight), p(tf[0].bias), p(tf[3].weight), p(tf[3].bias)
+            L.channel_norm_w, L.channel_norm_b = p(m.channel_norm.weight), p(m.channel_norm.bias)
+            L.channel_fc0_w, L.channel_fc0_b, L.channel_fc1_w, L.channel_fc1_b = p(cf[0].weight), p(cf[0].bias), p(cf[3].weight), p(cf[3].bias)
+        w.output_w, w.output_b = p(self.output_layer.weight), p(self.output_layer.bias)
+        return w
+
+    def _forward(self, nodes: torch.Tensor, tms: torch.Tensor, num_neighbors: int, time_gap: int, taps: Optional[int] = None):
+        dev = nodes.device
+        n = nodes.numel()
+        cfg = self._config(num_neighbors, time_gap)
+        if self.num_layers > _capi.DYGNN_MAX_LAYERS or len(self.mlp_mixers) != self.num_layers:
+            raise NotImplementedError(f"graphmixer: num_layers {self.num_layers} not supported (1..{_capi.DYGNN_MAX_LAYERS})")
+        nbytes = self._lib.dygnn_graphmixer_workspace_bytes(C.byref(cfg), n)
+        if nbytes == 0:                                  # AssertionError (bad argument) or NotImplementedError (unsupported) with the library's message
+            _capi.check(self._lib.dygnn_graphmixer_check(C.byref(cfg)))
+        ws = _workspace(self._workspace, nbytes, n, num_neighbors, dev)
+        out = torch.empty((n, self.node_feat_dim), dtype=torch.float32, device=dev)
+        tap_struct, tap_out = None, None
+        if taps is not None:
+            r, K, Cc = min(int(taps), n), self.num_tokens, self.num_channels
+            new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+            tap_out = dict(projection=new(r, K, Cc), layer_out=[new(r, K, Cc) for _ in range(self.num_layers)], token_mean=new(r, Cc),
+                           node_term=new(r, self.node_feat_dim))
+            tap_struct = _capi.GraphmixerTaps()
+            tap_struct.rows = r
+            tap_struct.projection, tap_struct.token_mean, tap_struct.node_term = (tap_out[k].data_ptr() for k in ("projection", "token_mean", "node_term"))
+            for l, t in enumerate(tap_out["layer_out"]):
+                tap_struct.layer_out[l] = t.data_ptr()
+        if n > 0:
+            _capi.check(self._lib.dygnn_graphmixer_forward(C.byref(cfg), C.byref(self._weights()), self.neighbor_sampler.csr.on_device(dev),
+                                                           self.node_raw_features.data_ptr(), self.edge_raw_features.data_ptr(), nodes.data_ptr(),
+                                                           tms.data_ptr(), n, out.data_ptr(), C.byref(tap_struct) if tap_struct is not None else None,
+                                                           ws.data_ptr(), ws.numel(), _capi.current_stream_ptr()))
+        return out if taps is None else (out, tap_out)

@@ -280,3 +280,54 @@ def make_tgn_params(seed: int, num_nodes: int, num_layers: int = 1) -> Dict[str,
     out["memory_updater.memory_updater.bias_ih"] = rs.uniform(-b, b, (3 * Fn,)).astype(np.float32)
     out["memory_updater.memory_updater.bias_hh"] = rs.uniform(-b, b, (3 * Fn,)).astype(np.float32)
     return out
+
+
+def graphmixer_param_shapes(num_tokens: int, node_feat_dim: int = NODE_FEAT_DIM, edge_feat_dim: int = NODE_FEAT_DIM, time_feat_dim: int = 100,
+                            num_layers: int = 2, token_dim_expansion_factor: float = 0.5,
+                            channel_dim_expansion_factor: float = 4.0) -> Dict[str, Tuple[int, ...]]:
+    """state_dict of the reference GraphMixer (models/GraphMixer.py:41-50, :176-180, :208-214), in its order: 6 + 12 num_layers tensors."""
+    K, Cc = num_tokens, edge_feat_dim
+    Kh, Ch = int(token_dim_expansion_factor * K), int(channel_dim_expansion_factor * Cc)
+    shapes: Dict[str, Tuple[int, ...]] = {"time_encoder.w.weight": (time_feat_dim, 1), "time_encoder.w.bias": (time_feat_dim,),
+                                          "projection_layer.weight": (Cc, Cc + time_feat_dim), "projection_layer.bias": (Cc,)}
+    for l in range(num_layers):
+        p = f"mlp_mixers.{l}."
+        shapes[p + "token_norm.weight"] = (K,)
+        shapes[p + "token_norm.bias"] = (K,)
+        shapes[p + "token_feedforward.ffn.0.weight"] = (Kh, K)
+        shapes[p + "token_feedforward.ffn.0.bias"] = (Kh,)
+        shapes[p + "token_feedforward.ffn.3.weight"] = (K, Kh)
+        shapes[p + "token_feedforward.ffn.3.bias"] = (K,)
+        shapes[p + "channel_norm.weight"] = (Cc,)
+        shapes[p + "channel_norm.bias"] = (Cc,)
+        shapes[p + "channel_feedforward.ffn.0.weight"] = (Ch, Cc)
+        shapes[p + "channel_feedforward.ffn.0.bias"] = (Ch,)
+        shapes[p + "channel_feedforward.ffn.3.weight"] = (Cc, Ch)
+        shapes[p + "channel_feedforward.ffn.3.bias"] = (Cc,)
+    shapes["output_layer.weight"] = (node_feat_dim, Cc + node_feat_dim)
+    shapes["output_layer.bias"] = (node_feat_dim,)
+    return shapes
+
+
+def make_graphmixer_params(seed: int, num_tokens: int, num_layers: int = 2, node_feat_dim: int = NODE_FEAT_DIM, edge_feat_dim: int = NODE_FEAT_DIM,
+                           time_feat_dim: int = 100, token_dim_expansion_factor: float = 0.5,
+                           channel_dim_expansion_factor: float = 4.0) -> Dict[str, np.ndarray]:
+    """Deterministic float32 parameters in the style of make_tgat_params: LayerNorm weights 1 +- 0.1 and every bias non-zero, so a dropped
+    term shows in the output."""
+    rs = np.random.RandomState(seed)
+    out: Dict[str, np.ndarray] = {}
+    shapes = graphmixer_param_shapes(num_tokens, node_feat_dim, edge_feat_dim, time_feat_dim, num_layers, token_dim_expansion_factor,
+                                     channel_dim_expansion_factor)
+    for key, shape in shapes.items():
+        if key == "time_encoder.w.weight":
+            base = (1.0 / 10 ** np.linspace(0, 9, time_feat_dim, dtype=np.float32)).reshape(shape)
+            val = base * (1.0 + 0.01 * rs.uniform(-1, 1, size=shape))
+        elif key == "time_encoder.w.bias":
+            val = 0.1 * rs.uniform(-1, 1, size=shape)
+        elif "_norm." in key:
+            val = (1.0 if key.endswith("weight") else 0.0) + 0.1 * rs.uniform(-1, 1, size=shape)
+        else:
+            fan_in = shape[1] if len(shape) == 2 else out[key[:-4] + "weight"].shape[1]
+            val = rs.uniform(-1, 1, size=shape) / np.sqrt(fan_in)
+        out[key] = np.ascontiguousarray(val, dtype=np.float32)
+    return out

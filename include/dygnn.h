@@ -421,6 +421,66 @@ int dygnn_merge_layer_backward(const float* a, const float* b, int64_t n, int32_
                                float* workspace, dygnn_stream_t stream);
 
 
+/* ------------------------------------------------------------------------------------------
+ * GraphMixer.compute_node_temporal_embeddings (models/GraphMixer.py:70-150), eval mode, `recent` sampling, fp32.  Per root (v, t):
+ *   link encoder: the K = num_tokens most recent interactions before t (dygnn_sample_recent's layout: right-aligned, zero padded) as tokens
+ *     [edge_feat[eid] | cos(w dt + b)] (time features ZERO on padded slots, edge row edge_feat[0]), projection_layer, num_layers MLP-Mixer
+ *     blocks (token LayerNorm + FFN K -> token_hidden_dim -> K over the token axis, channel LayerNorm + FFN C -> channel_hidden_dim -> C,
+ *     exact GELU, residuals), mean over the K tokens;
+ *   node encoder: m = min(history length, time_gap) most recent neighbours: (1 / time_gap) (1 / m) sum node_feat[nbr] (+ node_feat[v]);
+ *     m = 0: node_feat[0] / time_gap (the reference's softmax over an all-masked row is uniform).  The neighbour rows are read straight from
+ *     the CSR row: no [n, time_gap] array exists, and the workspace does not depend on time_gap;
+ *   output_layer on [link part | node part].
+ * One call serves any list of roots ([src ; dst], [src ; dst ; neg_dst], ...); a root's row does not depend on the other roots.
+ * Configurations: feature dims multiples of 4, each <= 256; 2 <= num_tokens <= 32; 1 <= token_hidden_dim <= 16; channel_hidden_dim a
+ * multiple of 16, <= 1024; 1 <= num_layers <= DYGNN_MAX_LAYERS; time_gap >= 1.  Others: DYGNN_E_UNSUPPORTED.  num_neighbors <= 0,
+ * time_gap <= 0 and num_neighbors != num_tokens are DYGNN_E_INVALID.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct dygnn_graphmixer_config {
+    int32_t node_feat_dim, edge_feat_dim, time_feat_dim;   /* F_n, C = num_channels, F_t                                        */
+    int32_t num_tokens;                                    /* K: the length of the token LayerNorm / FFN                        */
+    int32_t num_layers;
+    int32_t token_hidden_dim;                              /* int(token_dim_expansion_factor * num_tokens)                      */
+    int32_t channel_hidden_dim;                            /* int(channel_dim_expansion_factor * C)                             */
+    int32_t num_neighbors;                                 /* of the call; must equal num_tokens                                */
+    int32_t time_gap;                                      /* G of the call                                                     */
+    int32_t num_node_rows;                                 /* rows of node_feat (root ids outside read row 0); 0: csr num_nodes */
+} dygnn_graphmixer_config;
+
+typedef struct dygnn_mixer_layer_weights {                 /* mlp_mixers.l.*, PyTorch [out,in] layout                           */
+    const float *token_norm_w, *token_norm_b;              /* token_norm.{weight,bias}                          [K]             */
+    const float *token_fc0_w, *token_fc0_b;                /* token_feedforward.ffn.0          [token_hidden,K],[token_hidden]  */
+    const float *token_fc1_w, *token_fc1_b;                /* token_feedforward.ffn.3          [K,token_hidden],[K]             */
+    const float *channel_norm_w, *channel_norm_b;          /* channel_norm.{weight,bias}                        [C]             */
+    const float *channel_fc0_w, *channel_fc0_b;            /* channel_feedforward.ffn.0    [channel_hidden,C],[channel_hidden]  */
+    const float *channel_fc1_w, *channel_fc1_b;            /* channel_feedforward.ffn.3    [C,channel_hidden],[C]               */
+} dygnn_mixer_layer_weights;
+
+typedef struct dygnn_graphmixer_weights {
+    const float *time_w, *time_b;                          /* time_encoder.w.{weight,bias}                   [F_t,1],[F_t]      */
+    const float *proj_w, *proj_b;                          /* projection_layer                             [C,C+F_t],[C]        */
+    dygnn_mixer_layer_weights layers[DYGNN_MAX_LAYERS];
+    const float *output_w, *output_b;                      /* output_layer                              [F_n,C+F_n],[F_n]       */
+} dygnn_graphmixer_weights;
+
+/* Optional intermediates of the first min(rows, n) roots (device buffers, each nullable) */
+typedef struct dygnn_graphmixer_taps {
+    int64_t rows;
+    float* projection;                                     /* [rows, K, C] projection_layer output                              */
+    float* layer_out[DYGNN_MAX_LAYERS];                    /* [rows, K, C] output of Mixer block l                              */
+    float* token_mean;                                     /* [rows, C]                                                         */
+    float* node_term;                                      /* [rows, F_n] node-encoder term BEFORE node_feat[v] is added        */
+} dygnn_graphmixer_taps;
+
+/* DYGNN_OK, or why dygnn_graphmixer_workspace_bytes returned 0 (message in dygnn_last_error) */
+int dygnn_graphmixer_check(const dygnn_graphmixer_config* cfg_host);
+/* n_roots * (K * C + F_n) floats (+ alignment): the token activations and the node-encoder term.  0 = the configuration is refused. */
+size_t dygnn_graphmixer_workspace_bytes(const dygnn_graphmixer_config* cfg_host, int64_t n_roots);
+int dygnn_graphmixer_forward(const dygnn_graphmixer_config* cfg_host, const dygnn_graphmixer_weights* w_host, const dygnn_csr* csr_host,
+                             const float* node_feat, const float* edge_feat, const int64_t* nodes, const double* times, int64_t n,
+                             float* out /* [n, F_n] */, const dygnn_graphmixer_taps* taps_host /* or NULL */,
+                             void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
+
 /* Evaluation metrics on the device, replacing the scikit-learn host round trip of
  * get_link_prediction_metrics / get_node_classification_metrics (utils/metrics.py:5-34; called per batch at
  * evaluate_models_utils.py:139-150 and per evaluation at :245-249).  predicts / labels: [n_groups, group_size] float32
