@@ -228,6 +228,8 @@ struct Args {
     int tab_off, tab_slots, tab_bits;   // co-occurrence table per pair (LDS word offset, slots = 2^bits; 0: counts by scanning the rows)
     const float* bias_x;          // [208] projection biases in model-dim order
     const float* outfrag;         // output layer as fragments [ceil(Fn/16) tiles][13 k-chunks]
+    const float* w2frag;          // pooled last layer (PL != 0): its W2 as fragments [13 n-tiles][50 k-chunks]
+    const float* b2_last;         // ... and its second FFN bias [200]
     LayerP layer[DYGNN_MAX_LAYERS];
     const float *outT, *outb;     // output layer: transposed [200][Fn], bias [Fn]
     float *out_src, *out_dst;
@@ -488,6 +490,27 @@ __device__ __forceinline__ void residual_dropped(f4 (&x)[kNT], const float* xin,
     }
 }
 
+// per-side sums over the 16 tokens of this wave's tile of the 13 register tiles: pool[wave][side][208] (lane c == 0 of every row stores)
+__device__ __forceinline__ void pool_sides(const f4 (&x)[kNT], float* pool, int wave, int c, int g, bool in_src, bool in_dst) {
+#pragma unroll
+    for (int i = 0; i < kNT; ++i) {
+        f4 vs = in_src ? x[i] : zero4();
+        f4 vd = in_dst ? x[i] : zero4();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { vs[r] = row_sum16(vs[r]); vd[r] = row_sum16(vd[r]); }
+        if (c == 0) {
+            *reinterpret_cast<f4*>(pool + (wave * 2 + 0) * kDP + 16 * i + 4 * g) = vs;
+            *reinterpret_cast<f4*>(pool + (wave * 2 + 1) * kDP + 16 * i + 4 * g) = vd;
+        }
+    }
+}
+// pooled last layer: where its sums live in the K/V region (dead from the last out-projection on)
+constexpr int kLdsGPool = 0;                        // [8 waves][2 sides][800] per-wave sums of gelu(h) over the wave's tokens = the K region
+constexpr int kLdsPool = kLdsV;                     // [8 waves][2 sides][208] per-wave sums of the residual
+constexpr int kLdsMean = kLdsPool + 8 * 2 * kDP;    // [4 columns][208] per-side token means, column = 2 * pair + side
+constexpr int kLdsMeanG = kLdsMean + 4 * kDP;       // [4 columns][800] per-side token means of gelu(h)
+static_assert(8 * 2 * kHid <= kLdsV && kLdsMeanG + 4 * kHid <= kLdsRing, "the pooled sums fit the K/V region");
+
 // ================================================================================================
 // TR = false: inference.  TR = true: the training forward — dropout at the reference's four sites per layer and every
 // activation the backward pass reads written to HBM as dense rows (a.tr); the residual stream is re-read from those rows after the
@@ -495,8 +518,15 @@ __device__ __forceinline__ void residual_dropped(f4 (&x)[kNT], const float* xin,
 // NW = waves per workgroup: 8 (two pairs of <= 64 tokens, or one of <= 128), or 4 = ONE pair of <= 64 tokens per workgroup, for calls of at most 256
 // pairs (the reference's own 200-pair call: 100 eight-wave workgroups would leave 156 CUs idle and run two waves per SIMD on the rest; 200
 // four-wave workgroups give every wave a matrix pipe of its own)
-template <int TPW, bool TR, int NW = 8>
+// PL (inference only): the LAST layer's second FFN product is taken after the per-side token mean instead of per token — nothing after
+// that layer is non-linear, so  mean_tok(x_L) = mean_tok(x1) + W2 . mean_tok(gelu(h)) + b2  (DyGFormer.py:181-192, :457-460):
+//   1  the product path: the last layer's FFN steps run W1 and GELU only and leave per-wave, per-side sums of gelu(h) in the K region; the
+//      stream (its own: the last layer carries W1 blocks only) ends there, and the epilogue multiplies the 4 (pair, side) means by W2
+//   2  a call whose taps ask for the last layer's per-token output: the same sums and the same epilogue — the embeddings are those of
+//      PL = 1 bit for bit — and, for the tap alone, the per-token W2 product from the full stream
+template <int TPW, bool TR, int NW = 8, int PL = 0>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(const Args a) {
+    static_assert(!(TR && PL != 0), "the training forward keeps the per-token form: its backward reads the per-token activations");
     constexpr int NP = NW / TPW;                 // pairs per workgroup
     constexpr int PT = 64 * NW / NP;             // threads per pair
     constexpr int NTHR = 64 * NW;
@@ -951,7 +981,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
         const LayerP& W = a.layer[l];
         TACC(T_MISC);
         float* b1s = misc + kMiscB1 + (l & 1) * kHid;
-        for (int i = tid; i < kHid; i += NTHR) b1s[i] = W.b1[i];
+        int tl = tid;
+        // (PL: tid + NTHR and the 64-bit form of lane * 4 below are formed where they are used, not kept — spilled — through the layers;
+        //  with both, <4, false, 8, 1> needs 243 VGPRs and no scratch, <8, false, 8, 1> spills the 2 VGPRs of the per-token form)
+        if constexpr (PL != 0) asm volatile("" : "+v"(tl));
+        for (int i = tl; i < kHid; i += NTHR) b1s[i] = W.b1[i];
         if (l == 0) __syncthreads();     // the re-zeroing of K/V above is complete before the first K/V rows are written
 
         f4 xn[kNT];
@@ -1207,6 +1241,37 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
         const uint32_t sk2 = TR ? a.tr.dr.site_key((uint32_t)(4 * l + 2)) : 0u;
         TACC(T_LN);
         ws.align26();
+        const bool last = PL != 0 && l == a.NL - 1;      // the pooled layer
+        const int ptok = 16 * tt + c;
+        if (last) {
+            // Every wave has passed the stage barriers of the last out-projection: K and V are dead.  The residual's per-side sums are
+            // taken here (x1: what the per-token form adds the FFN output to).
+            pool_sides(x, lds + kLdsPool, wave, c, g, ptok < Ts, ptok >= Ts && ptok < T);
+        }
+        const bool straddle = 16 * tt < Ts && Ts < 16 * (tt + 1);      // wave-uniform: the tile holds tokens of both sides
+        const bool dst_tile = 16 * tt >= Ts;
+        // sums of gelu(h) over the tile's tokens of either side (DPP row sums, as pool_sides); a tile of one side sums once: the other
+        // side's sum of zeros is zero, so the bits do not depend on which form ran
+        auto gelu_sums = [&](const f4 (&h)[2], int p) {
+            float* gp = lds + kLdsGPool + wave * 2 * kHid + 32 * p + 4 * g;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                f4 vs, vd;
+                if (straddle) {
+                    vs = ptok < Ts ? h[u] : zero4();
+                    vd = ptok >= Ts && ptok < T ? h[u] : zero4();
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { vs[r] = row_sum16(vs[r]); vd[r] = row_sum16(vd[r]); }
+                } else {
+                    f4 v = ptok < T ? h[u] : zero4();
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = row_sum16(v[r]);
+                    vs = dst_tile ? zero4() : v;
+                    vd = dst_tile ? v : zero4();
+                }
+                if (c == 0) { *reinterpret_cast<f4*>(gp + 16 * u) = vs; *reinterpret_cast<f4*>(gp + kHid + 16 * u) = vd; }
+            }
+        };
         // W1(p) | W2(p) per step; W2 accumulates straight into the residual registers (no separate FFN accumulator: 52 VGPRs fewer)
         constexpr bool XB = F3_XBAR && !TR;      // (the training forward has no registers to spare)
         f4 pre1[2];                      // first fragments of the next W1 block, read across the stage barrier in front of it
@@ -1234,6 +1299,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
                         *reinterpret_cast<f4*>(hp) = h[0]; *reinterpret_cast<f4*>(hp + 16) = h[1];
                     }
                 }
+                if (last) gelu_sums(h, p);
                 TACC(T_F_GELU);
             }
             f4 pre2[4];                  // first fragments of this step's W2 block (blocks sit at ring positions 0 / 26)
@@ -1244,6 +1310,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
             }
             ws.advance(26, (TR && active) ? 4 : 0);      // training: the four hpre / hact stores of this step stay in flight through the W2 block
             TACC(T_F_ADV1);
+            if (PL == 1 && last) {               // the pooled stream: this layer's blocks are W1 only
+                if (XB && active && p + 1 < 25) { pre1[0] = lds4(ringl + ws.pos * kFrag); pre1[1] = lds4(ringl + (ws.pos + 1) * kFrag); }      // the next W1 block
+                continue;
+            }
             if (active) {
                 ffn_w2(f2, h, ringl + ws.pos * kFrag, (XB && F3_XBAR > 1) ? pre2 : nullptr);
                 if (XB && p + 1 < 25) {
@@ -1255,6 +1325,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
             ws.advance(26);
             TACC(T_F_ADV2);
         }
+        if (!(PL == 1 && last)) {
         ws.fit(1);
         {
             const float* b2 = lds + kLdsRing + ws.pos * kFrag + 4 * g;
@@ -1268,40 +1339,77 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
         ws.advance(1);
         TACC(T_FFN);
         tap_store<TPW>(x, a.tap_layer[l], b, a.Tmax, T, tt, c, g);
+        }
     }
 
     TACC(T_MISC);
     // ================= per-side mean over tokens + output layer (DyGFormer.py:181-192) =================
-    __syncthreads();        // K/V are dead: reuse as scratch
+    __syncthreads();        // K/V are dead: reuse as scratch (PL: every wave's sums of the last layer are written)
     {
-        float* pool = Kb;                        // [wave][side][208]
+        float* pool = lds + kLdsPool;            // [wave][side][208]
         const int tok = 16 * tt + c;
-        const bool in_src = tok < Ts, in_dst = tok >= Ts && tok < T;
-#pragma unroll
-        for (int i = 0; i < kNT; ++i) {
-            f4 vs = in_src ? x[i] : zero4();
-            f4 vd = in_dst ? x[i] : zero4();
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { vs[r] = row_sum16(vs[r]); vd[r] = row_sum16(vd[r]); }
-            if (c == 0) {
-                *reinterpret_cast<f4*>(pool + (wave * 2 + 0) * kDP + 16 * i + 4 * g) = vs;
-                *reinterpret_cast<f4*>(pool + (wave * 2 + 1) * kDP + 16 * i + 4 * g) = vd;
-            }
+        int lane4 = lane * 4;
+        if constexpr (PL != 0) asm volatile("" : "+v"(lane4));
+        if constexpr (PL == 0) {
+            pool_sides(x, pool, wave, c, g, tok < Ts, tok >= Ts && tok < T);
+            TACC(T_POOL1);
+            __syncthreads();
         }
-        TACC(T_POOL1);
-        __syncthreads();
         TACC(T_POOL2);
         // mean[col][208], col = 2*pair + side (4 columns of the 16-wide B operand are used; the rest multiply zeros)
-        float* mean = Vb;
-        const int Td = T - Ts;
+        float* mean = lds + kLdsMean;
+        const int Tse = Ts, Td = T - Ts;
         for (int i = ptid; i < 2 * kDP; i += PT) {
             const int side = i / kDP, n = i % kDP;
             float s = 0.f;
 #pragma unroll
             for (int w = 0; w < TPW; ++w) s += pool[((pi * TPW + w) * 2 + side) * kDP + n];
-            const float mv = n < kD ? s / (float)(side ? Td : Ts) : 0.f;
+            const float mv = n < kD ? s / (float)(side ? Td : Tse) : 0.f;
             mean[pi * 2 * kDP + i] = mv;
             if constexpr (TR) { if (pair_ok && n < kD) a.tr.pooled[((int64_t)side * a.B + b) * kD + n] = mv; }
+        }
+        if constexpr (PL != 0) {
+            // mean_g[col][800]: the per-wave sums in the pair-local wave order, then the scale by 1 / T_side, then the product
+            const float* gpool = lds + kLdsGPool;
+            float* meang = lds + kLdsMeanG;
+            for (int i = ptid; i < 2 * kHid; i += PT) {
+                const int side = i / kHid, n = i % kHid;
+                float s = 0.f;
+#pragma unroll
+                for (int w = 0; w < TPW; ++w) if (16 * w < T) s += gpool[((pi * TPW + w) * 2 + side) * kHid + n];      // a wave without tokens wrote nothing
+                meang[pi * 2 * kHid + i] = s / (float)(side ? Td : Tse);
+            }
+            __syncthreads();
+            // mean[col] += W2 . mean_g[col] + b2 on the matrix cores: wave w owns model-dim tiles w, w + NW, ...; 50 k-chunks whose fragments
+            // (used by this wave only) come straight from global memory ten at a time, one group ahead.  One tile's sum is one fixed chain
+            // (even chunks in acc0, odd in acc1), whichever wave of whichever kernel shape runs it.
+            constexpr int GK = 10, NG = kHid / 16 / GK;
+            for (int it = wave; it < kNT; it += NW) {
+                const float* fp = a.w2frag + (size_t)it * (kHid / 16) * kFrag + lane4;
+                f4 fa[2][GK];
+#pragma unroll
+                for (int u = 0; u < GK; ++u) fa[0][u] = ldg4(fp + (size_t)u * kFrag);
+                const int n0 = 16 * it + 4 * g;
+                f4 acc0 = n0 < kD ? ldg4(a.b2_last + n0) : zero4(), acc1 = zero4();
+#pragma unroll
+                for (int gk = 0; gk < NG; ++gk) {
+                    if (gk + 1 < NG) {
+#pragma unroll
+                        for (int u = 0; u < GK; ++u) fa[(gk + 1) & 1][u] = ldg4(fp + (size_t)((gk + 1) * GK + u) * kFrag);
+                    }
+#pragma unroll
+                    for (int u = 0; u < GK; ++u) {
+                        const f4 fr = fa[gk & 1][u];
+                        const f4 bm = c < 2 * NP ? lds4(meang + c * kHid + 16 * (gk * GK + u) + 4 * g) : zero4();
+                        if (u & 1) { acc1 = mfma(fr.x, bm.x, acc1); acc1 = mfma(fr.y, bm.y, acc1); acc1 = mfma(fr.z, bm.z, acc1); acc1 = mfma(fr.w, bm.w, acc1); }
+                        else { acc0 = mfma(fr.x, bm.x, acc0); acc0 = mfma(fr.y, bm.y, acc0); acc0 = mfma(fr.z, bm.z, acc0); acc0 = mfma(fr.w, bm.w, acc0); }
+                    }
+                }
+                if (c < 2 * NP) {        // this lane alone owns rows n0 .. n0 + 3 of column c (written before this barrier, read after the next)
+                    f4* mp = reinterpret_cast<f4*>(mean + c * kDP + n0);
+                    *mp = *mp + (acc0 + acc1);
+                }
+            }
         }
         __syncthreads();
         // output layer on the matrix cores: out^T[j][col] = sum_k W[j][k] mean[col][k] + b[j]; wave w owns output tiles w, w+8, ...
@@ -1310,7 +1418,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
         for (int jt = wave; jt < ntile; jt += NW) {
             f4 fa[kKC];
 #pragma unroll
-            for (int kc = 0; kc < kKC; ++kc) fa[kc] = ldg4(a.outfrag + ((size_t)jt * kKC + kc) * kFrag + lane * 4);
+            for (int kc = 0; kc < kKC; ++kc) fa[kc] = ldg4(a.outfrag + ((size_t)jt * kKC + kc) * kFrag + lane4);
             const int j0 = 16 * jt + 4 * g;
             f4 acc0 = j0 < a.Fn ? ldg4(a.outb + j0) : zero4(), acc1 = zero4();
 #pragma unroll
@@ -1887,7 +1995,7 @@ __global__ void k_pack_stream(const FragDesc* __restrict__ desc, int64_t nfrag, 
 
 // every fragment stream of the packed buffer in ONE launch (the in-place refresh after an optimizer step): the descriptor table is one
 // array, `r` maps its ranges to their destinations
-struct PackRanges { int n; int64_t start[4 + 2 * DYGNN_MAX_LAYERS]; float* dst[3 + 2 * DYGNN_MAX_LAYERS]; };
+struct PackRanges { int n; int64_t start[6 + 2 * DYGNN_MAX_LAYERS]; float* dst[5 + 2 * DYGNN_MAX_LAYERS]; };
 __global__ void k_pack_ranges(const FragDesc* __restrict__ desc, const PackRanges r) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t f = idx >> 8;
@@ -1921,7 +2029,9 @@ struct StreamBuilder {
     void put_vec(const float* src, int off, int n) { put(src, -1, 0, n, off, 0); }     // floats [0, n) of the fragment = src[off ..]
 };
 
-static void build_stream(const Dims& d, const dygnn_dygformer_weights* w, StreamBuilder& sb, int (&nchunk)[4]) {
+// pooled: the stream of k_dygformer_fused3<.., PL = 1> — the last layer's FFN carries its W1 blocks only and ends with the last of them (that
+// layer's W2 and b2 are read by the epilogue: build_w2)
+static void build_stream(const Dims& d, const dygnn_dygformer_weights* w, StreamBuilder& sb, int (&nchunk)[4], bool pooled = false) {
     const int K[4] = {d.P * d.Fn, d.P * d.Fe, d.P * d.Ft, d.P * d.C};
     for (int ch = 0; ch < 4; ++ch) nchunk[ch] = (K[ch] + 15) / 16;
     for (int l = 0; l < d.NL; ++l) {
@@ -1965,6 +2075,10 @@ static void build_stream(const Dims& d, const dygnn_dygformer_weights* w, Stream
             for (int u = 0; u < 2; ++u)
                 for (int i = 0; i < kNT; ++i) sb.put(L.ffn1_weight, kHid, 16 * i, kD, 16 * (2 * p + u), kHid);
         };
+        if (pooled && l == d.NL - 1) {
+            for (int p = 0; p < 25; ++p) { put_w1(p); }
+            break;
+        }
         for (int p = 0; p < 25; ++p) { put_w1(p); put_w2(p); }
         sb.fit(1);
         sb.put_vec(L.ffn1_bias, 0, kD);
@@ -2038,6 +2152,13 @@ static void build_aux(const Dims& d, const dygnn_dygformer_weights* w, StreamBui
         for (int kc = 0; kc < kKC; ++kc) sb.put(w->output_w, kD, 16 * jt, d.Fn, 16 * kc, kD);
 }
 
+// the last layer's W2 for the pooled epilogue, laid out like the output layer: [13 n-tiles][50 k-chunks], each fragment read by one wave
+constexpr int64_t kW2Frags = (int64_t)kNT * (kHid / 16);
+static void build_w2(const Dims& d, const dygnn_dygformer_weights* w, StreamBuilder& sb) {
+    for (int i = 0; i < kNT; ++i)
+        for (int kc = 0; kc < kHid / 16; ++kc) sb.put(w->layers[d.NL - 1].ffn1_weight, kHid, 16 * i, kD, 16 * kc, kHid);
+}
+
 struct PackLayout3 {       // float offsets relative to PackedLayout.fused3
     size_t bias_x;
     size_t stream; int64_t nfrag; int nstages;     // ring stream: nfrag fragments, padded to whole stages (+ one of slack)
@@ -2048,11 +2169,13 @@ struct PackLayout3 {       // float offsets relative to PackedLayout.fused3
     int tab_off, tab_slots, tab_bits;              // co-occurrence table (long windows): LDS word offset, slots per pair
     size_t bwd[DYGNN_MAX_LAYERS]; int bwd_nstages;  // per layer: the backward stream of its FFN block (training only)
     size_t bwa[DYGNN_MAX_LAYERS]; int bwa_nstages; int64_t bwa_frags;      // ... and of its attention block
+    size_t stream_p; int64_t nfrag_p; int nstages_p;       // ring stream of the pooled inference kernels (build_stream, pooled)
+    size_t w2;                                     // ... and their last layer's W2 fragments (build_w2)
     size_t desc;           // FragDesc table (device copy), 8-byte aligned
     size_t total;
 };
 
-static int64_t stream_frags(const Dims& d) {
+static int64_t stream_frags(const Dims& d, bool pooled) {
     // fragment count of build_stream without touching weights: run the builder with null sources
     dygnn_dygformer_weights w{};
     static float dummy;
@@ -2063,8 +2186,24 @@ static int64_t stream_frags(const Dims& d) {
     for (int l = 0; l < d.NL; ++l) w.layers[l] = lw;
     StreamBuilder sb;
     int nchunk[4];
-    build_stream(d, &w, sb, nchunk);
+    build_stream(d, &w, sb, nchunk, pooled);
     return (int64_t)sb.frags.size();
+}
+// the same counts without running the builder on every forward call (make_layout3 is on the call path): they depend on the number of
+// layers alone, so both forms of every depth are counted once per process
+static int64_t stream_frags_cached(const Dims& d, bool pooled) {
+    struct Table { int64_t n[2][DYGNN_MAX_LAYERS + 1]; };
+    static const Table t = [] {
+        Table r{};
+        for (int nl = 1; nl <= DYGNN_MAX_LAYERS; ++nl) {
+            Dims dd{};
+            dd.NL = nl;
+            r.n[0][nl] = stream_frags(dd, false);
+            r.n[1][nl] = stream_frags(dd, true);
+        }
+        return r;
+    }();
+    return (d.NL >= 1 && d.NL <= DYGNN_MAX_LAYERS) ? t.n[pooled ? 1 : 0][d.NL] : stream_frags(d, pooled);
 }
 
 static PackLayout3 make_layout3(const Dims& d) {
@@ -2072,7 +2211,7 @@ static PackLayout3 make_layout3(const Dims& d) {
     size_t o = 0;
     auto take = [&](size_t n) { size_t r = o; o += (n + 63) & ~size_t(63); return r; };
     f.bias_x = take(kDP);
-    f.nfrag = stream_frags(d);
+    f.nfrag = stream_frags_cached(d, false);
     f.nstages = (int)((f.nfrag + kStage - 1) / kStage);
     f.stream = take((size_t)(f.nstages + 1) * kStage * kFrag);
     f.naux = (int64_t)((d.Fn + 15) / 16) * kKC;
@@ -2086,7 +2225,11 @@ static PackLayout3 make_layout3(const Dims& d) {
     f.bwa_frags = bwd_attn_frags();
     f.bwa_nstages = (int)((f.bwa_frags + kStage - 1) / kStage);
     for (int l = 0; l < d.NL; ++l) f.bwa[l] = take((size_t)(f.bwa_nstages + 1) * kStage * kFrag);
-    f.desc = take(((size_t)(f.nfrag + f.naux + f.nproj + d.NL * (kBwdFfnFrags + f.bwa_frags)) * sizeof(FragDesc) + 3) / 4);
+    f.nfrag_p = stream_frags_cached(d, true);
+    f.nstages_p = (int)((f.nfrag_p + kStage - 1) / kStage);
+    f.stream_p = take((size_t)(f.nstages_p + 1) * kStage * kFrag);
+    f.w2 = take((size_t)kW2Frags * kFrag);
+    f.desc = take(((size_t)(f.nfrag + f.naux + f.nproj + d.NL * (kBwdFfnFrags + f.bwa_frags) + f.nfrag_p + kW2Frags) * sizeof(FragDesc) + 3) / 4);
     // prologue LDS split: pairs per workgroup, window arrays (5 x 2 sides x Smax ints per pair), projection slab
     const int per_pair = 5 * 2 * ((d.Smax + 3) & ~3);
     f.np = 0; f.slab_in_ring = 0; f.scr_floats = 0; f.slab_chunks = 0; f.tab_off = 0; f.tab_slots = 0; f.tab_bits = 0;
@@ -2135,13 +2278,14 @@ int pack(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w
     hipLaunchKernelGGL(k_pack_bias4, dim3(1), dim3(256), 0, s, w->proj_node_b, w->proj_edge_b, w->proj_time_b, w->proj_cooc_b, base + f.bias_x);
     DYGNN_LAUNCH_CHECK();
     if (reuse_desc) {
-        // table order (as laid down by the full pack below): stream | aux | proj | NL x FFN backward | NL x attention backward
+        // table order (as laid down by the full pack below): stream | aux | proj | NL x FFN backward | NL x attention backward | pooled stream | W2
         PackRanges r{};
         int64_t o = 0;
         auto range = [&](int64_t nfr, float* dst) { r.start[r.n] = o; r.dst[r.n] = dst; ++r.n; o += nfr; };
         range(f.nfrag, base + f.stream); range(f.naux, base + f.aux); range(f.nproj, base + f.proj);
         for (int l = 0; l < d.NL; ++l) range(kBwdFfnFrags, base + f.bwd[l]);
         for (int l = 0; l < d.NL; ++l) range(f.bwa_frags, base + f.bwa[l]);
+        range(f.nfrag_p, base + f.stream_p); range(kW2Frags, base + f.w2);
         r.start[r.n] = o;
         hipLaunchKernelGGL(k_pack_ranges, dim3((unsigned)ceil_div(o * kFrag, 256)), dim3(256), 0, s, reinterpret_cast<const FragDesc*>(base + f.desc), r);
         DYGNN_LAUNCH_CHECK();
@@ -2190,6 +2334,18 @@ int pack(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w
                            base + f.bwa[l]);
         DYGNN_LAUNCH_CHECK();
     }
+    StreamBuilder sp;
+    build_stream(d, w, sp, nchunk, true);
+    if ((int64_t)sp.frags.size() != f.nfrag_p) { set_error("pack: pooled stream builder mismatch"); return DYGNN_E_INVALID; }
+    StreamBuilder sw;
+    build_w2(d, w, sw);
+    FragDesc* pdesc = bdesc + (int64_t)d.NL * (kBwdFfnFrags + f.bwa_frags);
+    DYGNN_HIP(hipMemcpyAsync(pdesc, sp.frags.data(), sp.frags.size() * sizeof(FragDesc), hipMemcpyHostToDevice, s));
+    DYGNN_HIP(hipMemcpyAsync(pdesc + f.nfrag_p, sw.frags.data(), sw.frags.size() * sizeof(FragDesc), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_pack_stream, dim3((unsigned)ceil_div(f.nfrag_p * kFrag, 256)), dim3(256), 0, s, pdesc, f.nfrag_p, base + f.stream_p);
+    DYGNN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_pack_stream, dim3((unsigned)ceil_div(kW2Frags * kFrag, 256)), dim3(256), 0, s, pdesc + f.nfrag_p, kW2Frags, base + f.w2);
+    DYGNN_LAUNCH_CHECK();
     DYGNN_HIP(hipStreamSynchronize(s));     // the descriptor tables are copied from this call's host vectors
     return DYGNN_OK;
 }
@@ -2228,6 +2384,7 @@ static int fused3_args(const Dims& d, const PackedLayout& pl, const dygnn_dygfor
         a.tap_layer[l] = taps ? taps->layer_out[l] : nullptr;
     }
     a.outfrag = base + f.aux;
+    a.w2frag = base + f.w2; a.b2_last = w->layers[d.NL - 1].ffn1_bias;
     a.projw = base + f.proj; a.proj_frags = (int)f.nproj; a.slab_chunks = f.slab_chunks; a.scr_floats = f.scr_floats;
     a.slab_in_ring = f.slab_in_ring;
     a.tab_off = f.tab_off; a.tab_slots = f.tab_slots; a.tab_bits = f.tab_bits;
@@ -2253,16 +2410,25 @@ int forward_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_
     PackLayout3 f;
     if (int rc = fused3_args(d, pl, w, packed, csr, node_feat, edge_feat, src, dst, times, B, G, out_src, out_dst, ws, wl, taps, a, f)) return rc;
     if (taps && taps->seq_lens) DYGNN_HIP(hipMemcpyAsync(taps->seq_lens, ws + wl.dims + 2 * sizeof(int32_t), 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    // per device and cheap: set on every call (a process may drive several GPUs, or call from several threads)
-    DYGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dygformer_fused3<4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-    DYGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dygformer_fused3<8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
     if (taps && taps->ev_kernel_start) DYGNN_HIP(hipEventRecord(static_cast<hipEvent_t>(taps->ev_kernel_start), s));
     a.pair_stride = (f.np == 2 && pair_stride > 0) ? pair_stride : 0;      // one pair per workgroup (128 tokens): nothing to share inside a workgroup
-    if (f.np == 2 && a.pair_stride == 0 && B <= kSmallBatchPairs && !small_off()) {      // a small call: one pair per four-wave workgroup
-        DYGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dygformer_fused3<4, false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        hipLaunchKernelGGL((k_dygformer_fused3<4, false, 4>), dim3((unsigned)B), dim3(256), kLdsBytes, s, a);
-    } else if (f.np == 2) hipLaunchKernelGGL((k_dygformer_fused3<4, false>), dim3((unsigned)(a.pair_stride ? a.pair_stride : (B + 1) / 2)), dim3(512), kLdsBytes, s, a);
-    else hipLaunchKernelGGL((k_dygformer_fused3<8, false>), dim3((unsigned)B), dim3(512), kLdsBytes, s, a);
+    // Inference runs the pooled last layer.  A call that taps the last layer's per-token output gets it from the full stream (PL = 2); its
+    // embeddings are the pooled ones bit for bit.  Every other call streams the pooled form (PL = 1).
+    const bool tap_last = taps && taps->layer_out[d.NL - 1] != nullptr;
+    if (!tap_last) { a.stream = packed + pl.fused3 + f.stream_p; a.nstages = f.nstages_p; }
+    const bool small = f.np == 2 && a.pair_stride == 0 && B <= kSmallBatchPairs && !small_off();      // a small call: one pair per four-wave workgroup
+    const unsigned grid = small || f.np != 2 ? (unsigned)B : (unsigned)(a.pair_stride ? a.pair_stride : (B + 1) / 2);
+    auto launch = [&](auto kern, unsigned threads) -> int {
+        // per device and cheap: set on every call (a process may drive several GPUs, or call from several threads)
+        DYGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), kLdsBytes, s, a);
+        return DYGNN_OK;
+    };
+    int rc;
+    if (small) rc = tap_last ? launch(k_dygformer_fused3<4, false, 4, 2>, 256) : launch(k_dygformer_fused3<4, false, 4, 1>, 256);
+    else if (f.np == 2) rc = tap_last ? launch(k_dygformer_fused3<4, false, 8, 2>, 512) : launch(k_dygformer_fused3<4, false, 8, 1>, 512);
+    else rc = tap_last ? launch(k_dygformer_fused3<8, false, 8, 2>, 512) : launch(k_dygformer_fused3<8, false, 8, 1>, 512);
+    if (rc) return rc;
     DYGNN_LAUNCH_CHECK();
     if (taps && taps->ev_kernel_stop) DYGNN_HIP(hipEventRecord(static_cast<hipEvent_t>(taps->ev_kernel_stop), s));
     return DYGNN_OK;
