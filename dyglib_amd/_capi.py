@@ -16,7 +16,8 @@ import torch  # noqa: F401  (must be imported first: see module docstring)
 from . import _build
 
 DYGNN_MAX_LAYERS = 8
-ABI_VERSION = 17
+ABI_VERSION = 18
+TABLE_NODE_ZERO, TABLE_EDGE_ZERO = 1, 2      # table_flags of dygnn_dygformer_forward_tables (include/dygnn.h)
 
 c_i32p = C.POINTER(C.c_int32)
 c_i64p = C.POINTER(C.c_int64)
@@ -136,6 +137,10 @@ SIGNATURES = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(DygformerTaps),
                                           C.c_int32, C.c_void_p]),
+    "dygnn_dygformer_forward_tables": (C.c_int, [C.POINTER(DygformerConfig), C.POINTER(DygformerWeights), C.c_void_p, C.POINTER(Csr),
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(DygformerTaps),
+                                                 C.c_int32, C.c_void_p, C.c_uint32]),
     "dygnn_tgat_workspace_bytes": (C.c_size_t, [C.POINTER(TgatConfig), C.c_int64]),
     "dygnn_tgat_forward_levels": (C.c_int, [C.POINTER(TgatConfig), C.POINTER(TgatWeights), C.POINTER(TgatLevels), C.c_void_p, C.c_void_p, C.c_int64,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -15,7 +15,7 @@ int pack_fused3(const Dims&, const PackedLayout&, const dygnn_dygformer_weights*
 int forward_fused3(const Dims&, const PackedLayout&, const dygnn_dygformer_weights*, const float* packed, const dygnn_csr*,
                    const float* node_feat, const float* edge_feat, const int64_t* src, const int64_t* dst, const double* times,
                    int64_t B, int64_t G, int64_t pair_stride, float* out_src, float* out_dst, char* ws, const WorkspaceLayout&,
-                   const dygnn_dygformer_taps*, hipStream_t);
+                   const dygnn_dygformer_taps*, uint32_t table_flags, hipStream_t);
 
 static int check_weights(const Dims& d, const dygnn_dygformer_weights* w) {
     DYGNN_REQUIRE(w != nullptr, "weights is NULL");
@@ -376,12 +376,13 @@ extern "C" int dygnn_dygformer_repack(const dygnn_dygformer_config* cfg, const d
     return pack_impl(cfg, w, packed, packed_bytes, stream, true, fused_only != 0);
 }
 
-extern "C" int dygnn_dygformer_forward(const dygnn_dygformer_config* cfg, const dygnn_dygformer_weights* w, const void* packed,
-                                       const dygnn_csr* csr, const float* node_feat, const float* edge_feat, const int64_t* src,
-                                       const int64_t* dst, const double* times, int64_t batch, int64_t group_size, int64_t pair_stride,
-                                       float* out_src, float* out_dst, void* workspace, size_t workspace_bytes, const dygnn_dygformer_taps* taps,
-                                       int32_t impl, dygnn_stream_t stream) {
+extern "C" int dygnn_dygformer_forward_tables(const dygnn_dygformer_config* cfg, const dygnn_dygformer_weights* w, const void* packed,
+                                              const dygnn_csr* csr, const float* node_feat, const float* edge_feat, const int64_t* src,
+                                              const int64_t* dst, const double* times, int64_t batch, int64_t group_size, int64_t pair_stride,
+                                              float* out_src, float* out_dst, void* workspace, size_t workspace_bytes, const dygnn_dygformer_taps* taps,
+                                              int32_t impl, dygnn_stream_t stream, uint32_t table_flags) {
     if (int rc = check_config(cfg)) return rc;
+    DYGNN_REQUIRE((table_flags & ~(uint32_t)(DYGNN_TABLE_NODE_ZERO | DYGNN_TABLE_EDGE_ZERO)) == 0, "forward: unknown table_flags bit");
     const Dims d = make_dims(*cfg);
     if (int rc = check_weights(d, w)) return rc;
     DYGNN_REQUIRE(csr && csr->indptr && csr->num_nodes >= 1, "forward: bad csr");
@@ -406,10 +407,21 @@ extern "C" int dygnn_dygformer_forward(const dygnn_dygformer_config* cfg, const 
         set_error("forward: token-owner fused kernel does not support this shape (D=%d H=%d tokens<=%d)", d.D, d.H, d.Tmax);
         return DYGNN_E_UNSUPPORTED;
     }
-    auto fn = forward_generic;
-    if (impl == 3 || (impl == 0 && can_fuse3)) fn = forward_fused3;
-    return fn(d, pl, w, static_cast<const float*>(packed), csr, node_feat, edge_feat, src, dst, times, batch, group_size, pair_stride, out_src, out_dst,
-              static_cast<char*>(workspace), wl, taps, as_stream(stream));
+    if (impl == 3 || (impl == 0 && can_fuse3))
+        return forward_fused3(d, pl, w, static_cast<const float*>(packed), csr, node_feat, edge_feat, src, dst, times, batch, group_size, pair_stride, out_src,
+                              out_dst, static_cast<char*>(workspace), wl, taps, table_flags, as_stream(stream));
+    // the generic path multiplies the tables as they are: the flags promise nothing it uses
+    return forward_generic(d, pl, w, static_cast<const float*>(packed), csr, node_feat, edge_feat, src, dst, times, batch, group_size, pair_stride, out_src,
+                           out_dst, static_cast<char*>(workspace), wl, taps, as_stream(stream));
+}
+
+extern "C" int dygnn_dygformer_forward(const dygnn_dygformer_config* cfg, const dygnn_dygformer_weights* w, const void* packed,
+                                       const dygnn_csr* csr, const float* node_feat, const float* edge_feat, const int64_t* src,
+                                       const int64_t* dst, const double* times, int64_t batch, int64_t group_size, int64_t pair_stride,
+                                       float* out_src, float* out_dst, void* workspace, size_t workspace_bytes, const dygnn_dygformer_taps* taps,
+                                       int32_t impl, dygnn_stream_t stream) {
+    return dygnn_dygformer_forward_tables(cfg, w, packed, csr, node_feat, edge_feat, src, dst, times, batch, group_size, pair_stride, out_src, out_dst,
+                                          workspace, workspace_bytes, taps, impl, stream, 0);
 }
 
 static int merge_forward(const float* a, const float* b, int64_t n, int32_t dim, int32_t hidden, const float* fc1_w, const float* fc1_b, const float* fc2_w,

@@ -145,6 +145,18 @@ __device__ __forceinline__ float row_sum16(float v) {
     v += dpp_mov<0x140>(v);
     return v;
 }
+// The same four additions for the per-side pooling sums (pool_sides, and gelu(h) in the pooled layer), each as ONE instruction.  Written as above, hipcc pairs the
+// additions of two sums into a v_pk_add_f32, which has no DPP form: every stage then costs a v_mov_b32_dpp per value plus the packed
+// add.  An empty asm on each stage's result keeps the sums scalar, and the DPP move folds into its add (v_add_f32_dpp): one VALU
+// instruction per value and stage instead of 1.5, same operands, same order, same bits.
+__device__ __forceinline__ float keep_scalar(float v) { asm("" : "+v"(v)); return v; }
+__device__ __forceinline__ float row_sum16_dpp(float v) {
+    v = keep_scalar(v + dpp_mov<0xB1>(v));
+    v = keep_scalar(v + dpp_mov<0x4E>(v));
+    v = keep_scalar(v + dpp_mov<0x141>(v));
+    v = keep_scalar(v + dpp_mov<0x140>(v));
+    return v;
+}
 
 // cos for the time encoder.  The argument w*dt+b reaches 2.7e6 rad where libm's cosf takes its slow Payne-Hanek path; here x/(2 pi) is
 // formed as a two-float product (INV_HI + INV_LO = 1/(2 pi) to 2^-52), its fractional part u in [0, 0.5] is folded to [0, 0.25] and
@@ -221,7 +233,8 @@ struct Args {
     const float *node_feat, *edge_feat, *time_w, *time_b, *lut;
     const float* stream; int nstages;
     const float* projw;           // projection fragments in step order [node | time | edge | cooc chunks][4 tiles]
-    int proj_frags;               // total projection fragments
+    int proj_frags;               // projection fragments this launch walks (the whole sequence, less the channels of all-zero tables)
+    int proj_skip0, proj_cut, proj_skip1;   // zero-table channels: walked fragment i is stored fragment i + proj_skip0 (+ proj_skip1 from i = proj_cut on)
     int slab_chunks;              // k-chunk slots per LDS HALF (a multiple of 4; two halves)
     int scr_floats;               // LDS floats reserved for the window arrays (the slab follows)
     int slab_in_ring;             // long windows (e.g. L = 2048): the slab borrows the weight ring, whose stream then opens after the prologue
@@ -497,7 +510,7 @@ __device__ __forceinline__ void pool_sides(const f4 (&x)[kNT], float* pool, int 
         f4 vs = in_src ? x[i] : zero4();
         f4 vd = in_dst ? x[i] : zero4();
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { vs[r] = row_sum16(vs[r]); vd[r] = row_sum16(vd[r]); }
+        for (int r = 0; r < 4; ++r) { vs[r] = row_sum16_dpp(vs[r]); vd[r] = row_sum16_dpp(vd[r]); }
         if (c == 0) {
             *reinterpret_cast<f4*>(pool + (wave * 2 + 0) * kDP + 16 * i + 4 * g) = vs;
             *reinterpret_cast<f4*>(pool + (wave * 2 + 1) * kDP + 16 * i + 4 * g) = vd;
@@ -579,7 +592,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
     auto load_half = [&](int q) {
         const int f0 = q * half_frags;
         const int n = a.proj_frags - f0 < half_frags ? a.proj_frags - f0 : half_frags;      // <= 0 beyond the last half
-        for (int f = wave; f < n; f += NW) dma_frag(a.projw + (size_t)(f0 + f) * kFrag + lane * 4, slab_off + ((q & 1) * half_frags + f) * kFrag);
+        // a channel whose table is all zero (Args.proj_skip*) is not part of the walked sequence: its stored fragments are stepped over here
+        for (int f = wave; f < n; f += NW) {
+            const int sf = f0 + f + a.proj_skip0 + (f0 + f >= a.proj_cut ? a.proj_skip1 : 0);
+            dma_frag(a.projw + (size_t)sf * kFrag + lane * 4, slab_off + ((q & 1) * half_frags + f) * kFrag);
+        }
     };
     load_half(0);
     load_half(1);
@@ -926,18 +943,21 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
         };
 
         // Channel order node, time, edge, cooc: the edge gathers are issued before the time channel computes its cosines.  A wave whose
-        // tile is empty, or a source tile shared with the first pair (f4), only keeps the barriers of the channel.
+        // tile is empty, or a source tile shared with the first pair (f4), only keeps the barriers of the channel.  A gathered channel
+        // whose table the caller declared all zero has nchunk = 0 (and no slots in the walked sequence): no gathers, no MFMAs, no
+        // barriers — its rows of x keep the projection bias they started from, which is what adding w . 0 leaves of them.
         const bool work = active && !src_shared;
+        const bool work_n = work && a.nchunk[0] > 0, work_e = work && a.nchunk[1] > 0;
         f4 bq[GS];
         Cursor cu;
-        if (work) prefill(bq, cu, a.node_feat, ids, a.Fn);
+        if (work_n) prefill(bq, cu, a.node_feat, ids, a.Fn);
         TACC(T_PROJ);
-        if (work) run_gathered(integral_constant<int, 0>{}, bq, cu, a.nchunk[0], a.node_feat, ids, a.Fn); else run_idle(a.nchunk[0]);
-        if (work) prefill(bq, cu, a.edge_feat, eids, a.Fe);            // in flight while the time channel runs
+        if (work_n) run_gathered(integral_constant<int, 0>{}, bq, cu, a.nchunk[0], a.node_feat, ids, a.Fn); else run_idle(a.nchunk[0]);
+        if (work_e) prefill(bq, cu, a.edge_feat, eids, a.Fe);          // in flight while the time channel runs
         TACC(T_PNODE);
         if (work) run_time(integral_constant<int, 6>{}, a.nchunk[2]); else run_idle(a.nchunk[2]);
         TACC(T_PTIME);
-        if (work) run_gathered(integral_constant<int, 3>{}, bq, cu, a.nchunk[1], a.edge_feat, eids, a.Fe); else run_idle(a.nchunk[1]);
+        if (work_e) run_gathered(integral_constant<int, 3>{}, bq, cu, a.nchunk[1], a.edge_feat, eids, a.Fe); else run_idle(a.nchunk[1]);
         TACC(T_PEDGE);
         if (active) run_cooc(integral_constant<int, 9>{}, a.nchunk[3]); else run_idle(a.nchunk[3]);
         TACC(T_PCOOC);
@@ -1261,11 +1281,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
                     vs = ptok < Ts ? h[u] : zero4();
                     vd = ptok >= Ts && ptok < T ? h[u] : zero4();
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) { vs[r] = row_sum16(vs[r]); vd[r] = row_sum16(vd[r]); }
+                    for (int r = 0; r < 4; ++r) { vs[r] = row_sum16_dpp(vs[r]); vd[r] = row_sum16_dpp(vd[r]); }
                 } else {
                     f4 v = ptok < T ? h[u] : zero4();
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = row_sum16(v[r]);
+                    for (int r = 0; r < 4; ++r) v[r] = row_sum16_dpp(v[r]);
                     vs = dst_tile ? zero4() : v;
                     vd = dst_tile ? v : zero4();
                 }
@@ -2395,20 +2415,33 @@ static int fused3_args(const Dims& d, const PackedLayout& pl, const dygnn_dygfor
     a.B = B; a.G = G; a.num_nodes = csr->num_nodes; a.Fn = d.Fn; a.Fe = d.Fe; a.Ft = d.Ft; a.P = d.P; a.L = d.L; a.NL = d.NL; a.Tmax = d.Tmax;
     const int K[4] = {d.P * d.Fn, d.P * d.Fe, d.P * d.Ft, d.P * d.C};
     for (int ch = 0; ch < 4; ++ch) a.nchunk[ch] = (K[ch] + 15) / 16;
+    a.proj_skip0 = 0; a.proj_skip1 = 0; a.proj_cut = 0;
     a.qscale = (float)sqrt(1.0 / (double)d.hd);
     return DYGNN_OK;
+}
+
+// table_flags (dygnn_dygformer_forward_tables): the stored fragment sequence is [node | time | edge | cooc], every channel in whole
+// groups of four slots (build_proj).  A channel whose table is all zero leaves the walk: its chunk count becomes 0 and the prologue's
+// DMA steps over its stored fragments.
+static void drop_zero_channels(v3::Args& a, uint32_t table_flags) {
+    using namespace v3;
+    const int node_frags = 4 * proj_slots(a.nchunk[0]), time_frags = 4 * proj_slots(a.nchunk[2]), edge_frags = 4 * proj_slots(a.nchunk[1]);
+    if (table_flags & DYGNN_TABLE_NODE_ZERO) { a.proj_skip0 = node_frags; a.proj_frags -= node_frags; a.nchunk[0] = 0; }
+    a.proj_cut = (a.nchunk[0] ? node_frags : 0) + time_frags;
+    if (table_flags & DYGNN_TABLE_EDGE_ZERO) { a.proj_skip1 = edge_frags; a.proj_frags -= edge_frags; a.nchunk[1] = 0; }
 }
 
 int forward_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, const float* packed,
                    const dygnn_csr* csr, const float* node_feat, const float* edge_feat, const int64_t* src,
                    const int64_t* dst, const double* times, int64_t B, int64_t G, int64_t pair_stride, float* out_src, float* out_dst, char* ws,
-                   const WorkspaceLayout& wl, const dygnn_dygformer_taps* taps, hipStream_t s) {
+                   const WorkspaceLayout& wl, const dygnn_dygformer_taps* taps, uint32_t table_flags, hipStream_t s) {
     using namespace v3;
     if (!supported(d)) { set_error("fused kernel: unsupported shape"); return DYGNN_E_UNSUPPORTED; }
     if (int rc = window_lengths_device(d, csr, src, dst, times, B, G, ws, wl, s)) return rc;
     Args a{};
     PackLayout3 f;
     if (int rc = fused3_args(d, pl, w, packed, csr, node_feat, edge_feat, src, dst, times, B, G, out_src, out_dst, ws, wl, taps, a, f)) return rc;
+    drop_zero_channels(a, table_flags);
     if (taps && taps->seq_lens) DYGNN_HIP(hipMemcpyAsync(taps->seq_lens, ws + wl.dims + 2 * sizeof(int32_t), 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     if (taps && taps->ev_kernel_start) DYGNN_HIP(hipEventRecord(static_cast<hipEvent_t>(taps->ev_kernel_start), s));
     a.pair_stride = (f.np == 2 && pair_stride > 0) ? pair_stride : 0;      // one pair per workgroup (128 tokens): nothing to share inside a workgroup

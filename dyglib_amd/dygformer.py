@@ -115,9 +115,11 @@ class DyGFormer(nn.Module):
                  time_feat_dim: int, channel_embedding_dim: int, patch_size: int = 1, num_layers: int = 2, num_heads: int = 2,
                  dropout: float = 0.1, max_input_sequence_length: int = 512, device: str = "cpu"):
         super().__init__()
-        # plain attributes, not buffers: they are not part of the state_dict (models/DyGFormer.py:32-33)
-        self.node_raw_features = torch.from_numpy(np.ascontiguousarray(node_raw_features, dtype=np.float32)).to(device)
-        self.edge_raw_features = torch.from_numpy(np.ascontiguousarray(edge_raw_features, dtype=np.float32)).to(device)
+        # plain attributes, not buffers: they are not part of the state_dict (models/DyGFormer.py:32-33).  Whether a table is all zero
+        # (the reference's preprocessing writes zero node features for every dataset) is established here, on the host arrays, once: the
+        # fused kernel then leaves that channel out of the patch projection (table_flags of dygnn_dygformer_forward_tables)
+        self._set_table("node", torch.from_numpy(np.ascontiguousarray(node_raw_features, dtype=np.float32)).to(device), not np.any(node_raw_features))
+        self._set_table("edge", torch.from_numpy(np.ascontiguousarray(edge_raw_features, dtype=np.float32)).to(device), not np.any(edge_raw_features))
 
         self.neighbor_sampler = neighbor_sampler
         self.node_feat_dim = self.node_raw_features.shape[1]
@@ -154,6 +156,34 @@ class DyGFormer(nn.Module):
         self._packed_key = None
         self._workspace: Dict[tuple, torch.Tensor] = {}
         self.impl = 0                      # 0 auto, 1 generic, 3 fused (see include/dygnn.h)
+
+    # ---- feature tables ------------------------------------------------------------------------
+    def _set_table(self, which: str, table: torch.Tensor, all_zero: Optional[bool] = None) -> None:
+        """Store a feature table with its "all zero" bit; all_zero=None looks at the tensor (one reduction, a host sync on a GPU)."""
+        self.__dict__["_" + which + "_raw_features"] = table
+        self.__dict__["_" + which + "_all_zero"] = bool(not table.any().item()) if all_zero is None else bool(all_zero)
+
+    @property
+    def node_raw_features(self) -> torch.Tensor:
+        return self.__dict__["_node_raw_features"]
+
+    @node_raw_features.setter
+    def node_raw_features(self, table: torch.Tensor) -> None:      # a new table: its bit is established again
+        self._set_table("node", table)
+
+    @property
+    def edge_raw_features(self) -> torch.Tensor:
+        return self.__dict__["_edge_raw_features"]
+
+    @edge_raw_features.setter
+    def edge_raw_features(self, table: torch.Tensor) -> None:
+        self._set_table("edge", table)
+
+    @property
+    def table_flags(self) -> int:
+        """table_flags of dygnn_dygformer_forward_tables for the current tables.  A table edited IN PLACE after it was assigned is not
+        seen: assign it again (`model.node_raw_features = model.node_raw_features`)."""
+        return (_capi.TABLE_NODE_ZERO if self.__dict__["_node_all_zero"] else 0) | (_capi.TABLE_EDGE_ZERO if self.__dict__["_edge_all_zero"] else 0)
 
     # ---- reference API -------------------------------------------------------------------------
     def set_neighbor_sampler(self, neighbor_sampler: NeighborSampler):
@@ -203,12 +233,12 @@ class DyGFormer(nn.Module):
             taps_struct = _capi.DygformerTaps()
             taps_struct.ev_kernel_start, taps_struct.ev_kernel_stop = e0.cuda_event, e1.cuda_event
         csr = self.neighbor_sampler.csr.on_device(dev)
-        rc = self._lib.dygnn_dygformer_forward(
+        rc = self._lib.dygnn_dygformer_forward_tables(
             C.byref(self._cfg), C.byref(weights), packed.data_ptr(), csr,
             self.node_raw_features.data_ptr(), self.edge_raw_features.data_ptr(),
             src.data_ptr(), dst.data_ptr(), tms.data_ptr(), B, int(_group_size), int(_pair_stride), out_src.data_ptr(), out_dst.data_ptr(),
             ws.data_ptr(), ws.numel(), C.byref(taps_struct) if taps_struct is not None else None,
-            int(self.impl), _capi.current_stream_ptr())
+            int(self.impl), _capi.current_stream_ptr(), self.table_flags)
         _capi.check(rc)
         return out_src, out_dst
 
@@ -359,8 +389,8 @@ class DyGFormer(nn.Module):
             raise _capi.DygnnError("dyglib_amd.DyGFormer runs on an MI355X only: move the model to a GPU "
                                    "(convert_to_gpu / .to('cuda')); there is no CPU fallback")
         if self.node_raw_features.device != dev:      # the reference places the tables at construction
-            self.node_raw_features = self.node_raw_features.to(dev)
-            self.edge_raw_features = self.edge_raw_features.to(dev)
+            self._set_table("node", self.node_raw_features.to(dev), self.__dict__["_node_all_zero"])      # a copy: the bits stay
+            self._set_table("edge", self.edge_raw_features.to(dev), self.__dict__["_edge_all_zero"])
         return dev
 
     @staticmethod

@@ -205,6 +205,29 @@ int dygnn_dygformer_forward(const dygnn_dygformer_config* cfg_host, const dygnn_
                             void* workspace, size_t workspace_bytes,
                             const dygnn_dygformer_taps* taps_host, int32_t impl, dygnn_stream_t stream);
 
+/* dygnn_dygformer_forward with a promise about the feature tables.  table_flags is a bit set:
+ *   DYGNN_TABLE_NODE_ZERO  every element of node_feat is 0.0 (what the reference's preprocessing writes for every dataset,
+ *                          preprocess_data/preprocess_data.py:108)
+ *   DYGNN_TABLE_EDGE_ZERO  every element of edge_feat is 0.0
+ * The fused inference kernel then leaves the channel out of the patch projection: no gathers, no MFMAs and no weight traffic for it;
+ * its token rows are the channel's projection bias.  For finite projection weights the result has the bits of the unflagged call,
+ * because adding w * 0 to the bias changes nothing — with one exception: a bias element of -0.0 stays -0.0 here, where the
+ * unflagged call turns it into +0.0 (-0.0 + 0.0).  Non-finite weights give NaN unflagged (inf * 0) and the bias here.
+ * The flags are the CALLER'S PROMISE and are not checked: a flag set for a table that holds a non-zero element gives WRONG RESULTS
+ * (the table is ignored).  Establish them once per table (it is a constructor argument of the model) and again when it changes.
+ * Every fused inference shape honours the flags, the long-window one whose projection slab borrows the weight ring included.  The
+ * generic path (impl = 1, or an unsupported shape under impl = 0) and the training entry points ignore them.  Any other bit is an
+ * error.  table_flags = 0 is dygnn_dygformer_forward. */
+#define DYGNN_TABLE_NODE_ZERO 1u
+#define DYGNN_TABLE_EDGE_ZERO 2u
+int dygnn_dygformer_forward_tables(const dygnn_dygformer_config* cfg_host, const dygnn_dygformer_weights* w_host,
+                                   const void* packed, const dygnn_csr* csr_host,
+                                   const float* node_feat, const float* edge_feat,
+                                   const int64_t* src, const int64_t* dst, const double* times, int64_t batch,
+                                   int64_t group_size, int64_t pair_stride, float* out_src, float* out_dst,
+                                   void* workspace, size_t workspace_bytes,
+                                   const dygnn_dygformer_taps* taps_host, int32_t impl, dygnn_stream_t stream, uint32_t table_flags);
+
 /* ------------------------------------------------------------------------------------------
  * TGAT.compute_src_dst_node_temporal_embeddings (models/TGAT.py:48-136), eval mode, `recent`
  * sampling: L temporal-attention layers (MultiHeadAttention models/modules.py:99-206, mask =
