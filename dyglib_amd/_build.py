@@ -19,7 +19,8 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 LIB_NAME = "libdygnn_hip.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
-SOURCES = ["csr_host.cpp", "sampler.hip", "cooccurrence.hip", "dygformer_generic.hip", "dygformer_fused3.hip", "dygformer_train.hip",
+SOURCES = ["csr_host.cpp", "sampler.hip", "cooccurrence.hip", "dygformer_generic.hip", "dygformer_fused3.hip", "dygformer_fused3_train.hip",
+           "dygformer_fused3_bwd.hip", "dygformer_fused3_pack.hip", "dygformer_train.hip",
            "dygformer_api.hip", "tgat.hip", "tgat_chain.hip", "tgat_train.hip", "tgn_train.hip", "graphmixer.hip", "metrics.hip"]
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
@@ -31,9 +32,7 @@ CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-W
 #           UndefinedBehaviorSanitizer; hipcc leaves the gfx950 code objects unsanitized (GPU ASan needs xnack+, unavailable here).
 #           Driven by tests/test_sanitizers_cpu.py on the CPU box, never loaded by the product path.
 SANITIZE = ["-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-g", "-shared-libsan", "-Wno-option-ignored"]
-VARIANTS = {"": [], "stamps": ["-DDYGNN_STAMPS=1"], "asan": SANITIZE,
-            # A/B arm of the fused DyGFormer kernel (tools/ab_fused3.py): its build-time feature switched off
-            "f3noskip": ["-DF3_KSKIP=0"]}
+VARIANTS = {"": [], "stamps": ["-DDYGNN_STAMPS=1"], "asan": SANITIZE}
 for _k, _v in list(os.environ.items()):          # ad-hoc arms: DYGNN_VARIANT_<name>="-DX=1 -DY=2"
     if _k.startswith("DYGNN_VARIANT_"):
         VARIANTS[_k[len("DYGNN_VARIANT_"):].lower()] = _v.split()

@@ -9,13 +9,6 @@ int forward_generic(const Dims&, const PackedLayout&, const dygnn_dygformer_weig
                     const float* node_feat, const float* edge_feat, const int64_t* src, const int64_t* dst, const double* times,
                     int64_t B, int64_t G, int64_t pair_stride, float* out_src, float* out_dst, char* ws, const WorkspaceLayout&,
                     const dygnn_dygformer_taps*, hipStream_t);
-// dygformer_fused3.hip
-bool fused3_supported(const Dims&);
-int pack_fused3(const Dims&, const PackedLayout&, const dygnn_dygformer_weights*, float* packed, hipStream_t, bool reuse_desc);
-int forward_fused3(const Dims&, const PackedLayout&, const dygnn_dygformer_weights*, const float* packed, const dygnn_csr*,
-                   const float* node_feat, const float* edge_feat, const int64_t* src, const int64_t* dst, const double* times,
-                   int64_t B, int64_t G, int64_t pair_stride, float* out_src, float* out_dst, char* ws, const WorkspaceLayout&,
-                   const dygnn_dygformer_taps*, uint32_t table_flags, hipStream_t);
 
 static int check_weights(const Dims& d, const dygnn_dygformer_weights* w) {
     DYGNN_REQUIRE(w != nullptr, "weights is NULL");

@@ -1,5 +1,5 @@
 // DyGFormer forward, generic path (any F/C/P/L/H, T <= 128 tokens per pair): a correctness-first
-// multi-kernel pipeline with activations in HBM.  The fused MFMA kernel (dygformer_fused3.hip)
+// multi-kernel pipeline with activations in HBM.  The fused MFMA kernel (fused3_forward.h)
 // is the fast path for the headline shape; this path covers every other shape and is the
 // on-device cross-check for the fused one.  No host synchronisation anywhere: the batch-wide
 // padded lengths S_src/S_dst (models/DyGFormer.py:219-226) stay on the device in CallDims and

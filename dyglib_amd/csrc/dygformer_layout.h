@@ -1,6 +1,7 @@
 // Packed-weight and workspace layouts shared by the generic and the fused DyGFormer paths.
 #pragma once
 #include "common.h"
+#include "fused3_host.h"      // prototypes of the fused path's entry points (fused3_packed_floats below)
 
 namespace dygnn {
 
@@ -49,8 +50,6 @@ struct PackedLayout {
     size_t fused3;                    // start of the token-owner fused kernel's section (one fragment stream)
     size_t total;                     // floats
 };
-
-size_t fused3_packed_floats(const Dims& d);   // defined in dygformer_fused3.hip
 
 inline PackedLayout make_packed_layout(const Dims& d) {
     PackedLayout p;

@@ -8,27 +8,14 @@
 // row-wise / element-wise kernels.  Dropout masks are not stored: both passes draw them from a counter-based hash of
 // (seed, site, element).  Gradients are produced for every parameter; the feature tables get none (the reference keeps
 // them as constants, models/DyGFormer.py:28-29).
-// This is the first, unfused version (correctness + a working training loop); inference uses dygformer_fused3.hip.
+// This is the first, unfused version (correctness + a working training loop); inference uses dygformer_fused3.hip; the fused training
+// kernels this file dispatches to are in dygformer_fused3_train.hip (forward) and dygformer_fused3_bwd.hip (backward).
 #include <cstdlib>
 #include "dygformer_layout.h"
 #include "gemm.h"
 #include "dropout.h"
 
 namespace dygnn {
-
-int window_lengths_device(const Dims& d, const dygnn_csr* csr, const int64_t* src, const int64_t* dst, const double* times,
-                          int64_t B, int64_t G, char* ws, const WorkspaceLayout& wl, hipStream_t s);   // dygformer_generic.hip
-namespace train { struct TrainOut; }
-bool fused3_supported(const Dims& d);                                                                   // dygformer_fused3.hip
-namespace train { struct Drop; }
-int attn_backward_fused3(const Dims& d, const PackedLayout& pl, const float* packed, int l, int64_t B, int T, float* dX, const float* X, const float* m0,
-                         const float* r0, const float* qkv, const float* P, const float* Pd, float* dAo, float* dQKV, float* dgamma, float* dbeta,
-                         const train::Drop& dr, hipStream_t s);
-int ffn_backward_fused3(const Dims& d, const PackedLayout& pl, const float* packed, int l, int64_t M, float* dX, const float* hpre, const float* x1,
-                        const float* m1, const float* r1, float* dF2, float* dH, float* dgamma, float* dbeta, const train::Drop& dr, hipStream_t s);
-int forward_fused3_train(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, const float* packed, const dygnn_csr* csr,
-                         const float* node_feat, const float* edge_feat, const int64_t* src, const int64_t* dst, const double* times, int64_t B,
-                         const float* lut, float* out_src, float* out_dst, char* ws, const WorkspaceLayout& wl, const train::TrainOut& tr, hipStream_t s);
 
 namespace train {
 
@@ -515,10 +502,13 @@ struct DwArgs {
     unsigned int item[kDwMaxItems];        // problem << 12 | m-group << 6 | n-chunk (up to kDwMaxProblems = 36 problems: a 16-bit code held 16)
     int nitems, K, kchunk;
 };
-__device__ __forceinline__ void dw_dma(const float* gsrc_lane, int lds_float_off_uniform) {      // see v3::dma_frag (dygformer_fused3.hip)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"      // the m0 clobber is reported once per inlined copy
+__device__ __forceinline__ void dw_dma(const float* gsrc_lane, int lds_float_off_uniform) {      // see v3::dma_frag (fused3_device.h)
     const unsigned m0v = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_groupstaticsize() + 4u * (unsigned)lds_float_off_uniform);
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc_lane), "s"(m0v) : "memory", "m0");
 }
+#pragma clang diagnostic pop
 __global__ __launch_bounds__(256, 2) void k_dw_grouped(const DwArgs a) {
     extern __shared__ __attribute__((aligned(16))) float dw_lds[];
     const int it = blockIdx.x % a.nitems, ks = blockIdx.x / a.nitems;
@@ -933,7 +923,7 @@ __global__ void k_lut_fwd(const float* __restrict__ w0, const float* __restrict_
         lut[c * C + j] = acc;
     }
 }
-// sin of the time encoder's argument (up to ~3e6 rad): the range reduction of the forward's cosine (dygformer_fused3.hip cos_time) a quarter
+// sin of the time encoder's argument (up to ~3e6 rad): the range reduction of the forward's cosine (fused3_device.h cos_time) a quarter
 // turn on: x / (2 pi) as a two-float product, the fraction folded to [0, 0.25], cos(2 pi u) by an even polynomial; libm's sinf takes its slow
 // Payne-Hanek path for such arguments and is kept only beyond the product's accuracy
 __device__ __forceinline__ float sin_time(float x) {
@@ -1194,7 +1184,7 @@ extern "C" int dygnn_dygformer_train_forward(const dygnn_dygformer_config* cfg, 
                  d.Fn, d.Fe, d.Ft, C, I32(p.ids), I32(p.c0), I32(p.c1), F32(p.dts), F32(p.Pn), F32(p.Pe), F32(p.Pt), F32(p.Pc), csr->num_nodes};
     hipLaunchKernelGGL(k_embed_inputs, dim3((unsigned)B, (unsigned)(T >= 8 ? 8 : 1)), dim3(256), (size_t)5 * S * 4, s, ea);
     DYGNN_LAUNCH_CHECK();
-    // The fused forward (dygformer_fused3.hip, TR = true): one kernel from the windows to the embeddings that also writes every activation
+    // The fused forward (dygformer_fused3_train.hip, TR = true): one kernel from the windows to the embeddings that also writes every activation
     // the backward pass reads into this Plan's buffers.  `packed` = the kernel-ready copy of the CURRENT weights (dygnn_dygformer_pack /
     // dygnn_dygformer_repack); NULL, or a shape the fused kernel does not take: the product-by-product path below.
     if (packed != nullptr && fused3_supported(d) && (uint64_t)M * 4 * D < (1ull << 32) && (uint64_t)B * H * T * T < (1ull << 32) && !getenv("DYGNN_TRAIN_UNFUSED")) {
@@ -1296,7 +1286,7 @@ extern "C" int dygnn_dygformer_backward(const dygnn_dygformer_config* cfg, const
         // X_{l+1} = X1 + drop(F2), F2 = Hact W2^T + b2
         dw.add(dF2, D, D, F32(L.hact), 4 * D, 4 * D, G(Lg.ffn1_weight), 4 * D, G(Lg.ffn1_bias));                               // dW2 [D][4D], db2
         dw.add(dH, 4 * D, 4 * D, F32(L.xn1), D, D, G(Lg.ffn0_weight), D, G(Lg.ffn0_bias));                                     // dW1 [4D][D], db1
-        if (fused) {      // the whole block in one kernel (dygformer_fused3.hip: k_ffn_bwd): dF2, dHpre written for the grouped launch, dX <- dX1 in place
+        if (fused) {      // the whole block in one kernel (dygformer_fused3_bwd.hip: k_ffn_bwd): dF2, dHpre written for the grouped launch, dX <- dX1 in place
             if (int rc = ffn_backward_fused3(d, make_packed_layout(d), static_cast<const float*>(packed), l, M, dX, F32(L.hpre), F32(L.x1), F32(L.m1), F32(L.r1), dF2, dH,
                                              G(Lg.norm1_weight), G(Lg.norm1_bias), dr, s)) return rc;
         } else {
@@ -1311,7 +1301,7 @@ extern "C" int dygnn_dygformer_backward(const dygnn_dygformer_config* cfg, const
         // X1 = Xin + drop(Ao), Ao = Oa Wo^T + bo ; Oa_bh = Pd_bh V_bh ; S_bh = scale Q_bh K_bh^T ; [Q | K | V] = LN0(Xin) Win^T + bin
         dw.add(dAo, D, D, F32(L.oa), D, D, G(Lg.out_proj_weight), D, G(Lg.out_proj_bias));                                     // dWo [D][D], dbo
         dw.add(dQKV, 3 * D, 3 * D, F32(L.xn0), D, D, G(Lg.in_proj_weight), D, G(Lg.in_proj_bias));                              // dWin [3D][D], dbin
-        if (fused && T <= 128 && H == 2) {      // the whole block in one kernel (dygformer_fused3.hip: k_attn_bwd): dAo, dQKV written for the grouped launch, dX <- dX_l in place
+        if (fused && T <= 128 && H == 2) {      // the whole block in one kernel (dygformer_fused3_bwd.hip: k_attn_bwd): dAo, dQKV written for the grouped launch, dX <- dX_l in place
             if (int rc = attn_backward_fused3(d, make_packed_layout(d), static_cast<const float*>(packed), l, B, T, dX, F32(p.X[l]), F32(L.m0), F32(L.r0), F32(L.qkv), F32(L.P),
                                               F32(L.Pd), dAo, dQKV, G(Lg.norm0_weight), G(Lg.norm0_bias), dr, s)) return rc;
             continue;

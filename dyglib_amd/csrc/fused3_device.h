@@ -1,0 +1,491 @@
+// Fused DyGFormer forward for gfx950, "token-owner" layout (models/DyGFormer.py:68-194 end to end).
+//
+// One workgroup = 8 wave64 = 128 tokens: two (src,dst,t) pairs of <= 64 tokens (TPW = 4 token tiles per pair) or one
+// pair of <= 128 tokens (TPW = 8; BASELINE config 4, L=512 / P=8).  Wave w owns 16 tokens x ALL 200 channels:
+//   * the residual stream X^T (13 accumulator tiles = 52 VGPRs) never leaves the wave's registers;
+//   * LayerNorm is wave-local (register sums + two cross-lane adds) and its output IS the MFMA B operand of the
+//     QKV / FFN products — no LDS round trip, no partial-sum exchange between waves, no K-split;
+//   * Q^T, softmax(S)^T, O^T and gelu(H)^T feed the next product straight from accumulators (same layout trick
+//     an accumulator tile is the B operand of the product that sums over its rows).
+// Only K and V of ONE head at a time live in LDS ([128 tokens][100], 2 x 51.2 KB); heads run back to back.
+//
+// Weights: all 8 waves consume the SAME fragments in the SAME order, so the whole model is ONE linear stream of
+// 1-KiB MFMA-A fragments per kernel, brought on chip once per workgroup by LDS-DMA (global_load_lds, no VGPRs)
+// into a 52-fragment LDS ring and read with ds_read_b128.  (Measured in tools/v3_ubench.hip: weight fragments
+// loaded global->VGPR per wave hold the MFMA pipe at 66 %, LDS-DMA staged at 85 %, registers only 90 %.)
+// The ring protocol: stages of 13 fragments; after the step that finishes a stage every wave waits for its own
+// DMAs, passes one barrier, and issues its share of the stage four ahead.  Steps never straddle the ring end
+// (the packer inserts pad fragments with the same rule the consumer applies).
+//
+// This header holds what the forward kernel (fused3_forward.h) and the backward kernels (dygformer_fused3_bwd.hip) share: the constants,
+// the MFMA / LDS-DMA primitives, the weight stream and the products that more than one kernel runs.
+#pragma once
+#include "dygformer_layout.h"
+
+// The K = 200 products (QKV, FFN W1) spend 2 instead of 4 MFMAs on their last k-chunk (192..207: only 8 real k: mma_group2 / kpack), the
+// head-dim contractions (Q K^T, out-projection) 1 instead of 4 on theirs (96..111: only 4 real k: mma_group1 / kpack4); the packer lays the
+// A fragments of those chunks out to match (FragDesc.kmode).
+// Measured and NOT kept (round 2, profiles/r02_fused3_ab.md): a software-pipelined FFN (stream order W1(p+1) before W2(p), GELU of step p
+// issued inside the W1(p+1) block — in chunks between MFMA groups, or whole before / after the block's MFMAs with the two waves of a SIMD at
+// opposite ends): 1.3-1.6 % SLOWER in every arrangement, the two waves of a SIMD already run the block one after the other (the older or
+// prioritised wave takes nearly every matrix-pipe slot), so one GELU of the two is hidden as it is; a static s_setprio 1 for waves 4-7: +-0.2 %;
+// stage barriers every 13 instead of 26 fragments in the FFN with the next group's fragments read before the barrier: slower (twice the barriers).
+// Measured and NOT kept (round 3, tools/ab_fused3.py, 32 steps per launch; the build-time arms are gone, DESIGN §4.3 names the last commit that had
+// them): the FFN's W1 blocks (or W1 and W2 blocks) starting on fragments read across the stage barrier in front of them: -0.3 % (-2.7 %: 16 more
+// live VGPRs spill).
+
+namespace dygnn {
+namespace v3 {
+
+using f4 = __attribute__((ext_vector_type(4))) float;
+using i4 = __attribute__((ext_vector_type(4))) int;
+
+constexpr int kD = 200, kDP = 208, kNT = 13, kKC = 13, kHD = 100, kHid = 800, kC = 50;
+constexpr int kFrag = 256;            // floats per 16x16 fragment
+constexpr int kRing = 52;             // LDS ring, fragments
+// kStage = 26 (two stages of 26 fragments: half the stage barriers) measured +1.25 % at L = 64, +0.8 % at L = 512 (round 3, tools/ab_fused3.py) and
+// NOT kept: with two stages the fragments a step reads ahead ACROSS the barrier that ends a stage belong to a stage whose DMAs that very
+// barrier publishes (with four stages the barrier one stage earlier did) — a read-ahead that is legal only with three stages in flight;
+// re-reading after the barrier costs what the halved barriers save.
+constexpr int kStage = 13;            // DMA / barrier granularity, fragments: the ring holds kRing / kStage stages
+constexpr int kNStage = kRing / kStage;
+static_assert(kStage * kNStage == kRing && kNStage >= 2, "the ring is a whole number (>= 2) of stages");
+constexpr int kTokWG = 128;           // tokens per workgroup
+constexpr int kKV = 100;              // K/V row stride (floats): 4*25 -> conflict-free b128 row reads and b32 column reads
+constexpr int kLdsK = 0;
+constexpr int kLdsV = kTokWG * kKV;                 // 12800
+constexpr int kLdsRing = 2 * kTokWG * kKV + 16;     // 16 floats of slack: tile 6 of the last row reads 12 floats past it
+constexpr int kLdsMisc = kLdsRing + kRing * kFrag;  // 38928 floats = 155,712 B
+constexpr int kMiscB1 = 0;            // [2][800]: FFN hidden bias, double-buffered by layer parity (no barrier needed:
+                                      // dozens of stream barriers lie between a buffer's write and its reads / reuse)
+constexpr int kMiscFloats = 2 * kHid;               // 1600
+constexpr int kLdsBytes = 160 * 1024;
+static_assert((kLdsMisc + kMiscFloats) * 4 <= kLdsBytes, "LDS budget");
+constexpr int kScratchFloats = 2 * kTokWG * kKV;    // prologue window arrays live in the K/V region
+
+__device__ __forceinline__ f4 mfma(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+template <int N>
+__device__ __forceinline__ void mma_group(f4* acc, const f4* a, const f4 b) {
+#pragma unroll
+    for (int u = 0; u < N; ++u) acc[u] = mfma(a[u].x, b.x, acc[u]);
+#pragma unroll
+    for (int u = 0; u < N; ++u) acc[u] = mfma(a[u].y, b.y, acc[u]);
+#pragma unroll
+    for (int u = 0; u < N; ++u) acc[u] = mfma(a[u].z, b.z, acc[u]);
+#pragma unroll
+    for (int u = 0; u < N; ++u) acc[u] = mfma(a[u].w, b.w, acc[u]);
+}
+// last k-chunk of a K = 200 product: k = 192..199 packed into TWO MFMAs (b0: k = 192 + {0,4,1,5}[g], b1: k = 192 + {2,6,3,7}[g]);
+// the A fragments of that chunk are packed to match (FragDesc.kmode 1)
+template <int N>
+__device__ __forceinline__ void mma_group2(f4* acc, const f4* a, const float b0, const float b1) {
+#pragma unroll
+    for (int u = 0; u < N; ++u) acc[u] = mfma(a[u].x, b0, acc[u]);
+#pragma unroll
+    for (int u = 0; u < N; ++u) acc[u] = mfma(a[u].y, b1, acc[u]);
+}
+// v = rows 192 + 4g + r of an accumulator-layout tile (g >= 2: zero padding).  v_permlane32_swap moves lanes 0..31 of the second
+// operand into lanes 32..63 of the first: (x, y) -> lanes g = 0,1,2,3 hold rows 192, 196, 193, 197; (z, w) -> 194, 198, 195, 199
+__device__ __forceinline__ void kpack(const f4 v, float& b0, float& b1) {
+    // (scalars first: __builtin_bit_cast applied to a vector ELEMENT expression reads element 0 whatever the element — hipcc, ROCm 7.2)
+    const float vx = v.x, vy = v.y, vz = v.z, vw = v.w;
+    const auto r0 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, vx), __builtin_bit_cast(unsigned, vy), false, false);
+    const auto r1 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, vz), __builtin_bit_cast(unsigned, vw), false, false);
+    b0 = __builtin_bit_cast(float, r0[0]);
+    b1 = __builtin_bit_cast(float, r1[0]);
+}
+// v = rows 96 + 4 g + r of a head-dim tile: only rows 96 .. 99 (lane group 0) are real (head dim 100).  Returns the B operand of ONE
+// MFMA that carries all four: lane group g holds row 96 + g (permlane16_swap: 16-lane rows 1, 3 of the first operand <-> rows 0, 2 of the
+// second; then permlane32_swap as in kpack).  The A fragments of that k-chunk are packed to match (FragDesc.kmode 2: k = 96 + g).
+__device__ __forceinline__ float kpack4(const f4 v) {
+    const float vx = v.x, vy = v.y, vz = v.z, vw = v.w;
+    const auto t1 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, vx), __builtin_bit_cast(unsigned, vy), false, false);
+    const auto t2 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, vz), __builtin_bit_cast(unsigned, vw), false, false);
+    const auto r = __builtin_amdgcn_permlane32_swap(t1[0], t2[0], false, false);
+    return __builtin_bit_cast(float, r[0]);
+}
+template <int N>
+__device__ __forceinline__ void mma_group1(f4* acc, const f4* a, const float b0) {
+#pragma unroll
+    for (int u = 0; u < N; ++u) acc[u] = mfma(a[u].x, b0, acc[u]);
+}
+__device__ __forceinline__ f4 ldg4(const float* p) { return *reinterpret_cast<const f4*>(p); }
+__device__ __forceinline__ f4 lds4(const float* p) { return *reinterpret_cast<const f4*>(p); }
+__device__ __forceinline__ f4 zero4() { return f4{0.f, 0.f, 0.f, 0.f}; }
+// One LDS-DMA piece: 64 lanes x 16 B from per-lane global addresses to LDS [dst, dst + 1 KiB), no VGPR destination.
+// Written as inline asm on purpose.  With the builtin (__builtin_amdgcn_global_load_lds) hipcc (ROCm 7.2) knows an LDS-DMA is in flight
+// and from then on waits `s_waitcnt lgkmcnt(0)` — not a counted lgkmcnt(N) — before the MFMAs that consume ds_read results: every other
+// MFMA group of every weight loop then stalls for the LDS round trip of the fragments it has just PREFETCHED for the next group (this
+// kernel keeps a DMA in flight all the time).  The asm form is invisible to that bookkeeping; the protocol needs nothing from it: every
+// wave drains its own DMAs with an explicit `s_waitcnt vmcnt(0)` in front of the stage barrier (WStream::advance).
+// The destination is given as a FLOAT OFFSET into the kernel's one dynamic LDS array (which starts at __builtin_amdgcn_groupstaticsize():
+// the kernel has no static LDS), not as a pointer: an addrspacecast of a generic pointer in this position trips an instruction verifier error.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"      // "clobber list contains reserved registers: m0", once per inlined copy: m0 IS written here
+__device__ __forceinline__ void dma_frag(const float* gsrc_lane, int lds_float_off_uniform) {
+    const unsigned m0v = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_groupstaticsize() + 4u * (unsigned)lds_float_off_uniform);
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc_lane), "s"(m0v) : "memory", "m0");
+}
+#pragma clang diagnostic pop
+
+// sum over the 16 lanes of a DPP row (= the 16 tokens of a tile, lane & 15), result in every lane: four VALU adds with
+// DPP operands (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror) instead of four LDS bpermutes
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float row_sum16(float v) {
+    v += dpp_mov<0xB1>(v);
+    v += dpp_mov<0x4E>(v);
+    v += dpp_mov<0x141>(v);
+    v += dpp_mov<0x140>(v);
+    return v;
+}
+// The same four additions for the per-side pooling sums (pool_sides, and gelu(h) in the pooled layer), each as ONE instruction.  Written as above, hipcc pairs the
+// additions of two sums into a v_pk_add_f32, which has no DPP form: every stage then costs a v_mov_b32_dpp per value plus the packed
+// add.  An empty asm on each stage's result keeps the sums scalar, and the DPP move folds into its add (v_add_f32_dpp): one VALU
+// instruction per value and stage instead of 1.5, same operands, same order, same bits.
+__device__ __forceinline__ float keep_scalar(float v) { asm("" : "+v"(v)); return v; }
+__device__ __forceinline__ float row_sum16_dpp(float v) {
+    v = keep_scalar(v + dpp_mov<0xB1>(v));
+    v = keep_scalar(v + dpp_mov<0x4E>(v));
+    v = keep_scalar(v + dpp_mov<0x141>(v));
+    v = keep_scalar(v + dpp_mov<0x140>(v));
+    return v;
+}
+
+// cos for the time encoder.  The argument w*dt+b reaches 2.7e6 rad where libm's cosf takes its slow Payne-Hanek path; here x/(2 pi) is
+// formed as a two-float product (INV_HI + INV_LO = 1/(2 pi) to 2^-52), its fractional part u in [0, 0.5] is folded to [0, 0.25] and
+// cos(2 pi u) evaluated by an even degree-12 minimax polynomial (|err| <= 6e-8 on the folded range); beyond 3e7 the product's rounding
+// error would exceed 1e-7 turns and libm is called instead (tests/test_dygformer_gpu.py::test_large_timestamps_take_the_libm_cosine_path).
+// erf for the exact GELU: Abramowitz & Stegun 7.1.26 (|err| <= 1.5e-7), branch-free.
+__device__ __forceinline__ float cos_time_fast(float x) {      // |x| <= 3e7 (branch-free; cos_time checks)
+    const float INV_HI = 0.15915493667125702f, INV_LO = 6.4206382432985265e-09f;
+    const float p = x * INV_HI;
+    const float e = fmaf(x, INV_HI, -p);
+    const float q = fmaf(x, INV_LO, e);
+    const float t = (p - rintf(p)) + q;
+    float u = fabsf(t);
+    u = u > 0.5f ? 1.0f - u : u;
+    const bool flip = u > 0.25f;
+    const float v = flip ? 0.5f - u : u;
+    const float z = v * v;
+    float r = fmaf(7.903536371318467f, z, -26.42625678337438f);
+    r = fmaf(r, z, 60.24464137187666f);
+    r = fmaf(r, z, -85.45681720669373f);
+    r = fmaf(r, z, 64.93939402266829f);
+    r = fmaf(r, z, -19.739208802178716f);
+    r = fmaf(r, z, 1.0f);
+    return flip ? -r : r;
+}
+__device__ __forceinline__ float cos_time(float x) { return fabsf(x) <= 3.0e7f ? cos_time_fast(x) : cosf(x); }
+// the same operations on two arguments at once, written on 2-vectors so that hipcc emits packed fp32 instructions (v_pk_mul / v_pk_fma /
+// v_pk_add_f32: two results in ~1.6 issue slots, tools/coissue_ubench.hip; VALU instructions take matrix-pipe time in this kernel)
+using f2 = __attribute__((ext_vector_type(2))) float;
+__device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ __forceinline__ f2 cos_time_fast2(f2 x) {
+    const f2 INV_HI = {0.15915493667125702f, 0.15915493667125702f}, INV_LO = {6.4206382432985265e-09f, 6.4206382432985265e-09f};
+    const f2 p = x * INV_HI;
+    const f2 e = pk_fma(x, INV_HI, -p);
+    const f2 q = pk_fma(x, INV_LO, e);
+    const f2 rp = {rintf(p.x), rintf(p.y)};
+    const f2 t = (p - rp) + q;
+    f2 u = {fabsf(t.x), fabsf(t.y)};
+    const f2 one_u = f2{1.0f, 1.0f} - u;
+    u = f2{u.x > 0.5f ? one_u.x : u.x, u.y > 0.5f ? one_u.y : u.y};
+    const bool fx = u.x > 0.25f, fy = u.y > 0.25f;
+    const f2 half_u = f2{0.5f, 0.5f} - u;
+    const f2 v = {fx ? half_u.x : u.x, fy ? half_u.y : u.y};
+    const f2 z = v * v;
+    auto c2 = [](float c) { return f2{c, c}; };
+    f2 r = pk_fma(c2(7.903536371318467f), z, c2(-26.42625678337438f));
+    r = pk_fma(r, z, c2(60.24464137187666f));
+    r = pk_fma(r, z, c2(-85.45681720669373f));
+    r = pk_fma(r, z, c2(64.93939402266829f));
+    r = pk_fma(r, z, c2(-19.739208802178716f));
+    r = pk_fma(r, z, c2(1.0f));
+    return f2{fx ? -r.x : r.x, fy ? -r.y : r.y};
+}
+__device__ __forceinline__ float erf_as(float x) {
+    const float ax = fabsf(x);
+    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
+    float p = fmaf(1.061405429f, t, -1.453152027f);
+    p = fmaf(p, t, 1.421413741f);
+    p = fmaf(p, t, -0.284496736f);
+    p = fmaf(p, t, 0.254829592f);
+    const float e = __expf(-ax * ax);
+    return copysignf(fmaf(-p * t, e, 1.0f), x);
+}
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erf_as(v * 0.70710678118654752440f)); }
+
+// load / LDS-DMA source for rows that do not exist (static: one copy per translation unit, the build has no relocatable device code)
+[[maybe_unused]] static __device__ __attribute__((aligned(16))) float g_zero16[4] = {0.f, 0.f, 0.f, 0.f};
+
+// ---- the shared weight stream ---------------------------------------------------------------------------------
+struct WStream {
+    const float* gsrc;    // stream base + lane*4 (per lane)
+    int ring;             // LDS ring: float offset into the dynamic LDS array (wave-uniform)
+    int wave, nstages;
+    int nw;               // waves of the workgroup (8; 4 in the one-pair-per-workgroup kernels for small batches): they split a stage's 13 fragments
+    int pos;              // ring slot of the next fragment
+    int instage;          // fragments consumed of the current stage
+    int issued;           // stages whose DMA this wave has issued
+    __device__ __forceinline__ void issue(int s) {
+        if (s < nstages) {
+            const float* srcp = gsrc + (size_t)s * (kStage * kFrag);
+            const int dst = ring + (s % kNStage) * (kStage * kFrag);
+#pragma unroll
+            for (int u = 0; u < (kStage + 3) / 4; ++u) {      // nw >= 4 waves split the stage's fragments
+                const int f = wave + u * nw;
+                if (f < kStage) dma_frag(srcp + f * kFrag, dst + f * kFrag);
+            }
+        }
+    }
+    __device__ __forceinline__ void open(const float* stream, int ring_, int lane, int wave_, int nstages_, int nw_ = 8) {
+        gsrc = stream + lane * 4; ring = ring_; wave = wave_; nstages = nstages_; nw = nw_;
+        pos = 0; instage = 0; issued = kNStage;
+#pragma unroll
+        for (int s = 0; s < kNStage; ++s) issue(s);
+    }
+    // n fragments consumed (or skipped).  Crossing a stage boundary: wait for own DMAs, barrier (every wave is done with
+    // the finished stage, every stage issued before is now visible), then refill the freed ring quarter.
+    // younger_stores (training forward): this wave has issued exactly that many global stores since its last DMA issue.  vmcnt retires in
+    // issue order, so waiting until only those are outstanding proves the (older) DMAs landed without exposing the stores' latency.
+    __device__ __forceinline__ void advance(int n, int younger_stores = 0) {
+        pos += n;
+        if (pos >= kRing) pos -= kRing;
+        instage += n;
+        if (instage >= kStage) {
+            if (younger_stores == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            else if (younger_stores == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's LDS-DMA has landed before anyone passes the barrier
+            __syncthreads();
+            do { instage -= kStage; issue(issued); ++issued; } while (instage >= kStage);
+        }
+    }
+    __device__ __forceinline__ void fit(int n) { if (pos + n > kRing) advance(kRing - pos); }
+    __device__ __forceinline__ void align26() {
+        if (pos != 0 && pos != 26) advance(pos < 26 ? 26 - pos : kRing - pos);
+    }
+    // ring slot of the step after one of n fragments that starts at `pos` (same rule as advance + fit)
+    __device__ __forceinline__ int next_pos(int n, int n_next) const {
+        int p = pos + n;
+        if (p >= kRing) p -= kRing;
+        if (p + n_next > kRing) p = 0;
+        return p;
+    }
+};
+
+// Diagnostic build (-DDYGNN_STAMPS): every wave accumulates s_memtime ticks per phase category and the last four
+// workgroups of the grid store them: taps.phase_cycles[wg][wave][cat]; cat 31 = total.
+#ifdef DYGNN_STAMPS
+#define TDECL unsigned long long tacc_[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long tk_ = __builtin_amdgcn_s_memtime(); const unsigned long long tk0_ = tk_
+#define TACC(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); tacc_[i] += t_ - tk_; tk_ = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
+#define TSTORE()                                                                                   \
+    do {                                                                                           \
+        if (a.stamps != nullptr && lane == 0 && blockIdx.x + 4 >= gridDim.x) {                     \
+            unsigned long long* o_ = a.stamps + ((size_t)(blockIdx.x + 4 - gridDim.x) * 8 + wave) * 32;   \
+            for (int i_ = 0; i_ < 24; ++i_) o_[i_] = tacc_[i_];                                    \
+            o_[31] = tk_ - tk0_;                                                                   \
+        }                                                                                          \
+    } while (0)
+#else
+#define TDECL do { } while (0)
+#define TACC(i) do { } while (0)
+#define TSTORE() do { } while (0)
+#endif
+enum { T_WIN = 0, T_PROJ, T_LN, T_QKV, T_QKVBAR, T_ATTN, T_OPROJ, T_FFN, T_POOL, T_MISC, T_POOL1, T_POOL2, T_PNODE, T_PTIME, T_PEDGE, T_PCOOC,
+       T_F_W1 = 16, T_F_GELU, T_F_ADV1, T_F_W2, T_F_ADV2 };      // FFN sub-phases
+
+// LayerNorm of the register-resident X^T (two-pass, biased variance, eps 1e-5); gamma/beta from LDS
+__device__ __forceinline__ void layernorm(f4 (&xn)[kNT], const f4 (&x)[kNT], const float* gamma, const float* beta, int g, float& mean_o, float& rstd_o) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < kNT; ++i) s += (x[i].x + x[i].y) + (x[i].z + x[i].w);     // rows 200..207 are exact zeros
+    s += __shfl_xor(s, 16, 64);
+    s += __shfl_xor(s, 32, 64);
+    const float mean = s * (1.0f / kD);
+    float v = 0.f;
+#pragma unroll
+    for (int i = 0; i < kNT; ++i) {
+        if (i < 12 || g < 2) {            // rows 200..207 (tile 12, g >= 2) are padding
+            const float d0 = x[i].x - mean, d1 = x[i].y - mean, d2 = x[i].z - mean, d3 = x[i].w - mean;
+            v += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+        }
+    }
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    const float rstd = 1.0f / sqrtf(v * (1.0f / kD) + 1e-5f);
+    mean_o = mean; rstd_o = rstd;
+#pragma unroll
+    for (int i = 0; i < kNT; ++i) {
+        const f4 gm = lds4(gamma + 16 * i + 4 * g), bt = lds4(beta + 16 * i + 4 * g);   // zero beyond 200
+        xn[i].x = (x[i].x - mean) * rstd * gm.x + bt.x;
+        xn[i].y = (x[i].y - mean) * rstd * gm.y + bt.y;
+        xn[i].z = (x[i].z - mean) * rstd * gm.z + bt.z;
+        xn[i].w = (x[i].w - mean) * rstd * gm.w + bt.w;
+    }
+}
+
+// acc[NT] += W(NT tiles of one head's q, k or v) . xn : 13 stream steps of NT fragments [k-chunk][tile], each multiplied
+// as sub-groups of 4 and NT - 4 tiles whose fragments are read one sub-group ahead (8 fragments live instead of 14)
+template <int NT>
+__device__ __forceinline__ void qkv_group(f4 (&acc)[NT], const f4 (&xn)[kNT], const float xk0, const float xk1, WStream& ws, const float* ringl, bool active) {
+    constexpr int N2 = NT - 4;
+    f4 fs[2][4];
+    ws.fit(NT);
+    if (active) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) fs[0][u] = lds4(ringl + (ws.pos + u) * kFrag);
+    }
+#pragma unroll
+    for (int kc = 0; kc < kKC; ++kc) {
+        if (active) {
+#pragma unroll
+            for (int u = 0; u < N2; ++u) fs[1][u] = lds4(ringl + (ws.pos + 4 + u) * kFrag);
+            __builtin_amdgcn_sched_barrier(0);
+            if (kc == kKC - 1) mma_group2<4>(&acc[0], fs[0], xk0, xk1); else mma_group<4>(&acc[0], fs[0], xn[kc]);
+            __builtin_amdgcn_sched_barrier(0);
+            if (kc + 1 < kKC) {
+                const int p1 = ws.next_pos(NT, NT);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) fs[0][u] = lds4(ringl + (p1 + u) * kFrag);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (kc == kKC - 1) mma_group2<N2>(&acc[4], fs[1], xk0, xk1); else mma_group<N2>(&acc[4], fs[1], xn[kc]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        ws.advance(NT);
+        if (kc + 1 < kKC) ws.fit(NT);
+    }
+}
+
+// ---- FFN blocks: one block = the 26 fragments of one product of one step, at ring position 0 or 26.
+// First product: h[2] (two 16-wide hidden tiles) = b1 + W1 . LN(x); 13 k-chunks of two fragments [k-chunk][tile] read one chunk ahead.
+__device__ __forceinline__ void ffn_w1(f4 (&h)[2], const f4 (&xn)[kNT], const float xk0, const float xk1, const float* abuf, const float* b1p, const int g) {
+    if (b1p != nullptr) { h[0] = lds4(b1p + 4 * g); h[1] = lds4(b1p + 16 + 4 * g); }
+    else { h[0] = zero4(); h[1] = zero4(); }
+    f4 sa[2][2];
+    sa[0][0] = lds4(abuf); sa[0][1] = lds4(abuf + kFrag);
+#pragma unroll
+    for (int kc = 0; kc < kKC; ++kc) {
+        const int cur = kc & 1;
+        if (kc + 1 < kKC) {
+            sa[cur ^ 1][0] = lds4(abuf + (size_t)(2 * (kc + 1)) * kFrag);
+            sa[cur ^ 1][1] = lds4(abuf + (size_t)(2 * (kc + 1) + 1) * kFrag);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (kc == kKC - 1) mma_group2<2>(h, sa[cur], xk0, xk1); else mma_group<2>(h, sa[cur], xn[kc]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+// Second product: acc (13 model-dim tiles) += W2[:, the two hidden tiles] . h; fragments [tile u][n-tile i] in sub-groups (4,3,3,3)
+// read one sub-group ahead
+__device__ __forceinline__ void ffn_w2(f4 (&acc)[kNT], const f4 (&h)[2], const float* bbuf) {
+    f4 fs[2][4];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) fs[0][v] = lds4(bbuf + (size_t)v * kFrag);
+#pragma unroll
+    for (int gi = 0; gi < 8; ++gi) {
+        const int u = gi >> 2, q = gi & 3;
+        const int i0 = q == 0 ? 0 : 4 + 3 * (q - 1), n = q == 0 ? 4 : 3;
+        if (gi + 1 < 8) {
+            const int u2 = (gi + 1) >> 2, q2 = (gi + 1) & 3;
+            const int j0 = q2 == 0 ? 0 : 4 + 3 * (q2 - 1), n2 = q2 == 0 ? 4 : 3;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) if (v < n2) fs[(gi + 1) & 1][v] = lds4(bbuf + (size_t)(u2 * 13 + j0 + v) * kFrag);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (n == 4) mma_group<4>(&acc[i0], fs[gi & 1], h[u]); else mma_group<3>(&acc[i0], fs[gi & 1], h[u]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// ---- the attention-shaped products (the forward's S^T, O^T and out-projection; the attention backward runs each of them several times)
+template <int TPW>
+__device__ __forceinline__ void s_like(f4 (&sa)[TPW], const float* base, const f4 (&q)[7], int c, int g) {       // sa[kt] += rows(16 kt ..)(base) . q   (forward: S^T = K Q^T)
+    const float q6 = kpack4(q[6]);       // rows 96 .. 99 of q for the one-MFMA last d-chunk; row tiles of `base` in chunks of 4
+#pragma unroll
+    for (int kh = 0; kh < TPW / 4; ++kh) {
+        const float* kbase = base + (64 * kh + c) * kKV + 4 * g;
+        f4 kf[2][4];
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) kf[0][kt] = lds4(kbase + 16 * kt * kKV);
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            if (j + 1 < 6) {
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt) kf[(j + 1) & 1][kt] = lds4(kbase + 16 * kt * kKV + 16 * (j + 1));
+            } else if (j + 1 == 6) {     // d = 96 .. 99 in ONE MFMA: lane group g reads base[row][96 + g] (kbase points at column 4 g)
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt) kf[0][kt].x = kbase[16 * kt * kKV + 96 - 3 * g];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (j == 6) mma_group1<4>(&sa[4 * kh], kf[0], q6); else mma_group<4>(&sa[4 * kh], kf[j & 1], q[j]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+template <int TPW>
+__device__ __forceinline__ void pv_like(f4 (&oa)[7], const float* base, const f4 (&p)[TPW], int c, int g) {     // oa += rows(base)^T . p   (forward: O^T = V^T P^T)
+    // the rows as the A operand: sub-steps (row tile kt, d-tiles 0..3 | 4..6), read one sub-step ahead (8 fragments live, not 14)
+    auto load_v = [&](f4 (&va)[4], int kt, int j0, int n) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j < n) {
+                const float* vp = base + (16 * kt + 4 * g) * kKV + 16 * (j0 + j) + c;
+                va[j].x = vp[0]; va[j].y = vp[kKV]; va[j].z = vp[2 * kKV]; va[j].w = vp[3 * kKV];
+            }
+        }
+    };
+    f4 va[2][4];
+    load_v(va[0], 0, 0, 4);
+#pragma unroll
+    for (int st = 0; st < 2 * TPW; ++st) {
+        const int kt = st >> 1, half = st & 1;
+        if (st + 1 < 2 * TPW) load_v(va[(st + 1) & 1], (st + 1) >> 1, ((st + 1) & 1) ? 4 : 0, ((st + 1) & 1) ? 3 : 4);
+        __builtin_amdgcn_sched_barrier(0);
+        if (half == 0) mma_group<4>(&oa[0], va[st & 1], p[kt]); else mma_group<3>(&oa[4], va[st & 1], p[kt]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+// acc (13 model-dim tiles) += W^T(7 d-chunks x 13 tiles, from the ring) . t (7 head-dim tiles)   (forward: the out-projection)
+// 7 steps (d-chunk j) of 13 fragments (n-tile i), sub-groups (4,3,3,3) read one ahead; the last d-chunk (rows 96 .. 99 of t) is one MFMA
+__device__ __forceinline__ void proj_t(f4 (&acc)[kNT], const f4 (&t)[7], WStream& ws, const float* ringl, bool active) {
+    ws.fit(13);
+    f4 fs[2][4];
+    float t6 = 0.f;
+    if (active) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) fs[0][v] = lds4(ringl + (ws.pos + v) * kFrag);
+        t6 = kpack4(t[6]);
+    }
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        const int pcur = ws.pos;
+        const int pnext = ws.next_pos(13, 13);
+        if (active) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int gi = 4 * j + q;
+                const int i0 = q == 0 ? 0 : 4 + 3 * (q - 1), n = q == 0 ? 4 : 3;
+                if (q + 1 < 4) {
+                    const int j0 = 4 + 3 * q;
+#pragma unroll
+                    for (int v = 0; v < 3; ++v) fs[(gi + 1) & 1][v] = lds4(ringl + (pcur + j0 + v) * kFrag);
+                } else if (j + 1 < 7) {
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) fs[(gi + 1) & 1][v] = lds4(ringl + (pnext + v) * kFrag);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                if (j == 6) { if (n == 4) mma_group1<4>(&acc[i0], fs[gi & 1], t6); else mma_group1<3>(&acc[i0], fs[gi & 1], t6); }
+                else if (n == 4) mma_group<4>(&acc[i0], fs[gi & 1], t[j]); else mma_group<3>(&acc[i0], fs[gi & 1], t[j]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        ws.advance(13);
+        if (j + 1 < 7) ws.fit(13);
+    }
+}
+}  // namespace v3
+}  // namespace dygnn

@@ -1,0 +1,66 @@
+// Host-side interface of the fused DyGFormer path: the layout of its section of the packed buffer and the prototype of every entry point
+// that another translation unit calls.  dygformer_layout.h includes this header, so the types below are only forward-declared here.
+#pragma once
+#include <cstdlib>
+
+#include "common.h"
+
+namespace dygnn {
+
+struct Dims;
+struct PackedLayout;
+struct WorkspaceLayout;
+namespace train { struct Drop; struct TrainOut; }
+
+namespace v3 {
+
+struct PackLayout3 {       // float offsets relative to PackedLayout.fused3
+    size_t bias_x;
+    size_t stream; int64_t nfrag; int nstages;     // ring stream: nfrag fragments, padded to whole stages (+ one of slack)
+    size_t aux; int64_t naux;                      // output-layer fragments
+    size_t proj; int64_t nproj;                    // projection fragments
+    int scr_floats, slab_chunks;                   // LDS split of the K/V region during the prologue
+    int np, slab_in_ring;                          // pairs per workgroup (0: shape unsupported); slab placed in the weight ring
+    int tab_off, tab_slots, tab_bits;              // co-occurrence table (long windows): LDS word offset, slots per pair
+    size_t bwd[DYGNN_MAX_LAYERS]; int bwd_nstages;  // per layer: the backward stream of its FFN block (training only)
+    size_t bwa[DYGNN_MAX_LAYERS]; int bwa_nstages; int64_t bwa_frags;      // ... and of its attention block
+    size_t stream_p; int64_t nfrag_p; int nstages_p;       // ring stream of the pooled inference kernels (build_stream, pooled)
+    size_t w2;                                     // ... and their last layer's W2 fragments (build_w2)
+    size_t desc;           // FragDesc table (device copy), 8-byte aligned
+    size_t total;
+};
+
+PackLayout3 make_layout3(const Dims& d);       // dygformer_fused3_pack.hip
+bool supported(const Dims& d);
+int proj_slots(int nchunk);                    // k-chunk slots a projection channel occupies in the stored fragment sequence
+
+}  // namespace v3
+
+// calls of at most this many pairs run one pair per four-wave workgroup (see k_dygformer_fused3): one round on the 256 CUs
+constexpr int64_t kSmallBatchPairs = 256;
+inline bool small_off() { static const bool off = [] { const char* e = getenv("DYGNN_SMALL_BATCH_KERNELS"); return e && e[0] == '0'; }(); return off; }
+
+// dygformer_generic.hip
+int window_lengths_device(const Dims& d, const dygnn_csr* csr, const int64_t* src, const int64_t* dst, const double* times,
+                          int64_t B, int64_t G, char* ws, const WorkspaceLayout& wl, hipStream_t s);
+// dygformer_fused3_pack.hip
+bool fused3_supported(const Dims& d);
+size_t fused3_packed_floats(const Dims& d);
+int pack_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, float* packed, hipStream_t s, bool reuse_desc);
+// dygformer_fused3.hip
+int forward_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, const float* packed,
+                   const dygnn_csr* csr, const float* node_feat, const float* edge_feat, const int64_t* src,
+                   const int64_t* dst, const double* times, int64_t B, int64_t G, int64_t pair_stride, float* out_src, float* out_dst, char* ws,
+                   const WorkspaceLayout& wl, const dygnn_dygformer_taps* taps, uint32_t table_flags, hipStream_t s);
+// dygformer_fused3_train.hip
+int forward_fused3_train(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, const float* packed, const dygnn_csr* csr,
+                         const float* node_feat, const float* edge_feat, const int64_t* src, const int64_t* dst, const double* times, int64_t B,
+                         const float* lut, float* out_src, float* out_dst, char* ws, const WorkspaceLayout& wl, const train::TrainOut& tr, hipStream_t s);
+// dygformer_fused3_bwd.hip
+int ffn_backward_fused3(const Dims& d, const PackedLayout& pl, const float* packed, int l, int64_t M, float* dX, const float* hpre, const float* x1,
+                        const float* m1, const float* r1, float* dF2, float* dH, float* dgamma, float* dbeta, const train::Drop& dr, hipStream_t s);
+int attn_backward_fused3(const Dims& d, const PackedLayout& pl, const float* packed, int l, int64_t B, int T, float* dX, const float* X, const float* m0,
+                         const float* r0, const float* qkv, const float* P, const float* Pd, float* dAo, float* dQKV, float* dgamma, float* dbeta,
+                         const train::Drop& dr, hipStream_t s);
+
+}  // namespace dygnn

@@ -9,7 +9,7 @@ namespace attn {
 using af4 = __attribute__((ext_vector_type(4))) float;
 
 __device__ __attribute__((noinline)) float cos_libm(float x) { return cosf(x); }
-__device__ __forceinline__ float cos_time_t(float x) {      // same range reduction + polynomial as dygformer_fused3.hip
+__device__ __forceinline__ float cos_time_t(float x) {      // same range reduction + polynomial as fused3_device.h
     if (!(fabsf(x) <= 3.0e7f)) return cos_libm(x);
     const float INV_HI = 0.15915493667125702f, INV_LO = 6.4206382432985265e-09f;
     const float p = x * INV_HI;

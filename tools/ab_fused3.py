@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B of builds of the fused DyGFormer kernel in ONE process (interleaved rounds, cdna_hip_programming.md §5.4 rule 24):
-    python tools/ab_fused3.py [variant ...]          # names of dyglib_amd/_build.py VARIANTS; "" or "default" = the shipped build
+    python tools/ab_fused3.py [variant ...]          # names of dyglib_amd/_build.py VARIANTS; "" or "default" = the shipped build (alone: the default)
 Build the variants on the CPU box first (python -m dyglib_amd._build --variant=NAME): the .so files travel with gpurun.
 Each arm runs the bench.py launch shape (32 steps = 64 groups of 200 pairs = 6,400 workgroups on the Wikipedia-shaped workload);
 prints per-arm median / min ms per launch, edges/s, the fraction of the fp32-MFMA peak, and max |out - out(arm 0)|."""
@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 from dyglib_amd import _capi  # noqa: E402
 
-names = [("" if a == "default" else a) for a in sys.argv[1:]] or ["", "f3base"]
+names = [("" if a == "default" else a) for a in sys.argv[1:]] or [""]
 rounds = int(os.environ.get("AB_ROUNDS", "9"))
 F = int(os.environ.get("AB_STEPS", "32"))
 workload = os.environ.get("AB_WORKLOAD", "wikipedia")
