@@ -16,7 +16,7 @@ import torch  # noqa: F401  (must be imported first: see module docstring)
 from . import _build
 
 DYGNN_MAX_LAYERS = 8
-ABI_VERSION = 18
+ABI_VERSION = 19
 TABLE_NODE_ZERO, TABLE_EDGE_ZERO = 1, 2      # table_flags of dygnn_dygformer_forward_tables (include/dygnn.h)
 
 c_i32p = C.POINTER(C.c_int32)
@@ -102,6 +102,26 @@ class GraphmixerTaps(C.Structure):
                 ("node_term", C.c_void_p)]
 
 
+class TclConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("node_feat_dim", "edge_feat_dim", "time_feat_dim", "num_neighbors", "num_layers", "num_heads",
+                                         "num_node_rows", "num_edge_rows")]
+
+
+class TclLayerWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "fc0_w", "fc0_b", "fc1_w", "fc1_b",
+                                          "norm0_w", "norm0_b", "norm1_w", "norm1_b")]
+
+
+class TclWeights(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("time_w", "time_b", "depth_w", "proj_node_w", "proj_node_b", "proj_edge_w", "proj_edge_b",
+                                           "proj_time_w", "proj_time_b")]
+                + [("layers", TclLayerWeights * DYGNN_MAX_LAYERS)] + [("output_w", C.c_void_p), ("output_b", C.c_void_p)])
+
+
+class TclTaps(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("encoder_input", C.c_void_p), ("layer_out", C.c_void_p * DYGNN_MAX_LAYERS)]
+
+
 class DygformerTaps(C.Structure):
     _fields_ = [("seq_lens", C.c_void_p), ("encoder_input", C.c_void_p), ("layer_out", C.c_void_p * DYGNN_MAX_LAYERS),
                 ("phase_cycles", C.c_void_p), ("ev_kernel_start", C.c_void_p), ("ev_kernel_stop", C.c_void_p)]
@@ -180,6 +200,11 @@ SIGNATURES = {
     "dygnn_graphmixer_workspace_bytes": (C.c_size_t, [C.POINTER(GraphmixerConfig), C.c_int64]),
     "dygnn_graphmixer_forward": (C.c_int, [C.POINTER(GraphmixerConfig), C.POINTER(GraphmixerWeights), C.POINTER(Csr), C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(GraphmixerTaps), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dygnn_tcl_check": (C.c_int, [C.POINTER(TclConfig)]),
+    "dygnn_tcl_workspace_bytes": (C.c_size_t, [C.POINTER(TclConfig), C.c_int64, C.c_int64]),
+    "dygnn_tcl_forward": (C.c_int, [C.POINTER(TclConfig), C.POINTER(TclWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.POINTER(TclTaps), C.c_void_p, C.c_size_t, C.c_void_p]),
     "dygnn_merge_layer_sigmoid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dygnn_merge_layer_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,

@@ -7,62 +7,31 @@
 //   k_gm_out    16 roots per workgroup: token mean, [mean | node term + node_feat[v]], output_layer                    -> out [n, Fn]
 // The workspace is X and the node term: n (K C + Fn) floats.  Nothing has a time_gap dimension.
 //
-// Products use v_mfma_f32_16x16x4_f32 in the transposed form of k_gemm_nt (tgat.hip): the weight rows are the A operand, so lane (c, g) of a
-// tile ends up with out[m0 + c][n0 + 4g .. 4g + 3], one float4.  Both operands are K-contiguous: lane (c, g) reads the float4 at
-// [row c][k0 + 4g] of each and feeds its four components to four MFMAs (the k order inside a block of 16 is permuted the same way on both sides).
+// Products use the fp32 MFMA tile product of mfma_tile.h.
 #include "common.h"
+#include "mfma_tile.h"
 #include "tgat_attn.h"
 
 namespace dygnn {
 namespace gm {
 
-using f4 = __attribute__((ext_vector_type(4))) float;
 using attn::cos_time_t;
+using tile::f4;
+using tile::kThreads;
+using tile::kWaves;
+using tile::lds_limit;
+using tile::mfma4;
+using tile::round16;
+using tile::wave_product;
+using tile::wave_sum;
+using tile::z4;
 
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ float gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }      // nn.GELU(), exact
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ f4 z4() { return f4{0.f, 0.f, 0.f, 0.f}; }
-constexpr int kThreads = 256, kWaves = 4;
 constexpr int kFfnRows = 64;      // token rows per workgroup of k_gm_ffn
 constexpr int kFfnChunk = 64;     // hidden columns in LDS at a time
 constexpr int kOutRoots = 16;
 constexpr int kMaxTokens = 32;
 constexpr float kLnEps = 1e-5f;
-
-__host__ __device__ inline int round16(int x) { return (x + 15) & ~15; }
-
-// acc[t][mt] += W[n0(t) + ., 0:Kdim] . A[16 mt + ., 0:Kdim]^T for the calling wave's column tiles n0(t) = 16 (wave + 4 t), t < NT.
-// A: LDS rows of stride lda, zero beyond Kdim up to round16(Kdim).  W: global [N][ldw] (16-byte aligned rows), read at columns wk0 + k.
-template <int NT, int MT>
-__device__ __forceinline__ void wave_product(const float* __restrict__ A, int lda, const float* __restrict__ W, int ldw, int wk0, int N, int Kdim,
-                                             int wave, int lane, f4 (&acc)[NT][MT]) {
-    const int c = lane & 15, g = lane >> 4;
-    for (int k0 = 0; k0 < Kdim; k0 += 16) {
-        const int k = k0 + 4 * g;
-        f4 a[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) a[mt] = *reinterpret_cast<const f4*>(A + (size_t)(16 * mt + c) * lda + k);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int n0 = 16 * (wave + kWaves * t);
-            if (n0 >= N) continue;                                   // wave-uniform
-            const int n = n0 + c;
-            const f4 w = (n < N && k < Kdim) ? *reinterpret_cast<const f4*>(W + (size_t)n * ldw + wk0 + k) : z4();
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                acc[t][mt] = mfma4(w.x, a[mt].x, acc[t][mt]);
-                acc[t][mt] = mfma4(w.y, a[mt].y, acc[t][mt]);
-                acc[t][mt] = mfma4(w.z, a[mt].z, acc[t][mt]);
-                acc[t][mt] = mfma4(w.w, a[mt].w, acc[t][mt]);
-            }
-        }
-    }
-}
 
 struct Csr {
     const int64_t* indptr;
@@ -378,12 +347,6 @@ static Plan make_plan(const dygnn_graphmixer_config& c, int64_t n) {
     p.term = align256((size_t)n * c.num_tokens * c.edge_feat_dim * sizeof(float));
     p.total = p.term + align256((size_t)n * c.node_feat_dim * sizeof(float));
     return p;
-}
-
-template <typename Kern>
-static int lds_limit(Kern kernel, size_t bytes) {
-    if (bytes > 64 * 1024) DYGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return DYGNN_OK;
 }
 
 }  // namespace gm

@@ -331,3 +331,56 @@ def make_graphmixer_params(seed: int, num_tokens: int, num_layers: int = 2, node
             val = rs.uniform(-1, 1, size=shape) / np.sqrt(fan_in)
         out[key] = np.ascontiguousarray(val, dtype=np.float32)
     return out
+
+
+def tcl_param_shapes(num_neighbors: int, node_feat_dim: int = NODE_FEAT_DIM, edge_feat_dim: int = NODE_FEAT_DIM, time_feat_dim: int = 100,
+                     num_layers: int = 2) -> Dict[str, Tuple[int, ...]]:
+    """state_dict of the reference TCL (models/TCL.py:40-54, models/modules.py:220-231), in its order: 11 + 12 num_layers tensors."""
+    d = node_feat_dim
+    shapes: Dict[str, Tuple[int, ...]] = {"time_encoder.w.weight": (time_feat_dim, 1), "time_encoder.w.bias": (time_feat_dim,),
+                                          "depth_embedding.weight": (num_neighbors + 1, d),
+                                          "projection_layer.node.weight": (d, d), "projection_layer.node.bias": (d,),
+                                          "projection_layer.edge.weight": (d, edge_feat_dim), "projection_layer.edge.bias": (d,),
+                                          "projection_layer.time.weight": (d, time_feat_dim), "projection_layer.time.bias": (d,)}
+    for l in range(num_layers):
+        p = f"transformers.{l}."
+        shapes[p + "multi_head_attention.in_proj_weight"] = (3 * d, d)
+        shapes[p + "multi_head_attention.in_proj_bias"] = (3 * d,)
+        shapes[p + "multi_head_attention.out_proj.weight"] = (d, d)
+        shapes[p + "multi_head_attention.out_proj.bias"] = (d,)
+        shapes[p + "linear_layers.0.weight"] = (4 * d, d)
+        shapes[p + "linear_layers.0.bias"] = (4 * d,)
+        shapes[p + "linear_layers.1.weight"] = (d, 4 * d)
+        shapes[p + "linear_layers.1.bias"] = (d,)
+        shapes[p + "norm_layers.0.weight"] = (d,)
+        shapes[p + "norm_layers.0.bias"] = (d,)
+        shapes[p + "norm_layers.1.weight"] = (d,)
+        shapes[p + "norm_layers.1.bias"] = (d,)
+    shapes["output_layer.weight"] = (d, d)
+    shapes["output_layer.bias"] = (d,)
+    return shapes
+
+
+def make_tcl_params(seed: int, num_neighbors: int, num_layers: int = 2, node_feat_dim: int = NODE_FEAT_DIM, edge_feat_dim: int = NODE_FEAT_DIM,
+                    time_feat_dim: int = 100) -> Dict[str, np.ndarray]:
+    """Deterministic float32 parameters in the style of make_tgat_params: LayerNorm weights 1 +- 0.1, every bias non-zero and a depth
+    embedding of 0.5 N(0, 1) rows, so a dropped term shows in the output."""
+    rs = np.random.RandomState(seed)
+    out: Dict[str, np.ndarray] = {}
+    for key, shape in tcl_param_shapes(num_neighbors, node_feat_dim, edge_feat_dim, time_feat_dim, num_layers).items():
+        if key == "time_encoder.w.weight":
+            base = (1.0 / 10 ** np.linspace(0, 9, time_feat_dim, dtype=np.float32)).reshape(shape)
+            val = base * (1.0 + 0.01 * rs.uniform(-1, 1, size=shape))
+        elif key == "time_encoder.w.bias":
+            val = 0.1 * rs.uniform(-1, 1, size=shape)
+        elif key == "depth_embedding.weight":
+            val = 0.5 * rs.standard_normal(shape)
+        elif "norm_layers" in key:
+            val = (1.0 if key.endswith("weight") else 0.0) + 0.1 * rs.uniform(-1, 1, size=shape)
+        elif key.endswith("in_proj_bias"):
+            val = rs.uniform(-1, 1, size=shape) / np.sqrt(node_feat_dim)
+        else:
+            fan_in = shape[1] if len(shape) == 2 else out[key[:-4] + "weight"].shape[1]
+            val = rs.uniform(-1, 1, size=shape) / np.sqrt(fan_in)
+        out[key] = np.ascontiguousarray(val, dtype=np.float32)
+    return out

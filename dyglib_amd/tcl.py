@@ -1,0 +1,201 @@
+"""Drop-in for the reference `TCL` backbone (models/TCL.py:9-188): same constructor, same
+`compute_src_dst_node_temporal_embeddings(src_node_ids, dst_node_ids, node_interact_times, num_neighbors)` / `set_neighbor_sampler`
+signatures, same parameter names and shapes (a reference checkpoint loads with strict=True); the forward runs in libdygnn_hip.so
+(`dygnn_tcl_forward`, dyglib_amd/csrc/tcl.hip).
+
+Inference only (eval or train mode under torch.no_grad()): with autograd recording the calls raise NotImplementedError (the training path:
+backward, dropout, autograd, is not built yet).  All three neighbour sampling strategies work: the neighbours are sampled by
+`NeighborSampler.get_historical_neighbors_device` in the reference's call order (sources, then destinations) and handed to the library.
+
+In TCL the source embedding depends on the destination it is paired with (cross-attention), so an evaluation step has FOUR results:
+`compute_step_embeddings` returns (src of the positive call, dst, src of the negative call, neg_dst)."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _capi
+from .modules import TimeEncoder
+from .neighbor_sampler import NeighborSampler
+from .tgat import _to_dev, _workspace
+
+
+class TransformerEncoder(nn.Module):
+    """Parameters of models/modules.py:209-231."""
+
+    def __init__(self, attention_dim: int, num_heads: int, dropout: float = 0.1):
+        super().__init__()
+        self.multi_head_attention = nn.MultiheadAttention(embed_dim=attention_dim, num_heads=num_heads, dropout=dropout)
+        self.dropout = nn.Dropout(dropout)
+        self.linear_layers = nn.ModuleList([nn.Linear(attention_dim, 4 * attention_dim), nn.Linear(4 * attention_dim, attention_dim)])
+        self.norm_layers = nn.ModuleList([nn.LayerNorm(attention_dim), nn.LayerNorm(attention_dim)])
+
+
+class TCL(nn.Module):
+
+    def __init__(self, node_raw_features: np.ndarray, edge_raw_features: np.ndarray, neighbor_sampler: NeighborSampler,
+                 time_feat_dim: int, num_layers: int = 2, num_heads: int = 2, num_depths: int = 20, dropout: float = 0.1, device: str = "cpu"):
+        super().__init__()
+        self.node_raw_features = torch.from_numpy(np.ascontiguousarray(node_raw_features, dtype=np.float32)).to(device)
+        self.edge_raw_features = torch.from_numpy(np.ascontiguousarray(edge_raw_features, dtype=np.float32)).to(device)
+        self.neighbor_sampler = neighbor_sampler
+        self.node_feat_dim = self.node_raw_features.shape[1]
+        self.edge_feat_dim = self.edge_raw_features.shape[1]
+        self.time_feat_dim = time_feat_dim
+        self.num_layers = num_layers
+        self.num_heads = num_heads
+        self.num_depths = num_depths
+        self.dropout = dropout
+        self.device = device
+        self.time_encoder = TimeEncoder(time_dim=time_feat_dim)
+        self.depth_embedding = nn.Embedding(num_embeddings=num_depths, embedding_dim=self.node_feat_dim)
+        self.projection_layer = nn.ModuleDict({
+            "node": nn.Linear(self.node_feat_dim, self.node_feat_dim, bias=True),
+            "edge": nn.Linear(self.edge_feat_dim, self.node_feat_dim, bias=True),
+            "time": nn.Linear(self.time_feat_dim, self.node_feat_dim, bias=True)})
+        self.transformers = nn.ModuleList([TransformerEncoder(self.node_feat_dim, self.num_heads, self.dropout) for _ in range(self.num_layers)])
+        self.output_layer = nn.Linear(self.node_feat_dim, self.node_feat_dim, bias=True)
+        self._lib = _capi.load()
+        self._workspace: Dict[tuple, torch.Tensor] = {}
+
+    def set_neighbor_sampler(self, neighbor_sampler: NeighborSampler):
+        """models/TCL.py:179-188."""
+        self.neighbor_sampler = neighbor_sampler
+        if self.neighbor_sampler.sample_neighbor_strategy in ["uniform", "time_interval_aware"]:
+            assert self.neighbor_sampler.seed is not None
+            self.neighbor_sampler.reset_random_state()
+
+    # ---- the reference's entry point ---------------------------------------------------------------------------------------------------
+    def compute_src_dst_node_temporal_embeddings(self, src_node_ids, dst_node_ids, node_interact_times, num_neighbors: int = 20,
+                                                 taps: Optional[int] = None):
+        """models/TCL.py:56-154: two float32 tensors [B, node_feat_dim]; ONE library call on the sides [src ; dst] and the pairs (i, B + i).
+        `taps` = r (not in the reference): also return the intermediates of the first r pairs, (src, dst, dict(encoder_input [r, 2, S, d],
+        layer_out: per layer [r, 2, S, d])); index 0 / 1 of the second axis is the source / destination sequence."""
+        (src, dst), tms = self._inputs((src_node_ids, dst_node_ids), node_interact_times, num_neighbors)
+        B = src.numel()
+        sides = self._sample([src, dst], tms, num_neighbors)
+        idx = np.arange(B, dtype=np.int32)
+        out = self._forward(*sides, idx, idx + B, num_neighbors, taps)
+        return out if taps is None else (out[0], out[1], out[2])
+
+    def compute_step_embeddings(self, src_node_ids, dst_node_ids, neg_dst_node_ids, node_interact_times, num_neighbors: int = 20
+                                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The positive and the negative call of an evaluation step (evaluate_models_utils.py:126-136) as ONE library call: (src_pos, dst,
+        src_neg, neg_dst), bit-identical to compute_src_dst...(src, dst) followed by compute_src_dst...(src, neg_dst).  With `recent` sampling
+        the source sides are shared between the two pairs of an edge (sides [src ; dst ; neg_dst], 2 B pairs); a random strategy samples in
+        the order of the reference's two calls (src, dst, src, neg_dst), so the sources are drawn twice and are four B sides."""
+        (src, dst, neg), tms = self._inputs((src_node_ids, dst_node_ids, neg_dst_node_ids), node_interact_times, num_neighbors)
+        B = src.numel()
+        idx = np.arange(B, dtype=np.int32)
+        if self.neighbor_sampler.sample_neighbor_strategy == "recent":
+            sides = self._sample([src, dst, neg], tms, num_neighbors)
+            a, b = np.concatenate([idx, idx]), np.concatenate([idx + B, idx + 2 * B])
+        else:
+            sides = self._sample([src, dst, src, neg], tms, num_neighbors)
+            a, b = np.concatenate([idx, idx + 2 * B]), np.concatenate([idx + B, idx + 3 * B])
+        oa, ob = self._forward(*sides, a, b, num_neighbors)
+        return oa[:B], ob[:B], oa[B:], ob[B:]
+
+    # ---- glue ------------------------------------------------------------------------------------------------------------------------
+    def _inputs(self, id_arrays, node_interact_times, num_neighbors):
+        """Refuse what is not built (autograd recording, a CPU model), validate host ids like the reference (IndexError; a root id of 0 is an
+        AssertionError: the reference returns NaN rows for it, every key being masked), and move ids (int64) and times (float64) to the
+        model's device."""
+        if torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("TCL is inference-only on the HIP path: call it under torch.no_grad().  Training (backward, dropout, "
+                                      "autograd) is the follow-up to this forward and is not built yet")
+        self.neighbor_sampler._check_strategy()
+        assert num_neighbors > 0, "Number of sampled neighbors for each node should be greater than 0!"          # utils/utils.py:157
+        assert num_neighbors + 1 == self.depth_embedding.weight.shape[0], \
+            f"tcl: num_neighbors + 1 ({num_neighbors + 1}) must equal num_depths ({self.depth_embedding.weight.shape[0]})"      # models/TCL.py:173
+        dev = self.output_layer.weight.device
+        if dev.type != "cuda":
+            raise _capi.DygnnError("dyglib_amd.TCL runs on an MI355X only; there is no CPU fallback")
+        if self.node_raw_features.device != dev:
+            self.node_raw_features = self.node_raw_features.to(dev)
+            self.edge_raw_features = self.edge_raw_features.to(dev)
+        csr = self.neighbor_sampler.csr
+        if getattr(self, "_validated_csr", None) is not csr:
+            csr.check_tables(self.node_raw_features.shape[0], self.edge_raw_features.shape[0])
+            self._validated_csr = csr
+        for ids in id_arrays:
+            csr.check_query_ids(ids, limit=self.node_raw_features.shape[0])
+            if not isinstance(ids, torch.Tensor) and np.asarray(ids).size:
+                assert int(np.asarray(ids).min()) > 0, "tcl: node id 0 is the padding node: as a root it has no valid attention key"
+        parts = [_to_dev(ids, torch.int64, dev).reshape(-1) for ids in id_arrays]
+        tms = _to_dev(node_interact_times, torch.float64, dev).reshape(-1)
+        assert all(p.numel() == tms.numel() for p in parts)
+        return parts, tms
+
+    def _sample(self, parts, tms, num_neighbors):
+        """One sampler call per part, in order (the order matters for the random strategies) -> the sides' device arrays."""
+        smp = self.neighbor_sampler
+        if smp.device != tms.device:
+            raise _capi.DygnnError(f"the neighbor sampler is on {smp.device}, the model on {tms.device}")
+        drawn = [smp.get_historical_neighbors_device(p, tms, num_neighbors) for p in parts] if tms.numel() else []
+        if not drawn:
+            return None, None, None, None, None
+        cat = lambda xs: xs[0] if len(xs) == 1 else torch.cat(xs)
+        return (cat(parts), cat([tms] * len(parts)), cat([d[0] for d in drawn]), cat([d[1] for d in drawn]), cat([d[2] for d in drawn]))
+
+    def _config(self, num_neighbors: int) -> "_capi.TclConfig":
+        return _capi.TclConfig(self.node_feat_dim, self.edge_feat_dim, self.time_feat_dim, int(num_neighbors), self.num_layers, self.num_heads,
+                               self.node_raw_features.shape[0], self.edge_raw_features.shape[0])
+
+    def _weights(self) -> "_capi.TclWeights":
+        for p in self.parameters():
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise _capi.DygnnError("parameters must be contiguous float32")
+        w = _capi.TclWeights()
+        p = lambda t: t.data_ptr()
+        w.time_w, w.time_b, w.depth_w = p(self.time_encoder.w.weight), p(self.time_encoder.w.bias), p(self.depth_embedding.weight)
+        pl = self.projection_layer
+        w.proj_node_w, w.proj_node_b = p(pl["node"].weight), p(pl["node"].bias)
+        w.proj_edge_w, w.proj_edge_b = p(pl["edge"].weight), p(pl["edge"].bias)
+        w.proj_time_w, w.proj_time_b = p(pl["time"].weight), p(pl["time"].bias)
+        for l, t in enumerate(self.transformers):
+            L, a = w.layers[l], t.multi_head_attention
+            L.in_proj_w, L.in_proj_b, L.out_proj_w, L.out_proj_b = p(a.in_proj_weight), p(a.in_proj_bias), p(a.out_proj.weight), p(a.out_proj.bias)
+            L.fc0_w, L.fc0_b, L.fc1_w, L.fc1_b = (p(t.linear_layers[0].weight), p(t.linear_layers[0].bias), p(t.linear_layers[1].weight),
+                                                  p(t.linear_layers[1].bias))
+            L.norm0_w, L.norm0_b, L.norm1_w, L.norm1_b = (p(t.norm_layers[0].weight), p(t.norm_layers[0].bias), p(t.norm_layers[1].weight),
+                                                          p(t.norm_layers[1].bias))
+        w.output_w, w.output_b = p(self.output_layer.weight), p(self.output_layer.bias)
+        return w
+
+    def _forward(self, roots, tms, nbr, eid, nts, pair_a: np.ndarray, pair_b: np.ndarray, num_neighbors: int, taps: Optional[int] = None):
+        dev = self.output_layer.weight.device
+        P = len(pair_a)
+        n_sides = 0 if roots is None else roots.numel()
+        cfg = self._config(num_neighbors)
+        if len(self.transformers) != self.num_layers or self.num_layers > _capi.DYGNN_MAX_LAYERS:
+            raise NotImplementedError(f"tcl: num_layers {self.num_layers} not supported (1..{_capi.DYGNN_MAX_LAYERS})")
+        nbytes = self._lib.dygnn_tcl_workspace_bytes(C.byref(cfg), n_sides, P)
+        if nbytes == 0:                                  # AssertionError (bad argument) or NotImplementedError (unsupported) with the library's message
+            _capi.check(self._lib.dygnn_tcl_check(C.byref(cfg)))
+        ws = _workspace(self._workspace, nbytes, (n_sides, P), num_neighbors, dev)
+        d, S = self.node_feat_dim, int(num_neighbors) + 1
+        out_a = torch.empty((P, d), dtype=torch.float32, device=dev)
+        out_b = torch.empty((P, d), dtype=torch.float32, device=dev)
+        tap_struct, tap_out = None, None
+        if taps is not None:
+            r = min(int(taps), P)
+            new = lambda: torch.zeros((r, 2, S, d), dtype=torch.float32, device=dev)
+            tap_out = dict(encoder_input=new(), layer_out=[new() for _ in range(self.num_layers)])
+            tap_struct = _capi.TclTaps()
+            tap_struct.rows = r
+            tap_struct.encoder_input = tap_out["encoder_input"].data_ptr()
+            for l, t in enumerate(tap_out["layer_out"]):
+                tap_struct.layer_out[l] = t.data_ptr()
+        if P > 0:
+            pa, pb = np.ascontiguousarray(pair_a, dtype=np.int32), np.ascontiguousarray(pair_b, dtype=np.int32)
+            _capi.check(self._lib.dygnn_tcl_forward(C.byref(cfg), C.byref(self._weights()), self.node_raw_features.data_ptr(),
+                                                    self.edge_raw_features.data_ptr(), roots.data_ptr(), tms.data_ptr(), nbr.data_ptr(), eid.data_ptr(),
+                                                    nts.data_ptr(), n_sides, pa.ctypes.data, pb.ctypes.data, P, out_a.data_ptr(), out_b.data_ptr(),
+                                                    C.byref(tap_struct) if tap_struct is not None else None, ws.data_ptr(), ws.numel(),
+                                                    _capi.current_stream_ptr()))
+        return (out_a, out_b) if taps is None else (out_a, out_b, tap_out)

@@ -504,6 +504,70 @@ int dygnn_graphmixer_forward(const dygnn_graphmixer_config* cfg_host, const dygn
                              float* out /* [n, F_n] */, const dygnn_graphmixer_taps* taps_host /* or NULL */,
                              void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * TCL.compute_src_dst_node_temporal_embeddings (models/TCL.py:56-154, TransformerEncoder models/modules.py:209-266), eval mode, fp32.
+ * The call works on SIDES and PAIRS.  A side is one root (v, t) with its K sampled neighbours, as get_historical_neighbors returns them
+ * (any strategy: sampling is not part of the call).  Its sequence has S = K + 1 positions: position 0 is the root itself (edge id 0,
+ * time t), positions 1..K the neighbours.  Encoder input of a position:
+ *     node_proj(node_feat[id]) + edge_proj(edge_feat[eid]) + time_proj(cos(w float32(t - t_nbr) + b)) + depth_embedding[position]
+ * (a padded slot, id 0, reads node_feat[0], edge_feat[0] and dt = t - 0).  A pair names two sides a, b.  Every layer applies the SAME
+ * transformer block four times: self-attention on a, on b, then a over b's self-attended sequence and b over a's (both read the
+ * self-attended sequences).  Every attention masks the keys whose node id is 0.  Block: nn.MultiheadAttention (scale 1 / sqrt(d / heads)),
+ * LayerNorm(x + attn), Linear d -> 4d, ReLU, Linear 4d -> d, LayerNorm(residual).  out_a / out_b = output_layer(position 0) after the last
+ * layer.  A side named by several pairs has its encoder input and its first self-attention computed once.  A pair's rows do not depend on
+ * the other pairs of the call.  A sequence without any valid key (root id 0 and no neighbour) attends to nothing: its attention term is
+ * zero (the reference returns NaN there).
+ * Configurations: 1 <= num_neighbors <= 63; d = node_feat_dim, edge_feat_dim, time_feat_dim multiples of 4, each <= 256; 1 <= num_heads <= 8
+ * dividing d; 1 <= num_layers <= DYGNN_MAX_LAYERS.  Others: DYGNN_E_UNSUPPORTED.  num_neighbors <= 0: DYGNN_E_INVALID.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct dygnn_tcl_config {
+    int32_t node_feat_dim, edge_feat_dim, time_feat_dim;   /* d = F_n, F_e, F_t                                                 */
+    int32_t num_neighbors;                                 /* K of the call; the depth embedding has K + 1 rows                 */
+    int32_t num_layers, num_heads;
+    int32_t num_node_rows, num_edge_rows;                  /* rows of node_feat / edge_feat: ids outside read row 0             */
+} dygnn_tcl_config;
+
+typedef struct dygnn_tcl_layer_weights {                   /* transformers.l.*, PyTorch [out,in] layout                         */
+    const float *in_proj_w, *in_proj_b;                    /* multi_head_attention.in_proj_{weight,bias}        [3d,d],[3d]     */
+    const float *out_proj_w, *out_proj_b;                  /* multi_head_attention.out_proj                     [d,d],[d]       */
+    const float *fc0_w, *fc0_b;                            /* linear_layers.0                                   [4d,d],[4d]     */
+    const float *fc1_w, *fc1_b;                            /* linear_layers.1                                   [d,4d],[d]      */
+    const float *norm0_w, *norm0_b;                        /* norm_layers.0                                     [d]             */
+    const float *norm1_w, *norm1_b;                        /* norm_layers.1                                     [d]             */
+} dygnn_tcl_layer_weights;
+
+typedef struct dygnn_tcl_weights {
+    const float *time_w, *time_b;                          /* time_encoder.w.{weight,bias}                   [F_t,1],[F_t]      */
+    const float *depth_w;                                  /* depth_embedding.weight                         [K+1,d]            */
+    const float *proj_node_w, *proj_node_b;                /* projection_layer.node                          [d,d],[d]          */
+    const float *proj_edge_w, *proj_edge_b;                /* projection_layer.edge                          [d,F_e],[d]        */
+    const float *proj_time_w, *proj_time_b;                /* projection_layer.time                          [d,F_t],[d]        */
+    dygnn_tcl_layer_weights layers[DYGNN_MAX_LAYERS];
+    const float *output_w, *output_b;                      /* output_layer                                   [d,d],[d]          */
+} dygnn_tcl_weights;
+
+/* Optional intermediates of the first min(rows, n_pairs) pairs (device buffers, each nullable); index 1 of the second axis is side a / b.
+ * Values at padded positions are unspecified. */
+typedef struct dygnn_tcl_taps {
+    int64_t rows;
+    float* encoder_input;                                  /* [rows, 2, S, d]                                                   */
+    float* layer_out[DYGNN_MAX_LAYERS];                    /* [rows, 2, S, d] the two cross-attention outputs of layer l        */
+} dygnn_tcl_taps;
+
+/* DYGNN_OK, or why dygnn_tcl_workspace_bytes returned 0 (message in dygnn_last_error) */
+int dygnn_tcl_check(const dygnn_tcl_config* cfg_host);
+/* Activations of the sides and of the 2 n_pairs sequences of the pairs, their Q / K / V and attention output, and the pair index.
+ * 0 = the configuration is refused. */
+size_t dygnn_tcl_workspace_bytes(const dygnn_tcl_config* cfg_host, int64_t n_sides, int64_t n_pairs);
+/* side_* / nbr_* are device arrays; pair_a / pair_b are HOST arrays (checked against [0, n_sides) before any launch and copied). */
+int dygnn_tcl_forward(const dygnn_tcl_config* cfg_host, const dygnn_tcl_weights* w_host, const float* node_feat, const float* edge_feat,
+                      const int64_t* side_root /* [n_sides] */, const double* side_time /* [n_sides] */,
+                      const int64_t* nbr_id /* [n_sides, K] */, const int64_t* nbr_eid /* [n_sides, K] */, const float* nbr_t /* [n_sides, K] */,
+                      int64_t n_sides, const int32_t* pair_a_host /* [n_pairs] */, const int32_t* pair_b_host /* [n_pairs] */, int64_t n_pairs,
+                      float* out_a /* [n_pairs, d] */, float* out_b /* [n_pairs, d] */, const dygnn_tcl_taps* taps_host /* or NULL */,
+                      void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
+
 /* Evaluation metrics on the device, replacing the scikit-learn host round trip of
  * get_link_prediction_metrics / get_node_classification_metrics (utils/metrics.py:5-34; called per batch at
  * evaluate_models_utils.py:139-150 and per evaluation at :245-249).  predicts / labels: [n_groups, group_size] float32
