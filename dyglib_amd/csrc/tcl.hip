@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "mfma_tile.h"
+#include "tcl.h"
 #include "tgat_attn.h"
 
 namespace dygnn {
@@ -373,7 +374,7 @@ __global__ void k_tcl_tap(const float* __restrict__ X, const int32_t* __restrict
         }                                                         \
     } while (0)
 
-static int check_tcl(const dygnn_tcl_config* c) {
+int check_tcl(const dygnn_tcl_config* c) {
     DYGNN_REQUIRE(c != nullptr, "tcl: config is NULL");
     DYGNN_REQUIRE(c->num_neighbors > 0, "Number of sampled neighbors for each node should be greater than 0!");      // utils/utils.py:157
     DYGNN_REQUIRE(c->node_feat_dim > 0 && c->edge_feat_dim > 0 && c->time_feat_dim > 0, "tcl: feature dims must be positive");
@@ -423,6 +424,15 @@ static int launch_encode(const dygnn_tcl_config& c, const dygnn_tcl_weights& w, 
                        c.num_neighbors, c.node_feat_dim, c.edge_feat_dim, c.time_feat_dim, (int64_t)c.num_node_rows, (int64_t)c.num_edge_rows, X0);
     DYGNN_LAUNCH_CHECK();
     return DYGNN_OK;
+}
+
+int encode(hipStream_t s, const dygnn_tcl_config& c, const dygnn_tcl_weights& w, const float* node_feat, const float* edge_feat, const int64_t* side_root,
+           const double* side_time, const int64_t* nbr_id, const int64_t* nbr_eid, const float* nbr_t, int64_t N, float* X0) {
+    const int MT = (c.num_neighbors + 1 + 15) / 16;
+    return MT == 1 ? launch_encode<1>(c, w, node_feat, edge_feat, side_root, side_time, nbr_id, nbr_eid, nbr_t, N, X0, s)
+         : MT == 2 ? launch_encode<2>(c, w, node_feat, edge_feat, side_root, side_time, nbr_id, nbr_eid, nbr_t, N, X0, s)
+         : MT == 3 ? launch_encode<3>(c, w, node_feat, edge_feat, side_root, side_time, nbr_id, nbr_eid, nbr_t, N, X0, s)
+                   : launch_encode<4>(c, w, node_feat, edge_feat, side_root, side_time, nbr_id, nbr_eid, nbr_t, N, X0, s);
 }
 
 }  // namespace tcl
@@ -492,11 +502,7 @@ extern "C" int dygnn_tcl_forward(const dygnn_tcl_config* cfg, const dygnn_tcl_we
     const bool tapping = tap_rows > 0;
     const int64_t sd4 = (int64_t)S * d / 4;
 
-    const int MT = (S + 15) / 16;
-    int rc = MT == 1 ? launch_encode<1>(*cfg, *w, node_feat, edge_feat, side_root, side_time, nbr_id, nbr_eid, nbr_t, N, X0, s)
-           : MT == 2 ? launch_encode<2>(*cfg, *w, node_feat, edge_feat, side_root, side_time, nbr_id, nbr_eid, nbr_t, N, X0, s)
-           : MT == 3 ? launch_encode<3>(*cfg, *w, node_feat, edge_feat, side_root, side_time, nbr_id, nbr_eid, nbr_t, N, X0, s)
-                     : launch_encode<4>(*cfg, *w, node_feat, edge_feat, side_root, side_time, nbr_id, nbr_eid, nbr_t, N, X0, s);
+    int rc = encode(s, *cfg, *w, node_feat, edge_feat, side_root, side_time, nbr_id, nbr_eid, nbr_t, N, X0);
     if (rc) return rc;
     if (tapping && taps->encoder_input) {
         hipLaunchKernelGGL(k_tcl_tap, dim3((unsigned)(2 * tap_rows)), dim3(kThreads), 0, s, X0, own, sd4, reinterpret_cast<f4*>(taps->encoder_input));

@@ -13,6 +13,7 @@
 // K and V stay un-materialised: the attention kernels gather the k neighbour input rows x_ij = [h_lower | edge | cos(w dt + b)]
 // on the fly and work with W_k,h^T q_ih; the products go through the library's GEMMs (gemm.h), the weight gradients through one grouped
 // split-K launch per layer (train::dw_grouped).
+#include "colsum.h"
 #include "common.h"
 #include "dropout.h"
 #include "gemm.h"
@@ -379,25 +380,6 @@ __global__ void k_tt_feat0_rows(const float* __restrict__ g, const int32_t* __re
     if (float* frow = feat0_row(fg, ids[i], Fn)) atomicAdd(frow + (e - i * Fn), g[e]);
 }
 
-// Column sums in a fixed order: out[c] += sum_r A[r][c].  Stage 1: one workgroup per 32 rows -> part[blk][c]; stage 2: the partials in
-// block order.  (Deterministic: the time encoder's and the LayerNorm's gradients are the same bits run to run.)
-constexpr int kColRows = 32;
-__global__ __launch_bounds__(256) void k_tt_colsum_part(const float* __restrict__ A, int lda, int64_t rows, int cols, float* __restrict__ part) {
-    const int64_t r0 = (int64_t)blockIdx.x * kColRows, r1 = r0 + kColRows < rows ? r0 + kColRows : rows;
-    for (int c = threadIdx.x; c < cols; c += blockDim.x) {
-        float s = 0.f;
-        for (int64_t r = r0; r < r1; ++r) s += A[r * lda + c];
-        part[(size_t)blockIdx.x * cols + c] = s;
-    }
-}
-__global__ __launch_bounds__(256) void k_tt_colsum_fin(const float* __restrict__ part, int nblk, int cols, float* __restrict__ out) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    float s = 0.f;
-    for (int b = 0; b < nblk; ++b) s += part[(size_t)b * cols + c];
-    out[c] += s;
-}
-
 __global__ void k_tt_tabs(const float** tabs, const float* node_feat, const float* edge_feat) { tabs[0] = node_feat; tabs[1] = edge_feat; }
 
 // ---- workspace --------------------------------------------------------------------------------------------------------------------------
@@ -447,16 +429,6 @@ static TrainPlan make_plan(const dygnn_tgat_config& c, int64_t B) {
 static int check_train(const dygnn_tgat_config* cfg) {
     static_assert(4 * 64 * NC == 1024, "check_tgat bounds Dkv by the columns a lane holds");
     return check_tgat(cfg);
-}
-
-static int colsum(hipStream_t s, const float* A, int lda, int64_t rows, int cols, float* part, float* out) {
-    if (rows <= 0) return DYGNN_OK;
-    const int nblk = (int)ceil_div(rows, kColRows);
-    hipLaunchKernelGGL(k_tt_colsum_part, dim3((unsigned)nblk), dim3(256), 0, s, A, lda, rows, cols, part);
-    DYGNN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_tt_colsum_fin, dim3((unsigned)ceil_div(cols, 256)), dim3(256), 0, s, part, nblk, cols, out);
-    DYGNN_LAUNCH_CHECK();
-    return DYGNN_OK;
 }
 
 size_t train_plan_bytes(const dygnn_tgat_config& cfg, int64_t batch) { return make_plan(cfg, batch).total; }

@@ -3,9 +3,12 @@
 signatures, same parameter names and shapes (a reference checkpoint loads with strict=True); the forward runs in libdygnn_hip.so
 (`dygnn_tcl_forward`, dyglib_amd/csrc/tcl.hip).
 
-Inference only (eval or train mode under torch.no_grad()): with autograd recording the calls raise NotImplementedError (the training path:
-backward, dropout, autograd, is not built yet).  All three neighbour sampling strategies work: the neighbours are sampled by
-`NeighborSampler.get_historical_neighbors_device` in the reference's call order (sources, then destinations) and handed to the library.
+Inference (eval or train mode under torch.no_grad()) takes `dygnn_tcl_forward`.  Training (train mode with autograd recording) takes
+`dygnn_tcl_train_forward` / `dygnn_tcl_backward` (dyglib_amd/csrc/tcl_train.hip) through `_TclTrainFunction`: dropout `self.dropout` from the
+counter-based generator of dropout.h, every parameter receives a gradient, the feature tables do not.  Eval mode with autograd recording, and
+`compute_step_embeddings` (the evaluation step) with autograd recording in either mode, raise NotImplementedError.  All three neighbour
+sampling strategies work: the neighbours are sampled by `NeighborSampler.get_historical_neighbors_device` in the reference's call order
+(sources, then destinations) and handed to the library, on both paths.
 
 In TCL the source embedding depends on the destination it is paired with (cross-attention), so an evaluation step has FOUR results:
 `compute_step_embeddings` returns (src of the positive call, dst, src of the negative call, neg_dst)."""
@@ -22,6 +25,58 @@ from . import _capi
 from .modules import TimeEncoder
 from .neighbor_sampler import NeighborSampler
 from .tgat import _to_dev, _workspace
+
+
+class _TclTrainFunction(torch.autograd.Function):
+    """compute_src_dst_node_temporal_embeddings with gradients: forward = dygnn_tcl_train_forward, backward = dygnn_tcl_backward.  The
+    parameters are passed as inputs only so that autograd routes their gradients; the workspace belongs to this one call (a training step
+    issues a negative and a positive call before one backward())."""
+
+    @staticmethod
+    def forward(ctx, model, sides, B, num_neighbors, dropout_p, seed, *params):
+        dev = model.output_layer.weight.device
+        d = model.node_feat_dim
+        out = (torch.empty((B, d), dtype=torch.float32, device=dev), torch.empty((B, d), dtype=torch.float32, device=dev))
+        ctx.model, ctx.B = model, B
+        if B == 0:                                                           # nothing to launch, here or in backward
+            return out
+        lib = model._lib
+        cfg, w = model._config(num_neighbors), model._weights()
+        nbytes = lib.dygnn_tcl_train_workspace_bytes(C.byref(cfg), B)
+        if nbytes == 0:                                  # AssertionError (bad argument) or NotImplementedError (unsupported) with the library's message
+            _capi.check(lib.dygnn_tcl_check(C.byref(cfg)))
+            _capi.check(-1)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)          # lives until this call's backward
+        roots, tms, nbr, eid, nts = sides
+        _capi.check(lib.dygnn_tcl_train_forward(C.byref(cfg), C.byref(w), model.node_raw_features.data_ptr(), model.edge_raw_features.data_ptr(),
+                                                roots.data_ptr(), tms.data_ptr(), nbr.data_ptr(), eid.data_ptr(), nts.data_ptr(), B, float(dropout_p),
+                                                int(seed), out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), nbytes, _capi.current_stream_ptr()))
+        ctx.cfg, ctx.w, ctx.ws, ctx.dropout_p, ctx.seed = cfg, w, ws, float(dropout_p), int(seed)
+        ctx.feats = (model.node_raw_features, model.edge_raw_features)        # regathered by the backward pass
+        ctx.param_versions = [(p.data_ptr(), p._version) for p in params]
+        return out
+
+    @staticmethod
+    def backward(ctx, g_src, g_dst):
+        model = ctx.model
+        params = list(model.parameters())
+        if ctx.B == 0:
+            return (None,) * (6 + len(params))
+        dev = ctx.ws.device
+        g_src = (g_src if g_src is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
+        g_dst = (g_dst if g_dst is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
+        # the backward pass re-reads the CURRENT parameter values: they must be the ones the forward used
+        if [(p.data_ptr(), p._version) for p in params] != ctx.param_versions:
+            raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
+                               "a TCL parameter changed between this call's forward and its backward")
+        sizes = [p.numel() for p in params]
+        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)       # one fill for all gradient buffers
+        grads = [g.view_as(p) for g, p in zip(flat.split(sizes), params)]
+        gstruct = model._weights({id(p): g for p, g in zip(params, grads)})
+        _capi.check(model._lib.dygnn_tcl_backward(C.byref(ctx.cfg), C.byref(ctx.w), C.byref(gstruct), g_src.data_ptr(), g_dst.data_ptr(), ctx.B,
+                                                  ctx.dropout_p, ctx.seed, ctx.ws.data_ptr(), ctx.ws.numel(), _capi.current_stream_ptr()))
+        ctx.ws = ctx.feats = None
+        return (None,) * 6 + tuple(grads)
 
 
 class TransformerEncoder(nn.Module):
@@ -74,10 +129,21 @@ class TCL(nn.Module):
                                                  taps: Optional[int] = None):
         """models/TCL.py:56-154: two float32 tensors [B, node_feat_dim]; ONE library call on the sides [src ; dst] and the pairs (i, B + i).
         `taps` = r (not in the reference): also return the intermediates of the first r pairs, (src, dst, dict(encoder_input [r, 2, S, d],
-        layer_out: per layer [r, 2, S, d])); index 0 / 1 of the second axis is the source / destination sequence."""
-        (src, dst), tms = self._inputs((src_node_ids, dst_node_ids), node_interact_times, num_neighbors)
+        layer_out: per layer [r, 2, S, d])); index 0 / 1 of the second axis is the source / destination sequence.
+        In train mode with autograd recording the call is differentiable (dropout self.dropout; `taps` are refused there)."""
+        train = self.training and torch.is_grad_enabled()
+        (src, dst), tms = self._inputs((src_node_ids, dst_node_ids), node_interact_times, num_neighbors, trainable=True)
         B = src.numel()
         sides = self._sample([src, dst], tms, num_neighbors)
+        if train:
+            if taps is not None:
+                raise NotImplementedError("tcl: taps are an inference facility; the training path does not return intermediates")
+            if len(self.transformers) != self.num_layers or self.num_layers > _capi.DYGNN_MAX_LAYERS:
+                raise NotImplementedError(f"tcl: num_layers {self.num_layers} not supported (1..{_capi.DYGNN_MAX_LAYERS})")
+            seed = getattr(self, "_fixed_dropout_seed", None)             # tests pin the masks; normally torch.manual_seed governs them
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            return _TclTrainFunction.apply(self, sides, B, int(num_neighbors), float(self.dropout), seed, *self.parameters())
         idx = np.arange(B, dtype=np.int32)
         out = self._forward(*sides, idx, idx + B, num_neighbors, taps)
         return out if taps is None else (out[0], out[1], out[2])
@@ -101,13 +167,14 @@ class TCL(nn.Module):
         return oa[:B], ob[:B], oa[B:], ob[B:]
 
     # ---- glue ------------------------------------------------------------------------------------------------------------------------
-    def _inputs(self, id_arrays, node_interact_times, num_neighbors):
-        """Refuse what is not built (autograd recording, a CPU model), validate host ids like the reference (IndexError; a root id of 0 is an
-        AssertionError: the reference returns NaN rows for it, every key being masked), and move ids (int64) and times (float64) to the
-        model's device."""
-        if torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("TCL is inference-only on the HIP path: call it under torch.no_grad().  Training (backward, dropout, "
-                                      "autograd) is the follow-up to this forward and is not built yet")
+    def _inputs(self, id_arrays, node_interact_times, num_neighbors, trainable: bool = False):
+        """Refuse what is not built (autograd recording outside the training call, a CPU model), validate host ids like the reference
+        (IndexError; a root id of 0 is an AssertionError: the reference returns NaN rows for it, every key being masked), and move ids (int64)
+        and times (float64) to the model's device.  `trainable`: the caller has a differentiable path for train mode."""
+        if torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters())) and not (trainable and self.training):
+            raise NotImplementedError("this TCL call is inference-only on the HIP path: call it under torch.no_grad().  Gradients flow through "
+                                      "compute_src_dst_node_temporal_embeddings in train mode only (eval mode and compute_step_embeddings "
+                                      "have no backward pass)")
         self.neighbor_sampler._check_strategy()
         assert num_neighbors > 0, "Number of sampled neighbors for each node should be greater than 0!"          # utils/utils.py:157
         assert num_neighbors + 1 == self.depth_embedding.weight.shape[0], \
@@ -146,12 +213,14 @@ class TCL(nn.Module):
         return _capi.TclConfig(self.node_feat_dim, self.edge_feat_dim, self.time_feat_dim, int(num_neighbors), self.num_layers, self.num_heads,
                                self.node_raw_features.shape[0], self.edge_raw_features.shape[0])
 
-    def _weights(self) -> "_capi.TclWeights":
+    def _weights(self, replace: Optional[dict] = None) -> "_capi.TclWeights":
+        """ctypes view of the parameters; `replace` maps id(parameter) to another tensor of the same shape (the gradient buffers of the
+        backward pass)."""
         for p in self.parameters():
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise _capi.DygnnError("parameters must be contiguous float32")
         w = _capi.TclWeights()
-        p = lambda t: t.data_ptr()
+        p = (lambda t: t.data_ptr()) if replace is None else (lambda t: replace[id(t)].data_ptr())
         w.time_w, w.time_b, w.depth_w = p(self.time_encoder.w.weight), p(self.time_encoder.w.bias), p(self.depth_embedding.weight)
         pl = self.projection_layer
         w.proj_node_w, w.proj_node_b = p(pl["node"].weight), p(pl["node"].bias)

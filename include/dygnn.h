@@ -568,6 +568,27 @@ int dygnn_tcl_forward(const dygnn_tcl_config* cfg_host, const dygnn_tcl_weights*
                       float* out_a /* [n_pairs, d] */, float* out_b /* [n_pairs, d] */, const dygnn_tcl_taps* taps_host /* or NULL */,
                       void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
 
+/* TCL training (dyglib_amd/csrc/tcl_train.hip): the train-mode forward of one compute_src_dst_node_temporal_embeddings call and its backward
+ * pass.  The call's 2 batch sides are [src ; dst] and pair p is (side p, side batch + p): no index vector, no stream synchronisation.
+ * Dropout (p in [0, 1)) on the attention probabilities, the attention block's output, relu(fc0) and the fc1 output of every block, masks
+ * from the counter-based generator of dropout.h: site = 8 layer + 4 stage + {0, 1, 2, 3} (stage 0 = self, 1 = cross), sequence index
+ * q = 2 p + side, element ((q H + h) S + i) S + j (site 0), (q S + i) d + c (sites 1, 3), (q S + i) 4d + c (site 2).  dropout_p = 0 is the
+ * inference forward within fp32 rounding.  The workspace belongs to ONE forward / backward pair: it keeps the sampled sides and every
+ * activation the backward pass reads; node_feat / edge_feat must stay alive until the backward has run (it regathers their rows).
+ * workspace_bytes: 0 = the configuration or the batch is refused (message in dygnn_last_error).  batch == 0: DYGNN_OK, nothing launched. */
+size_t dygnn_tcl_train_workspace_bytes(const dygnn_tcl_config* cfg_host, int64_t batch);
+int dygnn_tcl_train_forward(const dygnn_tcl_config* cfg_host, const dygnn_tcl_weights* w_host, const float* node_feat, const float* edge_feat,
+                            const int64_t* side_root /* [2 batch] */, const double* side_time /* [2 batch] */,
+                            const int64_t* nbr_id /* [2 batch, K] */, const int64_t* nbr_eid /* [2 batch, K] */, const float* nbr_t /* [2 batch, K] */,
+                            int64_t batch, float dropout_p, uint64_t seed, float* out_src /* [batch, d] */, float* out_dst /* [batch, d] */,
+                            void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
+/* grads: a dygnn_tcl_weights of gradient buffers (same shapes as the weights), ZEROED by the caller: every tensor is accumulated into.
+ * Weight matrices are summed with float atomics (not bit-reproducible run to run); biases, LayerNorm, depth and time-encoder gradients
+ * are fixed-order column sums. */
+int dygnn_tcl_backward(const dygnn_tcl_config* cfg_host, const dygnn_tcl_weights* w_host, const dygnn_tcl_weights* grads_host,
+                       const float* grad_out_src /* [batch, d] */, const float* grad_out_dst /* [batch, d] */, int64_t batch, float dropout_p,
+                       uint64_t seed, void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
+
 /* Evaluation metrics on the device, replacing the scikit-learn host round trip of
  * get_link_prediction_metrics / get_node_classification_metrics (utils/metrics.py:5-34; called per batch at
  * evaluate_models_utils.py:139-150 and per evaluation at :245-249).  predicts / labels: [n_groups, group_size] float32
