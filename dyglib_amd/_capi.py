@@ -16,7 +16,7 @@ import torch  # noqa: F401  (must be imported first: see module docstring)
 from . import _build
 
 DYGNN_MAX_LAYERS = 8
-ABI_VERSION = 20
+ABI_VERSION = 21
 TABLE_NODE_ZERO, TABLE_EDGE_ZERO = 1, 2      # table_flags of dygnn_dygformer_forward_tables (include/dygnn.h)
 
 c_i32p = C.POINTER(C.c_int32)
@@ -200,6 +200,11 @@ SIGNATURES = {
     "dygnn_graphmixer_workspace_bytes": (C.c_size_t, [C.POINTER(GraphmixerConfig), C.c_int64]),
     "dygnn_graphmixer_forward": (C.c_int, [C.POINTER(GraphmixerConfig), C.POINTER(GraphmixerWeights), C.POINTER(Csr), C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(GraphmixerTaps), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dygnn_graphmixer_train_workspace_bytes": (C.c_size_t, [C.POINTER(GraphmixerConfig), C.c_int64]),
+    "dygnn_graphmixer_train_forward": (C.c_int, [C.POINTER(GraphmixerConfig), C.POINTER(GraphmixerWeights), C.POINTER(Csr), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dygnn_graphmixer_backward": (C.c_int, [C.POINTER(GraphmixerConfig), C.POINTER(GraphmixerWeights), C.POINTER(GraphmixerWeights), C.c_void_p,
+                                            C.c_int64, C.c_float, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dygnn_tcl_check": (C.c_int, [C.POINTER(TclConfig)]),
     "dygnn_tcl_workspace_bytes": (C.c_size_t, [C.POINTER(TclConfig), C.c_int64, C.c_int64]),
     "dygnn_tcl_forward": (C.c_int, [C.POINTER(TclConfig), C.POINTER(TclWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

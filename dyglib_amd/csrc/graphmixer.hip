@@ -9,6 +9,7 @@
 //
 // Products use the fp32 MFMA tile product of mfma_tile.h.
 #include "common.h"
+#include "graphmixer.h"
 #include "mfma_tile.h"
 #include "tgat_attn.h"
 
@@ -26,27 +27,9 @@ using tile::wave_product;
 using tile::wave_sum;
 using tile::z4;
 
-__device__ __forceinline__ float gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }      // nn.GELU(), exact
 constexpr int kFfnRows = 64;      // token rows per workgroup of k_gm_ffn
 constexpr int kFfnChunk = 64;     // hidden columns in LDS at a time
 constexpr int kOutRoots = 16;
-constexpr int kMaxTokens = 32;
-constexpr float kLnEps = 1e-5f;
-
-struct Csr {
-    const int64_t* indptr;
-    const int32_t* nbr;
-    const int32_t* eid;
-    const double* ts;
-    int64_t num_nodes;
-};
-
-// the strictly-earlier prefix [lo, end) of the root's CSR row; an id outside the graph has the empty row 0 (as query_row, sampler.hip)
-__device__ __forceinline__ void history(const Csr& g, int64_t node, double t, int lane, int64_t& lo, int64_t& end) {
-    if (node < 0 || node >= g.num_nodes) node = 0;
-    lo = g.indptr[node];
-    end = wave_lower_bound(g.ts, lo, g.indptr[node + 1], t, lane);
-}
 
 // ---- node encoder (models/GraphMixer.py:117-141) ---------------------------------------------------------------------------------------------
 // One root per workgroup, so a hub root (m = time_gap rows) holds up nobody: short roots retire and their slots are refilled.  The four waves
@@ -316,7 +299,7 @@ __global__ __launch_bounds__(kThreads) void k_gm_out(const float* __restrict__ X
         }                                                         \
     } while (0)
 
-static int check_graphmixer(const dygnn_graphmixer_config* c) {
+int check_graphmixer(const dygnn_graphmixer_config* c) {
     DYGNN_REQUIRE(c != nullptr, "graphmixer: config is NULL");
     // utils/utils.py:157, for the link encoder's and the node encoder's sampler call
     DYGNN_REQUIRE(c->num_neighbors > 0, "Number of sampled neighbors for each node should be greater than 0!");
@@ -334,6 +317,21 @@ static int check_graphmixer(const dygnn_graphmixer_config* c) {
     GM_SUPPORTED(c->node_feat_dim <= 256 && c->edge_feat_dim <= 256 && c->time_feat_dim <= 256, "graphmixer: feature dims > 256 not supported");
     GM_SUPPORTED(c->channel_hidden_dim >= 16 && c->channel_hidden_dim % 16 == 0 && c->channel_hidden_dim <= 1024,
                  "graphmixer: channel_hidden_dim %d not supported (a multiple of 16, at most 1024)", c->channel_hidden_dim);
+    return DYGNN_OK;
+}
+
+int node_term(hipStream_t s, const Csr& g, const float* node_feat, const int64_t* nodes, const double* times, int64_t n, int Fn, int G, float* term) {
+    hipLaunchKernelGGL(k_gm_node, dim3((unsigned)n), dim3(kThreads), 0, s, g, node_feat, nodes, times, Fn, G, term);
+    DYGNN_LAUNCH_CHECK();
+    return DYGNN_OK;
+}
+
+int project(hipStream_t s, const Csr& g, const float* edge_feat, const int64_t* nodes, const double* times, int64_t n, const dygnn_graphmixer_weights& w,
+            int K, int C, int Ft, float* X) {
+    const size_t lds_proj = (size_t)kMaxTokens * (round16(C + Ft) + 4) * sizeof(float);
+    if (int rc = lds_limit(k_gm_proj, lds_proj)) return rc;
+    hipLaunchKernelGGL(k_gm_proj, dim3((unsigned)n), dim3(kThreads), lds_proj, s, g, edge_feat, nodes, times, w.time_w, w.time_b, w.proj_w, w.proj_b, K, C, Ft, X);
+    DYGNN_LAUNCH_CHECK();
     return DYGNN_OK;
 }
 
@@ -394,13 +392,8 @@ extern "C" int dygnn_graphmixer_forward(const dygnn_graphmixer_config* cfg, cons
     const int64_t tap_rows = taps ? (taps->rows < n ? taps->rows : n) : 0;
     const size_t tap_bytes = (size_t)(tap_rows > 0 ? tap_rows : 0) * K * C * sizeof(float);
 
-    hipLaunchKernelGGL(k_gm_node, dim3((unsigned)n), dim3(kThreads), 0, s, g, node_feat, nodes, times, Fn, G, term);
-    DYGNN_LAUNCH_CHECK();
-    const size_t lds_proj = (size_t)kMaxTokens * (round16(C + Ft) + 4) * sizeof(float);
-    if (int rc = lds_limit(k_gm_proj, lds_proj)) return rc;
-    hipLaunchKernelGGL(k_gm_proj, dim3((unsigned)n), dim3(kThreads), lds_proj, s, g, edge_feat, nodes, times, w->time_w, w->time_b, w->proj_w, w->proj_b,
-                       K, C, Ft, X);
-    DYGNN_LAUNCH_CHECK();
+    if (int rc = node_term(s, g, node_feat, nodes, times, n, Fn, G, term)) return rc;
+    if (int rc = project(s, g, edge_feat, nodes, times, n, *w, K, C, Ft, X)) return rc;
     if (tap_bytes && taps->projection) DYGNN_HIP(hipMemcpyAsync(taps->projection, X, tap_bytes, hipMemcpyDeviceToDevice, s));
     const size_t lds_tok = (size_t)(K + Kh) * C * sizeof(float);
     const size_t lds_ffn = (size_t)kFfnRows * ((round16(C) + 4) + (kFfnChunk + 4)) * sizeof(float);

@@ -3,9 +3,13 @@
 `compute_node_temporal_embeddings` / `set_neighbor_sampler` signatures, same parameter names and shapes (a reference checkpoint
 loads with strict=True); the forward runs in libdygnn_hip.so (`dygnn_graphmixer_forward`, dyglib_amd/csrc/graphmixer.hip).
 
-Inference only (eval or train mode under torch.no_grad()) with `recent` neighbour sampling: with autograd recording the calls raise
-NotImplementedError (the training path: backward, dropout, autograd, is not built yet), and so does a sampler with a random strategy
-(the reference's evaluation forces `recent` for GraphMixer, evaluate_models_utils.py, and its training default is `recent`).
+Inference (eval or train mode under torch.no_grad()) takes `dygnn_graphmixer_forward`.  Training (train mode with autograd recording) takes
+`dygnn_graphmixer_train_forward` / `dygnn_graphmixer_backward` (dyglib_amd/csrc/graphmixer_train.hip) through `_GraphMixerTrainFunction`:
+dropout `self.dropout` from the counter-based generator of dropout.h; every parameter receives a gradient except the frozen time encoder,
+whose `.grad` stays None as in the reference; the feature tables receive none.  Eval mode with autograd recording, `compute_step_embeddings`
+(the evaluation step) and `taps` with autograd recording raise NotImplementedError.  `recent` neighbour sampling only, on both paths: a
+sampler with a random strategy raises NotImplementedError (the reference's evaluation forces `recent` for GraphMixer,
+evaluate_models_utils.py, and its training default is `recent`).
 
 The node encoder's `time_gap` most recent neighbours are read straight from the temporal CSR inside the kernel: no [n, time_gap] array
 exists on the host or on the device, and the call's workspace (n (K C + F_n) floats) does not depend on time_gap."""
@@ -22,6 +26,57 @@ from . import _capi
 from .modules import TimeEncoder
 from .neighbor_sampler import NeighborSampler
 from .tgat import _to_dev, _workspace
+
+
+class _GraphMixerTrainFunction(torch.autograd.Function):
+    """compute_node_temporal_embeddings with gradients: forward = dygnn_graphmixer_train_forward, backward = dygnn_graphmixer_backward.  The
+    parameters are passed as inputs only so that autograd routes their gradients; the workspace belongs to this one call (a training step
+    issues a negative and a positive call before one backward())."""
+
+    @staticmethod
+    def forward(ctx, model, nodes, tms, num_neighbors, time_gap, dropout_p, seed, *params):
+        dev = model.output_layer.weight.device
+        n = nodes.numel()
+        out = torch.empty((n, model.node_feat_dim), dtype=torch.float32, device=dev)
+        ctx.model, ctx.n = model, n
+        if n == 0:                                                           # nothing to launch, here or in backward
+            return out
+        lib = model._lib
+        cfg, w = model._config(num_neighbors, time_gap), model._weights()
+        nbytes = lib.dygnn_graphmixer_train_workspace_bytes(C.byref(cfg), n)
+        if nbytes == 0:                                  # AssertionError (bad argument) or NotImplementedError (unsupported) with the library's message
+            _capi.check(lib.dygnn_graphmixer_check(C.byref(cfg)))
+            _capi.check(-1)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)          # lives until this call's backward
+        _capi.check(lib.dygnn_graphmixer_train_forward(C.byref(cfg), C.byref(w), model.neighbor_sampler.csr.on_device(dev),
+                                                       model.node_raw_features.data_ptr(), model.edge_raw_features.data_ptr(), nodes.data_ptr(),
+                                                       tms.data_ptr(), n, float(dropout_p), int(seed), out.data_ptr(), ws.data_ptr(), nbytes,
+                                                       _capi.current_stream_ptr()))
+        ctx.cfg, ctx.w, ctx.ws, ctx.dropout_p, ctx.seed = cfg, w, ws, float(dropout_p), int(seed)
+        ctx.param_versions = [(p.data_ptr(), p._version) for p in params]
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        model = ctx.model
+        params = list(model.parameters())
+        if ctx.n == 0:
+            return (None,) * (7 + len(params))
+        dev = ctx.ws.device
+        g_out = (g_out if g_out is not None else torch.zeros((ctx.n, model.node_feat_dim), device=dev)).contiguous().float()
+        # the backward pass re-reads the CURRENT parameter values: they must be the ones the forward used
+        if [(p.data_ptr(), p._version) for p in params] != ctx.param_versions:
+            raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
+                               "a GraphMixer parameter changed between this call's forward and its backward")
+        trainable = [p for p in params if p.requires_grad]                    # the time encoder is frozen: no buffer, None below
+        sizes = [p.numel() for p in trainable]
+        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)       # one fill for all gradient buffers
+        grads = {id(p): g.view_as(p) for g, p in zip(flat.split(sizes), trainable)}
+        gstruct = model._weights(grads)
+        _capi.check(model._lib.dygnn_graphmixer_backward(C.byref(ctx.cfg), C.byref(ctx.w), C.byref(gstruct), g_out.data_ptr(), ctx.n, ctx.dropout_p,
+                                                         ctx.seed, ctx.ws.data_ptr(), ctx.ws.numel(), _capi.current_stream_ptr()))
+        ctx.ws = None
+        return (None,) * 7 + tuple(grads.get(id(p)) for p in params)
 
 
 class FeedForwardNet(nn.Module):
@@ -83,17 +138,25 @@ class GraphMixer(nn.Module):
     # ---- the reference's entry points ------------------------------------------------------------------------------------------
     def compute_src_dst_node_temporal_embeddings(self, src_node_ids, dst_node_ids, node_interact_times, num_neighbors: int = 20,
                                                  time_gap: int = 2000) -> Tuple[torch.Tensor, torch.Tensor]:
-        """models/GraphMixer.py:52-68: two float32 tensors [B, node_feat_dim]; ONE library call on the roots [src ; dst]."""
-        (src, dst), tms = self._inputs((src_node_ids, dst_node_ids), node_interact_times)
+        """models/GraphMixer.py:52-68: two float32 tensors [B, node_feat_dim]; ONE library call on the roots [src ; dst].
+        In train mode with autograd recording the call is differentiable (dropout self.dropout)."""
+        (src, dst), tms = self._inputs((src_node_ids, dst_node_ids), node_interact_times, trainable=True)
         B = src.numel()
-        out = self._forward(torch.cat([src, dst]), torch.cat([tms, tms]), num_neighbors, time_gap)
+        nodes, tms = torch.cat([src, dst]), torch.cat([tms, tms])
+        if self.training and torch.is_grad_enabled():
+            out = self._train_forward(nodes, tms, num_neighbors, time_gap)
+        else:
+            out = self._forward(nodes, tms, num_neighbors, time_gap)
         return out[:B], out[B:]
 
     def compute_node_temporal_embeddings(self, node_ids, node_interact_times, num_neighbors: int = 20, time_gap: int = 2000,
                                          taps: Optional[int] = None):
         """models/GraphMixer.py:70-150: [n, node_feat_dim].  `taps` = r (not in the reference): also return the intermediates of the first r
-        roots, (embeddings, dict(projection, layer_out, token_mean, node_term)), for the parity tests."""
-        (nodes,), tms = self._inputs((node_ids,), node_interact_times)
+        roots, (embeddings, dict(projection, layer_out, token_mean, node_term)), for the parity tests.
+        In train mode with autograd recording the call is differentiable (dropout self.dropout; `taps` are refused there)."""
+        (nodes,), tms = self._inputs((node_ids,), node_interact_times, trainable=taps is None)
+        if self.training and torch.is_grad_enabled():
+            return self._train_forward(nodes, tms, num_neighbors, time_gap)
         return self._forward(nodes, tms, num_neighbors, time_gap, taps)
 
     def compute_step_embeddings(self, src_node_ids, dst_node_ids, neg_dst_node_ids, node_interact_times, num_neighbors: int = 20,
@@ -107,12 +170,14 @@ class GraphMixer(nn.Module):
         return out[:B], out[B:2 * B], out[2 * B:]
 
     # ---- glue ------------------------------------------------------------------------------------------------------------------------
-    def _inputs(self, id_arrays, node_interact_times):
-        """Refuse what is not built (autograd recording, random sampling, a CPU model), validate host ids like the reference (IndexError),
-        and move ids (int64) and times (float64) to the model's device."""
-        if torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("GraphMixer is inference-only on the HIP path: call it under torch.no_grad().  Training (backward, dropout, "
-                                      "autograd) is the follow-up to this forward and is not built yet")
+    def _inputs(self, id_arrays, node_interact_times, trainable: bool = False):
+        """Refuse what is not built (autograd recording outside the training calls, random sampling, a CPU model), validate host ids like the
+        reference (IndexError), and move ids (int64) and times (float64) to the model's device.  `trainable`: the caller has a differentiable
+        path for train mode."""
+        if torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters())) and not (trainable and self.training):
+            raise NotImplementedError("this GraphMixer call is inference-only on the HIP path: call it under torch.no_grad().  Gradients flow "
+                                      "through compute_src_dst_node_temporal_embeddings and compute_node_temporal_embeddings (without taps) in "
+                                      "train mode only (eval mode and compute_step_embeddings have no backward pass)")
         self.neighbor_sampler._check_strategy()
         if self.neighbor_sampler.sample_neighbor_strategy != "recent":
             raise NotImplementedError(f"GraphMixer on the HIP path samples on the device and supports sample_neighbor_strategy 'recent' only, not "
@@ -140,12 +205,14 @@ class GraphMixer(nn.Module):
                                       int(self.token_dim_expansion_factor * K), int(self.channel_dim_expansion_factor * Cc),      # as FeedForwardNet
                                       int(num_neighbors), int(time_gap), self.node_raw_features.shape[0])
 
-    def _weights(self) -> "_capi.GraphmixerWeights":
+    def _weights(self, replace: Optional[dict] = None) -> "_capi.GraphmixerWeights":
+        """ctypes view of the parameters; `replace` maps id(parameter) to another tensor of the same shape (the gradient buffers of the
+        backward pass; a parameter it does not name, the frozen time encoder, becomes NULL)."""
         for p in self.parameters():
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise _capi.DygnnError("parameters must be contiguous float32")
         w = _capi.GraphmixerWeights()
-        p = lambda t: t.data_ptr()
+        p = (lambda t: t.data_ptr()) if replace is None else (lambda t: replace[id(t)].data_ptr() if id(t) in replace else None)
         w.time_w, w.time_b = p(self.time_encoder.w.weight), p(self.time_encoder.w.bias)
         w.proj_w, w.proj_b = p(self.projection_layer.weight), p(self.projection_layer.bias)
         for l, m in enumerate(self.mlp_mixers):
@@ -156,6 +223,14 @@ class GraphMixer(nn.Module):
             L.channel_fc0_w, L.channel_fc0_b, L.channel_fc1_w, L.channel_fc1_b = p(cf[0].weight), p(cf[0].bias), p(cf[3].weight), p(cf[3].bias)
         w.output_w, w.output_b = p(self.output_layer.weight), p(self.output_layer.bias)
         return w
+
+    def _train_forward(self, nodes: torch.Tensor, tms: torch.Tensor, num_neighbors: int, time_gap: int) -> torch.Tensor:
+        if self.num_layers > _capi.DYGNN_MAX_LAYERS or len(self.mlp_mixers) != self.num_layers:
+            raise NotImplementedError(f"graphmixer: num_layers {self.num_layers} not supported (1..{_capi.DYGNN_MAX_LAYERS})")
+        seed = getattr(self, "_fixed_dropout_seed", None)                 # tests pin the masks; normally torch.manual_seed governs them
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        return _GraphMixerTrainFunction.apply(self, nodes, tms, int(num_neighbors), int(time_gap), float(self.dropout), seed, *self.parameters())
 
     def _forward(self, nodes: torch.Tensor, tms: torch.Tensor, num_neighbors: int, time_gap: int, taps: Optional[int] = None):
         dev = nodes.device

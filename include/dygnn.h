@@ -504,6 +504,28 @@ int dygnn_graphmixer_forward(const dygnn_graphmixer_config* cfg_host, const dygn
                              float* out /* [n, F_n] */, const dygnn_graphmixer_taps* taps_host /* or NULL */,
                              void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
 
+/* GraphMixer training (dyglib_amd/csrc/graphmixer_train.hip): the train-mode forward of one compute_node_temporal_embeddings call on n roots
+ * (a training call: [src ; dst]) and its backward pass; `recent` sampling.  Dropout (p in [0, 1)) after the GELU and on the output of the
+ * token and of the channel FFN of every block, masks from the counter-based generator of dropout.h: site = 4 layer + s, q = the root's
+ * index in the call, elements numbered as the reference's dense activations: s = 0 token hidden [n, C, Kh]: (q C + ch) Kh + i; s = 1 token
+ * FFN output [n, C, K]: (q C + ch) K + j; s = 2 channel hidden [n, K, H]: (q K + j) H + h; s = 3 channel FFN output [n, K, C]:
+ * (q K + j) C + c.  dropout_p = 0 is the inference forward within fp32 rounding.  The workspace belongs to ONE forward / backward pair: it
+ * keeps the gathered token rows and every activation the backward pass reads (nothing in it has a time_gap dimension; the caller's
+ * arrays and tables are not read again).  Arguments are checked as dygnn_graphmixer_forward checks them.
+ * workspace_bytes: 0 = the configuration or n_roots is refused (message in dygnn_last_error).  n == 0: DYGNN_OK, nothing launched. */
+size_t dygnn_graphmixer_train_workspace_bytes(const dygnn_graphmixer_config* cfg_host, int64_t n_roots);
+int dygnn_graphmixer_train_forward(const dygnn_graphmixer_config* cfg_host, const dygnn_graphmixer_weights* w_host, const dygnn_csr* csr_host,
+                                   const float* node_feat, const float* edge_feat, const int64_t* nodes, const double* times, int64_t n,
+                                   float dropout_p, uint64_t seed, float* out /* [n, F_n] */, void* workspace, size_t workspace_bytes,
+                                   dygnn_stream_t stream);
+/* grads: a dygnn_graphmixer_weights of gradient buffers (same shapes as the weights), ZEROED by the caller: every tensor is accumulated
+ * into; its time_w / time_b may be NULL and are never written (the time encoder is frozen).  The four matrices projection_layer, output_layer
+ * and channel fc0 / fc1 are summed with float atomics (not bit-reproducible run to run); every bias, both LayerNorms and the token FFN's
+ * matrices are fixed-order sums (the same bits run to run). */
+int dygnn_graphmixer_backward(const dygnn_graphmixer_config* cfg_host, const dygnn_graphmixer_weights* w_host,
+                              const dygnn_graphmixer_weights* grads_host, const float* grad_out /* [n, F_n] */, int64_t n, float dropout_p,
+                              uint64_t seed, void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * TCL.compute_src_dst_node_temporal_embeddings (models/TCL.py:56-154, TransformerEncoder models/modules.py:209-266), eval mode, fp32.
