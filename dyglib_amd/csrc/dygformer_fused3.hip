@@ -1,4 +1,4 @@
-// Fused DyGFormer forward, inference: the host dispatch of k_dygformer_fused3 and its six inference instances (kernel and design:
+// Fused DyGFormer forward, inference: the host dispatch of k_dygformer_fused3 and its nine inference instances (kernel and design:
 // fused3_forward.h, fused3_device.h; training instances: dygformer_fused3_train.hip; backward: dygformer_fused3_bwd.hip; weight
 // packing: dygformer_fused3_pack.hip).
 #include "fused3_forward.h"
@@ -31,7 +31,8 @@ int forward_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_
     if (taps && taps->ev_kernel_start) DYGNN_HIP(hipEventRecord(static_cast<hipEvent_t>(taps->ev_kernel_start), s));
     a.pair_stride = (f.np == 2 && pair_stride > 0) ? pair_stride : 0;      // one pair per workgroup (128 tokens): nothing to share inside a workgroup
     // Inference runs the pooled last layer.  A call that taps the last layer's per-token output gets it from the full stream (PL = 2); its
-    // embeddings are the pooled ones bit for bit.  Every other call streams the pooled form (PL = 1).
+    // embeddings are the pooled ones bit for bit.  Every other call streams the pooled form: PL = 1, or from kPooledTailMinWorkgroups
+    // workgroups on PL = 3 followed by k_pooled_tail, which gives the same bits (dygformer_pooled_tail.hip).
     const bool tap_last = taps && taps->layer_out[d.NL - 1] != nullptr;
     if (!tap_last) { a.stream = packed + pl.fused3 + f.stream_p; a.nstages = f.nstages_p; }
     const bool small = f.np == 2 && a.pair_stride == 0 && B <= kSmallBatchPairs && !small_off();      // a small call: one pair per four-wave workgroup
@@ -42,12 +43,16 @@ int forward_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_
         hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), kLdsBytes, s, a);
         return DYGNN_OK;
     };
+    const bool tail = !tap_last && pooled_tail_wanted(grid);
     int rc;
-    if (small) rc = tap_last ? launch(k_dygformer_fused3<4, false, 4, 2>, 256) : launch(k_dygformer_fused3<4, false, 4, 1>, 256);
+    if (tail) rc = small ? launch(k_dygformer_fused3<4, false, 4, 3>, 256) : f.np == 2 ? launch(k_dygformer_fused3<4, false, 8, 3>, 512) : launch(k_dygformer_fused3<8, false, 8, 3>, 512);
+    else if (small) rc = tap_last ? launch(k_dygformer_fused3<4, false, 4, 2>, 256) : launch(k_dygformer_fused3<4, false, 4, 1>, 256);
     else if (f.np == 2) rc = tap_last ? launch(k_dygformer_fused3<4, false, 8, 2>, 512) : launch(k_dygformer_fused3<4, false, 8, 1>, 512);
     else rc = tap_last ? launch(k_dygformer_fused3<8, false, 8, 2>, 512) : launch(k_dygformer_fused3<8, false, 8, 1>, 512);
     if (rc) return rc;
     DYGNN_LAUNCH_CHECK();
+    if (tail)
+        if (int rc2 = pooled_tail(a.pooled_rows, 2 * B, a.w2frag, a.b2_last, a.outfrag, a.outb, a.Fn, out_src, out_dst, s)) return rc2;
     if (taps && taps->ev_kernel_stop) DYGNN_HIP(hipEventRecord(static_cast<hipEvent_t>(taps->ev_kernel_stop), s));
     return DYGNN_OK;
 }

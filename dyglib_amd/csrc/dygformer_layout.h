@@ -79,6 +79,7 @@ struct WorkspaceLayout {
     size_t dims;        // CallDims[groups]: max_window_src, max_window_dst, S_s, S_d, T_s, T_d, T, -
     size_t hist_len;    // int32[2B]
     size_t end_pos;     // int64[2B]
+    size_t pooled;      // float[2B][4 D + D padded to 16]: per-side token means of a fused launch whose epilogue is deferred (k_pooled_tail)
     size_t X, Xn, QKV, Hid;   // generic path activations, token stride Tmax
     size_t total;
 };
@@ -90,6 +91,7 @@ inline WorkspaceLayout make_workspace_layout(const Dims& d, int64_t B) {
     w.dims = take((size_t)(B > 0 ? B : 1) * sizeof(CallDims));      // one CallDims per group, at most one group per pair
     w.hist_len = take((size_t)2 * B * sizeof(int32_t));
     w.end_pos = take((size_t)2 * B * sizeof(int64_t));
+    w.pooled = take((size_t)2 * B * (4 * d.D + ((d.D + 15) & ~15)) * sizeof(float));
     const size_t rows = (size_t)B * d.Tmax;
     w.X = take(rows * d.D * sizeof(float));
     w.Xn = take(rows * d.D * sizeof(float));

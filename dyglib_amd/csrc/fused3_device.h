@@ -42,6 +42,7 @@ using i4 = __attribute__((ext_vector_type(4))) int;
 
 constexpr int kD = 200, kDP = 208, kNT = 13, kKC = 13, kHD = 100, kHid = 800, kC = 50;
 constexpr int kFrag = 256;            // floats per 16x16 fragment
+constexpr int kPoolRow = kHid + kDP;  // deferred pooled epilogue: one (pair, side) row = 800 means of gelu(h) | 208 means of the residual
 constexpr int kRing = 52;             // LDS ring, fragments
 // kStage = 26 (two stages of 26 fragments: half the stage barriers) measured +1.25 % at L = 64, +0.8 % at L = 512 (round 3, tools/ab_fused3.py) and
 // NOT kept: with two stages the fragments a step reads ahead ACROSS the barrier that ends a stage belong to a stage whose DMAs that very
@@ -295,7 +296,8 @@ struct WStream {
 #define TSTORE() do { } while (0)
 #endif
 enum { T_WIN = 0, T_PROJ, T_LN, T_QKV, T_QKVBAR, T_ATTN, T_OPROJ, T_FFN, T_POOL, T_MISC, T_POOL1, T_POOL2, T_PNODE, T_PTIME, T_PEDGE, T_PCOOC,
-       T_F_W1 = 16, T_F_GELU, T_F_ADV1, T_F_W2, T_F_ADV2 };      // FFN sub-phases
+       T_F_W1 = 16, T_F_GELU, T_F_ADV1, T_F_W2, T_F_ADV2,              // FFN sub-phases
+       T_E_MEAN = 21, T_E_W2 };      // pooled epilogue: the mean / mean_g columns, the W2 product; T_POOL keeps the output layer alone
 
 // LayerNorm of the register-resident X^T (two-pass, biased variance, eps 1e-5); gamma/beta from LDS
 __device__ __forceinline__ void layernorm(f4 (&xn)[kNT], const f4 (&x)[kNT], const float* gamma, const float* beta, int g, float& mean_o, float& rstd_o) {

@@ -34,6 +34,7 @@ struct Args {
     LayerP layer[DYGNN_MAX_LAYERS];
     const float *outT, *outb;     // output layer: transposed [200][Fn], bias [Fn]
     float *out_src, *out_dst;
+    float* pooled_rows;           // deferred epilogue (PL = 3): [2 B][kPoolRow] token means, row 2 * pair + side (workspace)
     float* tap_enc; float* tap_layer[DYGNN_MAX_LAYERS];
     unsigned long long* stamps;
     int64_t B, G, num_nodes;
@@ -133,6 +134,8 @@ static_assert(8 * 2 * kHid <= kLdsV && kLdsMeanG + 4 * kHid <= kLdsRing, "the po
 //      stream (its own: the last layer carries W1 blocks only) ends there, and the epilogue multiplies the 4 (pair, side) means by W2
 //   2  a call whose taps ask for the last layer's per-token output: the same sums and the same epilogue — the embeddings are those of
 //      PL = 1 bit for bit — and, for the tap alone, the per-token W2 product from the full stream
+//   3  the deferred form of 1 for large launches: the kernel ends with the token means, written as dense rows (Args.pooled_rows) instead of
+//      LDS columns; k_pooled_tail (dygformer_pooled_tail.hip) runs the W2 product and the output layer once per launch, same chains
 template <int TPW, bool TR, int NW = 8, int PL = 0>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(const Args a) {
     static_assert(!(TR && PL != 0), "the training forward keeps the per-token form: its backward reads the per-token activations");
@@ -839,13 +842,13 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
             }
             ws.advance(26, (TR && active) ? 4 : 0);      // training: the four hpre / hact stores of this step stay in flight through the W2 block
             TACC(T_F_ADV1);
-            if (PL == 1 && last) continue;       // the pooled stream: this layer's blocks are W1 only
+            if ((PL == 1 || PL == 3) && last) continue;       // the pooled stream: this layer's blocks are W1 only
             if (active) ffn_w2(f2, h, ringl + ws.pos * kFrag);
             TACC(T_F_W2);
             ws.advance(26);
             TACC(T_F_ADV2);
         }
-        if (!(PL == 1 && last)) {
+        if (!((PL == 1 || PL == 3) && last)) {
         ws.fit(1);
         {
             const float* b2 = lds + kLdsRing + ws.pos * kFrag + 4 * g;
@@ -885,7 +888,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
 #pragma unroll
             for (int w = 0; w < TPW; ++w) s += pool[((pi * TPW + w) * 2 + side) * kDP + n];
             const float mv = n < kD ? s / (float)(side ? Td : Tse) : 0.f;
-            mean[pi * 2 * kDP + i] = mv;
+            if constexpr (PL == 3) { if (pair_ok) a.pooled_rows[(2 * b + side) * kPoolRow + kHid + n] = mv; }
+            else mean[pi * 2 * kDP + i] = mv;
             if constexpr (TR) { if (pair_ok && n < kD) a.tr.pooled[((int64_t)side * a.B + b) * kD + n] = mv; }
         }
         if constexpr (PL != 0) {
@@ -897,9 +901,13 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
                 float s = 0.f;
 #pragma unroll
                 for (int w = 0; w < TPW; ++w) if (16 * w < T) s += gpool[((pi * TPW + w) * 2 + side) * kHid + n];      // a wave without tokens wrote nothing
-                meang[pi * 2 * kHid + i] = s / (float)(side ? Td : Tse);
+                const float mg = s / (float)(side ? Td : Tse);
+                if constexpr (PL == 3) { if (pair_ok) a.pooled_rows[(2 * b + side) * kPoolRow + n] = mg; }
+                else meang[pi * 2 * kHid + i] = mg;
             }
+            if constexpr (PL == 3) { TACC(T_E_MEAN); TSTORE(); return; }      // k_pooled_tail takes it from here
             __syncthreads();
+            TACC(T_E_MEAN);
             // mean[col] += W2 . mean_g[col] + b2 on the matrix cores: wave w owns model-dim tiles w, w + NW, ...; 50 k-chunks whose fragments
             // (used by this wave only) come straight from global memory ten at a time, one group ahead.  One tile's sum is one fixed chain
             // (even chunks in acc0, odd in acc1), whichever wave of whichever kernel shape runs it.
@@ -932,6 +940,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
             }
         }
         __syncthreads();
+        if constexpr (PL != 0) TACC(T_E_W2);
         // output layer on the matrix cores: out^T[j][col] = sum_k W[j][k] mean[col][k] + b[j]; wave w owns output tiles w, w+8, ...
         // (each fragment is used by one wave only, so they come straight from global memory, all 13 of a tile in flight)
         const int ntile = (a.Fn + 15) >> 4;
@@ -983,6 +992,7 @@ inline int fused3_args(const Dims& d, const PackedLayout& pl, const dygnn_dygfor
     a.tab_off = f.tab_off; a.tab_slots = f.tab_slots; a.tab_bits = f.tab_bits;
     a.outT = packed + pl.outputT; a.outb = w->output_b;
     a.out_src = out_src; a.out_dst = out_dst;
+    a.pooled_rows = reinterpret_cast<float*>(ws + wl.pooled);
     a.tap_enc = taps ? taps->encoder_input : nullptr;
     a.stamps = taps ? reinterpret_cast<unsigned long long*>(taps->phase_cycles) : nullptr;
     a.B = B; a.G = G; a.num_nodes = csr->num_nodes; a.Fn = d.Fn; a.Fe = d.Fe; a.Ft = d.Ft; a.P = d.P; a.L = d.L; a.NL = d.NL; a.Tmax = d.Tmax;

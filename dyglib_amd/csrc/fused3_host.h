@@ -40,6 +40,17 @@ int proj_slots(int nchunk);                    // k-chunk slots a projection cha
 constexpr int64_t kSmallBatchPairs = 256;
 inline bool small_off() { static const bool off = [] { const char* e = getenv("DYGNN_SMALL_BATCH_KERNELS"); return e && e[0] == '0'; }(); return off; }
 
+// Untapped inference launches of at least this many workgroups end with the token means and leave the last W2 product and the output
+// layer to k_pooled_tail (one more launch); smaller ones keep the in-kernel epilogue.  DESIGN §4.3 has the timings behind the figure.
+constexpr int64_t kPooledTailMinWorkgroups = 2000;
+// DYGNN_POOLED_TAIL = 1 / 0 puts every / no untapped inference launch on the tail path (tests, A/B runs); anything else: the size rule.
+// Read on every call.
+inline bool pooled_tail_wanted(int64_t workgroups) {
+    const char* e = getenv("DYGNN_POOLED_TAIL");
+    if (e && (e[0] == '0' || e[0] == '1') && e[1] == '\0') return e[0] == '1';
+    return workgroups >= kPooledTailMinWorkgroups;
+}
+
 // dygformer_generic.hip
 int window_lengths_device(const Dims& d, const dygnn_csr* csr, const int64_t* src, const int64_t* dst, const double* times,
                           int64_t B, int64_t G, char* ws, const WorkspaceLayout& wl, hipStream_t s);
@@ -52,6 +63,9 @@ int forward_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_
                    const dygnn_csr* csr, const float* node_feat, const float* edge_feat, const int64_t* src,
                    const int64_t* dst, const double* times, int64_t B, int64_t G, int64_t pair_stride, float* out_src, float* out_dst, char* ws,
                    const WorkspaceLayout& wl, const dygnn_dygformer_taps* taps, uint32_t table_flags, hipStream_t s);
+// dygformer_pooled_tail.hip: rows [R][1008] (R = 2 B, row 2 * pair + side) -> out_src / out_dst [B][Fn]
+int pooled_tail(const float* rows, int64_t R, const float* w2frag, const float* b2, const float* outfrag, const float* outb, int Fn,
+                float* out_src, float* out_dst, hipStream_t s);
 // dygformer_fused3_train.hip
 int forward_fused3_train(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, const float* packed, const dygnn_csr* csr,
                          const float* node_feat, const float* edge_feat, const int64_t* src, const int64_t* dst, const double* times, int64_t B,

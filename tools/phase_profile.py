@@ -2,6 +2,7 @@
 """Diagnostic: per-phase cycle shares of the fused DyGFormer kernel from in-kernel s_memtime stamps.
 Needs the stamps build:  python -m dyglib_amd._build --variant=stamps
 Run:  DYGNN_LIB_VARIANT=stamps python tools/phase_profile.py
+PHASE_UNTAPPED=1 stamps the kernel an ordinary inference call runs (the pooled stream, no taps) instead of the tapped full stream.
 Never quote this build's run time (the stamps perturb it): read the SHARES."""
 import os
 import sys
@@ -28,6 +29,16 @@ E = data.num_interactions
 NG = int(os.environ.get("PHASE_GROUPS", "16"))     # groups of 200 pairs per launch (bench default: 16)
 sl = slice(E - 200 * NG, E)
 src, dst, t = data.src_node_ids[sl], data.dst_node_ids[sl], data.node_interact_times[sl]
+if os.environ.get("PHASE_UNTAPPED") == "1":
+    make_taps = model._make_taps
+
+    def stamps_only(taps, B, dev_):
+        s = make_taps(taps, B, dev_)
+        s.encoder_input = None
+        for l in range(model.num_layers):
+            s.layer_out[l] = None
+        return s
+    model._make_taps = stamps_only
 with torch.no_grad():
     for _ in range(3):
         model.compute_src_dst_node_temporal_embeddings(src, dst, t, _group_size=200)
@@ -39,14 +50,15 @@ st = taps["phase_cycles"].cpu().numpy().astype(np.int64)      # [4 wg][8 waves][
 if model.impl == 3:
     cats = ["windows+counts", "projection", "layernorm", "QKV (+K/V store)", "barrier after K/V", "attention (S,softmax,PV)",
             "out-projection", "FFN", "mean+output layer", "misc (param copies, taps)", "pool shuffles", "pool barrier", "proj node", "proj time", "proj edge", "proj cooc",
-            "FFN: W1 MFMAs", "FFN: GELU", "FFN: barrier+refill after W1", "FFN: W2 MFMAs", "FFN: barrier+refill after W2"]
+            "FFN: W1 MFMAs", "FFN: GELU", "FFN: barrier+refill after W1", "FFN: W2 MFMAs", "FFN: barrier+refill after W2",
+            "epilogue: mean columns", "epilogue: W2 product"]      # with these two stamped apart, "mean+output layer" is the output layer alone
     tot = st[:, :, 31].astype(np.float64)
     print(f"total ticks per wave: mean {tot.mean():.0f} (min {tot.min():.0f} max {tot.max():.0f})")
     for i, nm in enumerate(cats):
         v = st[:, :, i].astype(np.float64)
         print(f"{nm:28s} {v.mean():12.0f} {100 * v.mean() / tot.mean():6.1f}%   (per-wave min {v.min():.0f} max {v.max():.0f})")
     print("per wave (mean over the 4 stamped workgroups), waves 0..7:")
-    for i in (3, 6, 16, 17, 18, 19, 20):
+    for i in (3, 6, 16, 17, 18, 19, 20, 21, 22, 8):
         print(f"{cats[i]:28s} " + " ".join(f"{st[:, w, i].mean():9.0f}" for w in range(8)))
     sys.exit(0)
 NL = 2
