@@ -18,6 +18,8 @@ from . import _build
 DYGNN_MAX_LAYERS = 8
 ABI_VERSION = 21
 TABLE_NODE_ZERO, TABLE_EDGE_ZERO = 1, 2      # table_flags of dygnn_dygformer_forward_tables (include/dygnn.h)
+TABLE_NODE_PROJ, TABLE_EDGE_PROJ = 4, 8      # ... and of dygnn_dygformer_forward_projected: the channel's projected table is passed
+PROJ_ROW_FLOATS = 64                         # floats per (table row, patch slot) of a projected table
 
 c_i32p = C.POINTER(C.c_int32)
 c_i64p = C.POINTER(C.c_int64)
@@ -161,6 +163,13 @@ SIGNATURES = {
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(DygformerTaps),
                                                  C.c_int32, C.c_void_p, C.c_uint32]),
+    "dygnn_dygformer_projected_bytes": (C.c_size_t, [C.POINTER(DygformerConfig), C.c_int64]),
+    "dygnn_dygformer_project_table": (C.c_int, [C.POINTER(DygformerConfig), C.POINTER(DygformerWeights), C.c_int32, C.c_void_p, C.c_int64,
+                                                C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dygnn_dygformer_forward_projected": (C.c_int, [C.POINTER(DygformerConfig), C.POINTER(DygformerWeights), C.c_void_p, C.POINTER(Csr),
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(DygformerTaps),
+                                                    C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "dygnn_tgat_workspace_bytes": (C.c_size_t, [C.POINTER(TgatConfig), C.c_int64]),
     "dygnn_tgat_forward_levels": (C.c_int, [C.POINTER(TgatConfig), C.POINTER(TgatWeights), C.POINTER(TgatLevels), C.c_void_p, C.c_void_p, C.c_int64,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

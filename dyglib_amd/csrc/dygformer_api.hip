@@ -369,13 +369,12 @@ extern "C" int dygnn_dygformer_repack(const dygnn_dygformer_config* cfg, const d
     return pack_impl(cfg, w, packed, packed_bytes, stream, true, fused_only != 0);
 }
 
-extern "C" int dygnn_dygformer_forward_tables(const dygnn_dygformer_config* cfg, const dygnn_dygformer_weights* w, const void* packed,
-                                              const dygnn_csr* csr, const float* node_feat, const float* edge_feat, const int64_t* src,
-                                              const int64_t* dst, const double* times, int64_t batch, int64_t group_size, int64_t pair_stride,
-                                              float* out_src, float* out_dst, void* workspace, size_t workspace_bytes, const dygnn_dygformer_taps* taps,
-                                              int32_t impl, dygnn_stream_t stream, uint32_t table_flags) {
+static int forward_impl(const dygnn_dygformer_config* cfg, const dygnn_dygformer_weights* w, const void* packed, const dygnn_csr* csr,
+                        const float* node_feat, const float* edge_feat, const int64_t* src, const int64_t* dst, const double* times, int64_t batch,
+                        int64_t group_size, int64_t pair_stride, float* out_src, float* out_dst, void* workspace, size_t workspace_bytes,
+                        const dygnn_dygformer_taps* taps, int32_t impl, dygnn_stream_t stream, uint32_t table_flags, const float* node_proj,
+                        const float* edge_proj) {
     if (int rc = check_config(cfg)) return rc;
-    DYGNN_REQUIRE((table_flags & ~(uint32_t)(DYGNN_TABLE_NODE_ZERO | DYGNN_TABLE_EDGE_ZERO)) == 0, "forward: unknown table_flags bit");
     const Dims d = make_dims(*cfg);
     if (int rc = check_weights(d, w)) return rc;
     DYGNN_REQUIRE(csr && csr->indptr && csr->num_nodes >= 1, "forward: bad csr");
@@ -402,10 +401,41 @@ extern "C" int dygnn_dygformer_forward_tables(const dygnn_dygformer_config* cfg,
     }
     if (impl == 3 || (impl == 0 && can_fuse3))
         return forward_fused3(d, pl, w, static_cast<const float*>(packed), csr, node_feat, edge_feat, src, dst, times, batch, group_size, pair_stride, out_src,
-                              out_dst, static_cast<char*>(workspace), wl, taps, table_flags, as_stream(stream));
+                              out_dst, static_cast<char*>(workspace), wl, taps, table_flags, node_proj, edge_proj, as_stream(stream));
     // the generic path multiplies the tables as they are: the flags promise nothing it uses
     return forward_generic(d, pl, w, static_cast<const float*>(packed), csr, node_feat, edge_feat, src, dst, times, batch, group_size, pair_stride, out_src,
                            out_dst, static_cast<char*>(workspace), wl, taps, as_stream(stream));
+}
+
+extern "C" int dygnn_dygformer_forward_tables(const dygnn_dygformer_config* cfg, const dygnn_dygformer_weights* w, const void* packed,
+                                              const dygnn_csr* csr, const float* node_feat, const float* edge_feat, const int64_t* src,
+                                              const int64_t* dst, const double* times, int64_t batch, int64_t group_size, int64_t pair_stride,
+                                              float* out_src, float* out_dst, void* workspace, size_t workspace_bytes, const dygnn_dygformer_taps* taps,
+                                              int32_t impl, dygnn_stream_t stream, uint32_t table_flags) {
+    if (int rc = check_config(cfg)) return rc;
+    DYGNN_REQUIRE((table_flags & ~(uint32_t)(DYGNN_TABLE_NODE_ZERO | DYGNN_TABLE_EDGE_ZERO)) == 0, "forward: unknown table_flags bit");
+    return forward_impl(cfg, w, packed, csr, node_feat, edge_feat, src, dst, times, batch, group_size, pair_stride, out_src, out_dst, workspace,
+                        workspace_bytes, taps, impl, stream, table_flags, nullptr, nullptr);
+}
+
+// The projected tables are the caller's (dygnn_dygformer_project_table): a channel whose bit is set takes the row-addition path of the
+// fused inference kernels.  DYGNN_PROJ_TABLES=0 ignores them (the MFMA path), as the generic path does.
+extern "C" int dygnn_dygformer_forward_projected(const dygnn_dygformer_config* cfg, const dygnn_dygformer_weights* w, const void* packed,
+                                                 const dygnn_csr* csr, const float* node_feat, const float* edge_feat, const int64_t* src,
+                                                 const int64_t* dst, const double* times, int64_t batch, int64_t group_size, int64_t pair_stride,
+                                                 float* out_src, float* out_dst, void* workspace, size_t workspace_bytes,
+                                                 const dygnn_dygformer_taps* taps, int32_t impl, dygnn_stream_t stream, uint32_t table_flags,
+                                                 const float* node_proj, const float* edge_proj) {
+    if (int rc = check_config(cfg)) return rc;
+    DYGNN_REQUIRE((table_flags & ~(uint32_t)(DYGNN_TABLE_NODE_ZERO | DYGNN_TABLE_EDGE_ZERO | DYGNN_TABLE_NODE_PROJ | DYGNN_TABLE_EDGE_PROJ)) == 0,
+                  "forward: unknown table_flags bit");
+    DYGNN_REQUIRE(!(table_flags & DYGNN_TABLE_NODE_PROJ) || node_proj != nullptr, "forward: table_flags names a projected node table, node_proj is NULL");
+    DYGNN_REQUIRE(!(table_flags & DYGNN_TABLE_EDGE_PROJ) || edge_proj != nullptr, "forward: table_flags names a projected edge table, edge_proj is NULL");
+    DYGNN_REQUIRE(((reinterpret_cast<uintptr_t>(node_proj) | reinterpret_cast<uintptr_t>(edge_proj)) & 15) == 0, "forward: projected tables must be 16-byte aligned");
+    const bool off = proj_tables_off();
+    return forward_impl(cfg, w, packed, csr, node_feat, edge_feat, src, dst, times, batch, group_size, pair_stride, out_src, out_dst, workspace,
+                        workspace_bytes, taps, impl, stream, table_flags & (uint32_t)(DYGNN_TABLE_NODE_ZERO | DYGNN_TABLE_EDGE_ZERO),
+                        !off && (table_flags & DYGNN_TABLE_NODE_PROJ) ? node_proj : nullptr, !off && (table_flags & DYGNN_TABLE_EDGE_PROJ) ? edge_proj : nullptr);
 }
 
 extern "C" int dygnn_dygformer_forward(const dygnn_dygformer_config* cfg, const dygnn_dygformer_weights* w, const void* packed,

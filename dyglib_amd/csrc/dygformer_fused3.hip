@@ -19,14 +19,20 @@ static void drop_zero_channels(v3::Args& a, uint32_t table_flags) {
 int forward_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, const float* packed,
                    const dygnn_csr* csr, const float* node_feat, const float* edge_feat, const int64_t* src,
                    const int64_t* dst, const double* times, int64_t B, int64_t G, int64_t pair_stride, float* out_src, float* out_dst, char* ws,
-                   const WorkspaceLayout& wl, const dygnn_dygformer_taps* taps, uint32_t table_flags, hipStream_t s) {
+                   const WorkspaceLayout& wl, const dygnn_dygformer_taps* taps, uint32_t table_flags, const float* node_proj, const float* edge_proj,
+                   hipStream_t s) {
     using namespace v3;
     if (!supported(d)) { set_error("fused kernel: unsupported shape"); return DYGNN_E_UNSUPPORTED; }
     if (int rc = window_lengths_device(d, csr, src, dst, times, B, G, ws, wl, s)) return rc;
     Args a{};
     PackLayout3 f;
     if (int rc = fused3_args(d, pl, w, packed, csr, node_feat, edge_feat, src, dst, times, B, G, out_src, out_dst, ws, wl, taps, a, f)) return rc;
-    drop_zero_channels(a, table_flags);
+    // A projected table (dygformer_proj_tables.hip) takes its channel out of the walk exactly as a zero table does; the kernel adds the
+    // projected rows instead.  A table flagged all zero needs neither.
+    if (table_flags & DYGNN_TABLE_NODE_ZERO) node_proj = nullptr;
+    if (table_flags & DYGNN_TABLE_EDGE_ZERO) edge_proj = nullptr;
+    drop_zero_channels(a, table_flags | (node_proj ? DYGNN_TABLE_NODE_ZERO : 0u) | (edge_proj ? DYGNN_TABLE_EDGE_ZERO : 0u));
+    a.pt_node = node_proj; a.pt_edge = edge_proj;
     if (taps && taps->seq_lens) DYGNN_HIP(hipMemcpyAsync(taps->seq_lens, ws + wl.dims + 2 * sizeof(int32_t), 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     if (taps && taps->ev_kernel_start) DYGNN_HIP(hipEventRecord(static_cast<hipEvent_t>(taps->ev_kernel_start), s));
     a.pair_stride = (f.np == 2 && pair_stride > 0) ? pair_stride : 0;      // one pair per workgroup (128 tokens): nothing to share inside a workgroup

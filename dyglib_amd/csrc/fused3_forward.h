@@ -42,6 +42,8 @@ struct Args {
                                   // negative call of one edge: where their (src, t) agree the src side is projected once
     int Fn, Fe, Ft, P, L, NL, Tmax;
     int nchunk[4];
+    const float *pt_node, *pt_edge;   // inference only: the channel's table already projected per (row, patch slot), [rows][P][kProjRow] (dygformer_proj_tables.hip);
+                                  // its chunks have left the walk like a zero table's (nchunk = 0) and the token owner adds P rows instead.  nullptr: the MFMA path
     float qscale;
     train::TrainOut tr;           // training forward only (k_dygformer_fused3<.., true>): the dense activations the backward pass reads
 };
@@ -541,6 +543,24 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
             else if (rem == 3) c_group(L0c, integral_constant<int, 3>{}, std::true_type{}, fa, cq);
         };
 
+        // ---- projected tables (Args.pt_node / pt_edge): W[:, slot p] . table[row] was computed once per (row, slot) when the weights were
+        // packed, so the channel is P row additions per token: x = ((bias + PT[row_0][0]) + PT[row_1][1]) + ..., one fixed chain per element in
+        // every instance.  A (row, slot) segment holds the channel's four x tiles (zero outside its 50 rows): lane (c, g) reads its accumulator
+        // registers as four float4s.  Absent positions read the zero word, by the address select of gather().
+        auto pt_load = [&](f4 (&q)[4], const float* pt, const int32_t* idx, int p) {
+            const int pc = p < P ? p : P - 1;
+            const int32_t r = idx[pos0 + pc];
+            const uintptr_t pz = reinterpret_cast<uintptr_t>(g_zero16), m = (tv && p < P) ? ~uintptr_t(0) : uintptr_t(0);
+            const uintptr_t pr = reinterpret_cast<uintptr_t>(pt + ((size_t)(r < 0 ? 0 : r) * P + pc) * kProjRow + 4 * g);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) q[v] = ldg4(reinterpret_cast<const float*>(pz + ((pr + 64 * v - pz) & m)));
+        };
+        auto pt_add = [&](auto L0c, const f4 (&q)[4]) {
+            constexpr int L0 = decltype(L0c)::value;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) x[L0 + v] = x[L0 + v] + q[v];
+        };
+
         // Channel order node, time, edge, cooc: the edge gathers are issued before the time channel computes its cosines.  A wave whose
         // tile is empty, or a source tile shared with the first pair (f4), only keeps the barriers of the channel.  A gathered channel
         // whose table the caller declared all zero has nchunk = 0 (and no slots in the walked sequence): no gathers, no MFMAs, no
@@ -552,11 +572,31 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
         if (work_n) prefill(bq, cu, a.node_feat, ids, a.Fn);
         TACC(T_PROJ);
         if (work_n) run_gathered(integral_constant<int, 0>{}, bq, cu, a.nchunk[0], a.node_feat, ids, a.Fn); else run_idle(a.nchunk[0]);
+        // projected channels: the edge rows of the first two slots are in flight while the time channel runs, like the gathers they replace;
+        // a projected node table (rare: the reference's node tables are zero) adds its rows here
+        f4 pq[2][4];
+        bool proj_e = false;
+        if constexpr (!TR) {
+            if (work && a.pt_node != nullptr) {
+                for (int p = 0; p < P; ++p) { pt_load(pq[0], a.pt_node, ids, p); pt_add(integral_constant<int, 0>{}, pq[0]); }
+            }
+            proj_e = work && a.pt_edge != nullptr;
+            if (proj_e) { pt_load(pq[0], a.pt_edge, eids, 0); pt_load(pq[1], a.pt_edge, eids, 1); }
+        }
         if (work_e) prefill(bq, cu, a.edge_feat, eids, a.Fe);          // in flight while the time channel runs
         TACC(T_PNODE);
         if (work) run_time(integral_constant<int, 6>{}, a.nchunk[2]); else run_idle(a.nchunk[2]);
         TACC(T_PTIME);
         if (work_e) run_gathered(integral_constant<int, 3>{}, bq, cu, a.nchunk[1], a.edge_feat, eids, a.Fe); else run_idle(a.nchunk[1]);
+        if constexpr (!TR) {
+            if (proj_e) {
+                for (int p = 0; p < P; p += 2) {       // slots 0 and 1 were loaded above; patches of more slots load the next two after these
+                    pt_add(integral_constant<int, 3>{}, pq[0]);
+                    if (p + 1 < P) pt_add(integral_constant<int, 3>{}, pq[1]);
+                    if (p + 2 < P) { pt_load(pq[0], a.pt_edge, eids, p + 2); pt_load(pq[1], a.pt_edge, eids, p + 3); }
+                }
+            }
+        }
         TACC(T_PEDGE);
         if (active) run_cooc(integral_constant<int, 9>{}, a.nchunk[3]); else run_idle(a.nchunk[3]);
         TACC(T_PCOOC);

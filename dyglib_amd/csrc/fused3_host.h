@@ -51,6 +51,11 @@ inline bool pooled_tail_wanted(int64_t workgroups) {
     return workgroups >= kPooledTailMinWorkgroups;
 }
 
+// Projected feature tables (dygformer_proj_tables.hip): one (table row, patch slot) segment = the channel's four x tiles, kProjRow floats
+constexpr int kProjRow = 64;
+// DYGNN_PROJ_TABLES = 0: a forward call ignores the projected tables it is handed (the MFMA path; tests, A/B runs).  Read on every call.
+inline bool proj_tables_off() { const char* e = getenv("DYGNN_PROJ_TABLES"); return e && e[0] == '0' && e[1] == '\0'; }
+
 // dygformer_generic.hip
 int window_lengths_device(const Dims& d, const dygnn_csr* csr, const int64_t* src, const int64_t* dst, const double* times,
                           int64_t B, int64_t G, char* ws, const WorkspaceLayout& wl, hipStream_t s);
@@ -62,7 +67,8 @@ int pack_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_wei
 int forward_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, const float* packed,
                    const dygnn_csr* csr, const float* node_feat, const float* edge_feat, const int64_t* src,
                    const int64_t* dst, const double* times, int64_t B, int64_t G, int64_t pair_stride, float* out_src, float* out_dst, char* ws,
-                   const WorkspaceLayout& wl, const dygnn_dygformer_taps* taps, uint32_t table_flags, hipStream_t s);
+                   const WorkspaceLayout& wl, const dygnn_dygformer_taps* taps, uint32_t table_flags, const float* node_proj, const float* edge_proj,
+                   hipStream_t s);
 // dygformer_pooled_tail.hip: rows [R][1008] (R = 2 B, row 2 * pair + side) -> out_src / out_dst [B][Fn]
 int pooled_tail(const float* rows, int64_t R, const float* w2frag, const float* b2, const float* outfrag, const float* outb, int Fn,
                 float* out_src, float* out_dst, hipStream_t s);

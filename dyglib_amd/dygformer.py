@@ -15,6 +15,7 @@ train_link_prediction.py:229-257 work unchanged.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -156,12 +157,16 @@ class DyGFormer(nn.Module):
         self._packed_key = None
         self._workspace: Dict[tuple, torch.Tensor] = {}
         self.impl = 0                      # 0 auto, 1 generic, 3 fused (see include/dygnn.h)
+        # projected feature tables (_projected_tables): a table whose projected form is larger than this keeps the kernel's MFMA path
+        self.proj_table_max_bytes = 1 << 30
+        self.__dict__["_proj"] = None
 
     # ---- feature tables ------------------------------------------------------------------------
     def _set_table(self, which: str, table: torch.Tensor, all_zero: Optional[bool] = None) -> None:
         """Store a feature table with its "all zero" bit; all_zero=None looks at the tensor (one reduction, a host sync on a GPU)."""
         self.__dict__["_" + which + "_raw_features"] = table
         self.__dict__["_" + which + "_all_zero"] = bool(not table.any().item()) if all_zero is None else bool(all_zero)
+        self.__dict__["_proj"] = None       # the projected tables were built from the table this one replaces
 
     @property
     def node_raw_features(self) -> torch.Tensor:
@@ -184,6 +189,60 @@ class DyGFormer(nn.Module):
         """table_flags of dygnn_dygformer_forward_tables for the current tables.  A table edited IN PLACE after it was assigned is not
         seen: assign it again (`model.node_raw_features = model.node_raw_features`)."""
         return (_capi.TABLE_NODE_ZERO if self.__dict__["_node_all_zero"] else 0) | (_capi.TABLE_EDGE_ZERO if self.__dict__["_edge_all_zero"] else 0)
+
+    # ---- projected feature tables --------------------------------------------------------------
+    def _proj_plan(self) -> Dict[str, int]:
+        """Bytes of the projected table each gathered channel gets ({} entries only for channels that get one).  The patch projection of
+        the node / edge channel is linear in the gathered table rows, so W[:, slot p] . table[row] is computed once per (row, slot) and
+        weights version (dygnn_dygformer_project_table) and the fused inference kernel adds patch_size rows per token instead of running
+        the product.  The choice depends on the model's state only, never on a call's batch size or kernel shape: a channel gets a table
+        unless its table is flagged all zero (nothing to add), `impl` pins an implementation, or the projected form exceeds
+        `proj_table_max_bytes` (default 1 GiB per table; patch_size = 8 costs 2 KB per row).  Only impl = 0 — the library's own choice —
+        takes the tables: impl = 1 is the generic path, and impl = 3 names the fused kernel's MFMA projection, whose bits are those of a
+        plain dygnn_dygformer_forward_tables call (the split sum differs from them in the last bits).  DYGNN_PROJ_TABLES=0 (read per call)
+        keeps every channel on the MFMA path, =1 builds the tables whatever their size.  The caveat of `table_flags` applies unchanged: a
+        table edited IN PLACE after it was assigned is not seen — assign it again."""
+        env = os.environ.get("DYGNN_PROJ_TABLES")
+        plan: Dict[str, int] = {}
+        if env == "0" or int(self.impl) != 0:
+            return plan
+        for which in ("node", "edge"):
+            if self.__dict__["_" + which + "_all_zero"]:
+                continue
+            nbytes = int(self._lib.dygnn_dygformer_projected_bytes(C.byref(self._cfg), int(self.__dict__["_" + which + "_raw_features"].shape[0])))
+            if nbytes > 0 and (env == "1" or nbytes <= int(self.proj_table_max_bytes)):
+                plan[which] = nbytes
+        return plan
+
+    def _proj_flags(self, plan: Dict[str, int]) -> int:
+        return (_capi.TABLE_NODE_PROJ if "node" in plan else 0) | (_capi.TABLE_EDGE_PROJ if "edge" in plan else 0)
+
+    def _projected_tables(self, dev, weights) -> Tuple[int, Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """(projected bits of table_flags, projected node table, projected edge table) for an inference call.  Built lazily on the first
+        inference call after a (re)pack of the weights — they live exactly as long as that kernel-ready copy — and dropped with it and
+        whenever a table is assigned."""
+        plan = self._proj_plan()
+        if not plan:
+            return 0, None, None
+        key = (self.__dict__.get("_pack_gen", 0), str(dev), tuple(sorted(plan.items())))
+        cache = self.__dict__["_proj"]
+        if cache is None or cache["key"] != key:
+            old = cache or {}
+            cache = {"key": key}
+            for ch, which in enumerate(("node", "edge")):
+                if which not in plan:
+                    continue
+                table = self.__dict__["_" + which + "_raw_features"]
+                if table.dtype != torch.float32 or not table.is_contiguous():
+                    raise _capi.DygnnError("feature tables must be contiguous float32")
+                buf = old.get(which)
+                if buf is None or buf.numel() != plan[which] or buf.device != dev:
+                    buf = torch.empty(plan[which], dtype=torch.uint8, device=dev)
+                _capi.check(self._lib.dygnn_dygformer_project_table(C.byref(self._cfg), C.byref(weights), ch, table.data_ptr(), int(table.shape[0]),
+                                                                    buf.data_ptr(), buf.numel(), _capi.current_stream_ptr()))
+                cache[which] = buf
+            self.__dict__["_proj"] = cache
+        return self._proj_flags(plan), cache.get("node"), cache.get("edge")
 
     # ---- reference API -------------------------------------------------------------------------
     def set_neighbor_sampler(self, neighbor_sampler: NeighborSampler):
@@ -233,12 +292,14 @@ class DyGFormer(nn.Module):
             taps_struct = _capi.DygformerTaps()
             taps_struct.ev_kernel_start, taps_struct.ev_kernel_stop = e0.cuda_event, e1.cuda_event
         csr = self.neighbor_sampler.csr.on_device(dev)
-        rc = self._lib.dygnn_dygformer_forward_tables(
+        proj_flags, proj_node, proj_edge = self._projected_tables(dev, weights)
+        rc = self._lib.dygnn_dygformer_forward_projected(
             C.byref(self._cfg), C.byref(weights), packed.data_ptr(), csr,
             self.node_raw_features.data_ptr(), self.edge_raw_features.data_ptr(),
             src.data_ptr(), dst.data_ptr(), tms.data_ptr(), B, int(_group_size), int(_pair_stride), out_src.data_ptr(), out_dst.data_ptr(),
             ws.data_ptr(), ws.numel(), C.byref(taps_struct) if taps_struct is not None else None,
-            int(self.impl), _capi.current_stream_ptr(), self.table_flags)
+            int(self.impl), _capi.current_stream_ptr(), self.table_flags | proj_flags,
+            proj_node.data_ptr() if proj_node is not None else None, proj_edge.data_ptr() if proj_edge is not None else None)
         _capi.check(rc)
         return out_src, out_dst
 
@@ -368,8 +429,10 @@ class DyGFormer(nn.Module):
     def invalidate_packed(self) -> None:
         """Drop the kernel-ready weight copy.  It is re-packed automatically when a parameter's version counter or address changes
         (optimizer steps, load_state_dict, .to()), on every train()/eval() switch and by this call; writes through `p.data` do not
-        bump the version counter, so code that edits weights that way (custom init, EMA) calls this afterwards."""
+        bump the version counter, so code that edits weights that way (custom init, EMA) calls this afterwards.  The projected feature
+        tables go with it."""
         self._packed_key = None
+        self.__dict__["_proj"] = None
 
     def train(self, mode: bool = True):
         self._packed_key = None
@@ -474,6 +537,7 @@ class DyGFormer(nn.Module):
                 self.__dict__["_packed_complete"] = True
             self.__dict__["_packed_ptrs"] = ptrs
             self._packed_key = key
+            self.__dict__["_pack_gen"] = self.__dict__.get("_pack_gen", 0) + 1      # the projected tables of the previous weights are stale
         return self._weights_cached, self._packed
 
     def _workspace_for(self, B: int, dev) -> torch.Tensor:

@@ -228,6 +228,37 @@ int dygnn_dygformer_forward_tables(const dygnn_dygformer_config* cfg_host, const
                                    void* workspace, size_t workspace_bytes,
                                    const dygnn_dygformer_taps* taps_host, int32_t impl, dygnn_stream_t stream, uint32_t table_flags);
 
+/* Projected feature tables.  The patch projection of the node and of the edge channel is linear in the table rows it gathers, and
+ * neither the table nor (in an evaluation pass) the weights change between calls: dygnn_dygformer_project_table computes
+ *     projected[row][p][0 .. 63] = proj_w[:, p F .. (p + 1) F) . table[row]        (p < patch_size; F = the channel's feature dim)
+ * once — each element one fmaf chain over the F features; the 64 floats are the four 16-row tiles of the model dimension that the
+ * channel touches, zero outside its 50 rows — and the fused inference kernel then adds patch_size gathered rows per token instead of
+ * running the product: x = ((bias + projected[row_0][0]) + projected[row_1][1]) + ...  The sum is split per slot, so the channel's rows
+ * differ from the unprojected call's in the last bits; they do not depend on kernel shape, batch size, group_size or pair_stride.
+ *   dygnn_dygformer_projected_bytes   size of one projected table of `rows` rows (host only; 0: bad config, rows <= 0, or a shape the
+ *                                     fused kernel does not support) = rows * patch_size * 64 * sizeof(float)
+ *   dygnn_dygformer_project_table     channel 0 = node features (proj_node_w), 1 = edge features (proj_edge_w); one launch on `stream`.
+ *                                     `projected` is device memory, 16-byte aligned.  Run it again whenever the weights or the table change.
+ *   dygnn_dygformer_forward_projected dygnn_dygformer_forward_tables plus
+ *       DYGNN_TABLE_NODE_PROJ  node_proj is the projected node table        DYGNN_TABLE_EDGE_PROJ  edge_proj is the projected edge table
+ *     A pointer whose bit is not set is ignored; a set bit with a NULL pointer is an error.  A channel flagged all zero ignores its
+ *     projected table.  The flags are the caller's promise, as above: a stale projected table gives wrong results.  The environment
+ *     variable DYGNN_PROJ_TABLES=0 (read on every call) makes the call ignore both, which is dygnn_dygformer_forward_tables; so do the
+ *     generic path and the training entry points.  Without projected bits the call IS dygnn_dygformer_forward_tables, bit for bit. */
+#define DYGNN_TABLE_NODE_PROJ 4u
+#define DYGNN_TABLE_EDGE_PROJ 8u
+size_t dygnn_dygformer_projected_bytes(const dygnn_dygformer_config* cfg_host, int64_t rows);
+int dygnn_dygformer_project_table(const dygnn_dygformer_config* cfg_host, const dygnn_dygformer_weights* w_host, int32_t channel,
+                                  const float* table, int64_t rows, void* projected, size_t projected_bytes, dygnn_stream_t stream);
+int dygnn_dygformer_forward_projected(const dygnn_dygformer_config* cfg_host, const dygnn_dygformer_weights* w_host,
+                                      const void* packed, const dygnn_csr* csr_host,
+                                      const float* node_feat, const float* edge_feat,
+                                      const int64_t* src, const int64_t* dst, const double* times, int64_t batch,
+                                      int64_t group_size, int64_t pair_stride, float* out_src, float* out_dst,
+                                      void* workspace, size_t workspace_bytes,
+                                      const dygnn_dygformer_taps* taps_host, int32_t impl, dygnn_stream_t stream, uint32_t table_flags,
+                                      const float* node_proj, const float* edge_proj);
+
 /* ------------------------------------------------------------------------------------------
  * TGAT.compute_src_dst_node_temporal_embeddings (models/TGAT.py:48-136), eval mode, `recent`
  * sampling: L temporal-attention layers (MultiHeadAttention models/modules.py:99-206, mask =
