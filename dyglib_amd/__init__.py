@@ -8,7 +8,7 @@ The compute lives in dyglib_amd/csrc (C ABI: include/dygnn.h).  There is no CPU 
 """
 from .synthetic import InteractionData  # noqa: F401
 
-__all__ = ["DyGFormer", "TGAT", "MemoryModel", "GraphMixer", "TCL", "MergeLayer", "TimeEncoder", "NeighborSampler", "get_neighbor_sampler", "TemporalCSR",
+__all__ = ["DyGFormer", "TGAT", "MemoryModel", "GraphMixer", "TCL", "CAWN", "MergeLayer", "TimeEncoder", "NeighborSampler", "get_neighbor_sampler", "TemporalCSR",
            "count_nodes_appearances", "InteractionData", "Data", "get_link_prediction_data",
            "get_link_prediction_metrics", "get_node_classification_metrics", "link_prediction_metrics_device",
            "NegativeEdgeSampler", "get_idx_data_loader", "evaluate_model_link_prediction"]
@@ -31,6 +31,9 @@ def __getattr__(name):
     if name == "TCL":
         from .tcl import TCL
         return TCL
+    if name == "CAWN":
+        from .cawn import CAWN
+        return CAWN
     if name in ("MergeLayer", "TimeEncoder"):
         from . import modules
         return getattr(modules, name)

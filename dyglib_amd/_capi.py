@@ -124,6 +124,29 @@ class TclTaps(C.Structure):
     _fields_ = [("rows", C.c_int64), ("encoder_input", C.c_void_p), ("layer_out", C.c_void_p * DYGNN_MAX_LAYERS)]
 
 
+class CawnConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("node_feat_dim", "edge_feat_dim", "time_feat_dim", "position_feat_dim", "walk_length", "num_neighbors",
+                                         "num_walk_heads", "num_node_rows", "num_edge_rows")]
+
+
+class CawnLstmWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh")]
+
+
+class CawnWeights(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("time_w", "time_b", "pos_w0", "pos_b0", "pos_w1", "pos_b1")]
+                + [("feature", CawnLstmWeights * 2), ("position", CawnLstmWeights * 2), ("attn", TclLayerWeights)]
+                + [(n, C.c_void_p) for n in ("proj0_w", "proj0_b", "proj1_w", "proj1_b")])
+
+
+class CawnHops(C.Structure):
+    _fields_ = [("id", C.c_void_p * 2), ("eid", C.c_void_p * 2), ("t", C.c_void_p * 2)]
+
+
+class CawnTaps(C.Structure):
+    _fields_ = [("rows", C.c_int64)] + [(n, C.c_void_p) for n in ("walk_ids", "counts", "feature_out", "position_out", "attn_in", "attn_out")]
+
+
 class DygformerTaps(C.Structure):
     _fields_ = [("seq_lens", C.c_void_p), ("encoder_input", C.c_void_p), ("layer_out", C.c_void_p * DYGNN_MAX_LAYERS),
                 ("phase_cycles", C.c_void_p), ("ev_kernel_start", C.c_void_p), ("ev_kernel_stop", C.c_void_p)]
@@ -225,6 +248,11 @@ SIGNATURES = {
                                           C.c_void_p]),
     "dygnn_tcl_backward": (C.c_int, [C.POINTER(TclConfig), C.POINTER(TclWeights), C.POINTER(TclWeights), C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
                                      C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dygnn_cawn_check": (C.c_int, [C.POINTER(CawnConfig)]),
+    "dygnn_cawn_workspace_bytes": (C.c_size_t, [C.POINTER(CawnConfig), C.c_int64, C.c_int64]),
+    "dygnn_cawn_forward": (C.c_int, [C.POINTER(CawnConfig), C.POINTER(CawnWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CawnHops),
+                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(CawnTaps), C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
     "dygnn_merge_layer_sigmoid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dygnn_merge_layer_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,

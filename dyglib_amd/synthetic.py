@@ -384,3 +384,74 @@ def make_tcl_params(seed: int, num_neighbors: int, num_layers: int = 2, node_fea
             val = rs.uniform(-1, 1, size=shape) / np.sqrt(fan_in)
         out[key] = np.ascontiguousarray(val, dtype=np.float32)
     return out
+
+
+def cawn_attention_dim(input_dim: int, num_walk_heads: int) -> int:
+    """models/CAWN.py:307-313: half the walk input dim, rounded up to a multiple of the heads."""
+    a = input_dim // 2
+    return a if a % num_walk_heads == 0 else a + num_walk_heads - a % num_walk_heads
+
+
+def cawn_param_shapes(position_feat_dim: int, walk_length: int, num_walk_heads: int = 8, node_feat_dim: int = NODE_FEAT_DIM,
+                      edge_feat_dim: int = NODE_FEAT_DIM, time_feat_dim: int = 100) -> Dict[str, Tuple[int, ...]]:
+    """state_dict of the reference CAWN (models/CAWN.py:41-46, :193-195, :316-328, :369), in its order: 38 tensors."""
+    P, D = position_feat_dim, node_feat_dim + edge_feat_dim + time_feat_dim + position_feat_dim
+    A = cawn_attention_dim(D, num_walk_heads)
+    shapes: Dict[str, Tuple[int, ...]] = {"time_encoder.w.weight": (time_feat_dim, 1), "time_encoder.w.bias": (time_feat_dim,),
+                                          "position_encoder.position_encode_layer.0.weight": (P, walk_length + 1),
+                                          "position_encoder.position_encode_layer.0.bias": (P,),
+                                          "position_encoder.position_encode_layer.2.weight": (P, P),
+                                          "position_encoder.position_encode_layer.2.bias": (P,)}
+    for enc, inp in (("feature_encoder", D), ("position_encoder", P)):
+        H = inp // 2
+        for suffix in ("", "_reverse"):
+            p = f"walk_encoder.{enc}.bilstm_encoder."
+            shapes[p + "weight_ih_l0" + suffix] = (4 * H, inp)
+            shapes[p + "weight_hh_l0" + suffix] = (4 * H, H)
+            shapes[p + "bias_ih_l0" + suffix] = (4 * H,)
+            shapes[p + "bias_hh_l0" + suffix] = (4 * H,)
+    p = "walk_encoder.transformer_encoder."
+    shapes[p + "multi_head_attention.in_proj_weight"] = (3 * A, A)
+    shapes[p + "multi_head_attention.in_proj_bias"] = (3 * A,)
+    shapes[p + "multi_head_attention.out_proj.weight"] = (A, A)
+    shapes[p + "multi_head_attention.out_proj.bias"] = (A,)
+    shapes[p + "linear_layers.0.weight"] = (4 * A, A)
+    shapes[p + "linear_layers.0.bias"] = (4 * A,)
+    shapes[p + "linear_layers.1.weight"] = (A, 4 * A)
+    shapes[p + "linear_layers.1.bias"] = (A,)
+    for i in (0, 1):
+        shapes[p + f"norm_layers.{i}.weight"] = (A,)
+        shapes[p + f"norm_layers.{i}.bias"] = (A,)
+    shapes["walk_encoder.projection_layers.0.weight"] = (A, 2 * (D // 2) + 2 * (P // 2))
+    shapes["walk_encoder.projection_layers.0.bias"] = (A,)
+    shapes["walk_encoder.projection_layers.1.weight"] = (node_feat_dim, A)
+    shapes["walk_encoder.projection_layers.1.bias"] = (node_feat_dim,)
+    return shapes
+
+
+def make_cawn_params(seed: int, position_feat_dim: int, walk_length: int, num_walk_heads: int = 8, node_feat_dim: int = NODE_FEAT_DIM,
+                     edge_feat_dim: int = NODE_FEAT_DIM, time_feat_dim: int = 100) -> Dict[str, np.ndarray]:
+    """Deterministic float32 parameters in the style of make_tcl_params: every bias non-zero, LayerNorm weights 1 +- 0.1, the position
+    MLP's first layer of order 1 (its inputs are landing probabilities in [0, 1]), LSTM tensors uniform in +- 1 / sqrt(hidden) as
+    nn.LSTM initialises them."""
+    rs = np.random.RandomState(seed)
+    out: Dict[str, np.ndarray] = {}
+    for key, shape in cawn_param_shapes(position_feat_dim, walk_length, num_walk_heads, node_feat_dim, edge_feat_dim, time_feat_dim).items():
+        if key == "time_encoder.w.weight":
+            base = (1.0 / 10 ** np.linspace(0, 9, time_feat_dim, dtype=np.float32)).reshape(shape)
+            val = base * (1.0 + 0.01 * rs.uniform(-1, 1, size=shape))
+        elif key == "time_encoder.w.bias":
+            val = 0.1 * rs.uniform(-1, 1, size=shape)
+        elif key.startswith("position_encoder.position_encode_layer.0"):
+            val = rs.uniform(-1, 1, size=shape)
+        elif "norm_layers" in key:
+            val = (1.0 if key.endswith("weight") else 0.0) + 0.1 * rs.uniform(-1, 1, size=shape)
+        elif "bilstm_encoder" in key:
+            val = rs.uniform(-1, 1, size=shape) / np.sqrt(shape[0] // 4)
+        elif key.endswith("in_proj_bias"):
+            val = rs.uniform(-1, 1, size=shape) / np.sqrt(shape[0] // 3)
+        else:
+            fan_in = shape[1] if len(shape) == 2 else out[key[:-4] + "weight"].shape[1]
+            val = rs.uniform(-1, 1, size=shape) / np.sqrt(fan_in)
+        out[key] = np.ascontiguousarray(val, dtype=np.float32)
+    return out

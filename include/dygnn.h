@@ -642,6 +642,73 @@ int dygnn_tcl_backward(const dygnn_tcl_config* cfg_host, const dygnn_tcl_weights
                        const float* grad_out_src /* [batch, d] */, const float* grad_out_dst /* [batch, d] */, int64_t batch, float dropout_p,
                        uint64_t seed, void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * CAWN.compute_src_dst_node_temporal_embeddings (models/CAWN.py:48-396), eval mode, fp32 (dyglib_amd/csrc/cawn.hip).
+ * The call works on SIDES and PAIRS, on PRE-SAMPLED hop arrays (any strategy: sampling is not part of the call).  A side is one target
+ * (v, t) with the arrays get_multi_hop_neighbors returns for it: hop h = 1..W holds k^h (node id, edge id, float32 time).  Walk j of the
+ * M = k^W walks of a side is [target, hop1[j / k^(W-1)], ..., hopW[j]]; position 0 carries edge id 0 and time t; the valid length is the
+ * number of non-zero ids (zeros are a suffix).  A pair names two sides a, b.  Per pair, every node id of the two trees gets the counts
+ * [2][W + 1] (row 0: appearances in a's tree, row 1: in b's, column = hop, each appearance 1 / k^hop; the entry of id 0 is zero) and the
+ * position feature sum_rows MLP(W + 1 -> P -> P, ReLU).  Input of a walk position: [node_feat[id] | cos(w float32(t - t_pos) + b) |
+ * edge_feat[eid] | position feature].  Two BiLSTMs (input D = F_n + F_e + F_t + P, hidden D / 2 per direction; input P, hidden P / 2) give
+ * their output at the last valid position; their concatenation goes through projection_layers[0] (-> attention_dim = D / 2 rounded up to a
+ * multiple of the heads), one TransformerEncoder block over the M walks of a side (no mask), the mean over the walks and
+ * projection_layers[1] (-> F_n).  A pair's rows do not depend on the other pairs of the call; a side named by several pairs is encoded
+ * once per pair (its position features depend on the partner).
+ * Configurations: walk_length 1 or 2; k^W <= 128; F_n, F_e, F_t multiples of 4, P even, each <= 256; attention_dim a multiple of 4, <= 512, and
+ * attention_dim / heads <= 64.  Others: DYGNN_E_UNSUPPORTED, the message names the value.  num_neighbors or walk_length <= 0: DYGNN_E_INVALID.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct dygnn_cawn_config {
+    int32_t node_feat_dim, edge_feat_dim, time_feat_dim, position_feat_dim;   /* F_n, F_e, F_t, P                                */
+    int32_t walk_length, num_neighbors, num_walk_heads;                       /* W, k, heads                                     */
+    int32_t num_node_rows, num_edge_rows;                  /* rows of node_feat / edge_feat: ids outside read row 0             */
+} dygnn_cawn_config;
+
+typedef struct dygnn_cawn_lstm_weights {                   /* one direction of an nn.LSTM with hidden size H, gates i, f, g, o  */
+    const float *w_ih, *w_hh;                              /* weight_ih_l0 [4H,in], weight_hh_l0 [4H,H]                         */
+    const float *b_ih, *b_hh;                              /* bias_ih_l0 [4H], bias_hh_l0 [4H]                                  */
+} dygnn_cawn_lstm_weights;
+
+typedef struct dygnn_cawn_weights {                        /* the order of the reference's state_dict                           */
+    const float *time_w, *time_b;                          /* time_encoder.w.{weight,bias}                      [F_t,1],[F_t]   */
+    const float *pos_w0, *pos_b0;                          /* position_encoder.position_encode_layer.0          [P,W+1],[P]     */
+    const float *pos_w1, *pos_b1;                          /* position_encoder.position_encode_layer.2          [P,P],[P]       */
+    dygnn_cawn_lstm_weights feature[2];                    /* walk_encoder.feature_encoder.bilstm_encoder: forward, reverse     */
+    dygnn_cawn_lstm_weights position[2];                   /* walk_encoder.position_encoder.bilstm_encoder: forward, reverse    */
+    dygnn_tcl_layer_weights attn;                          /* walk_encoder.transformer_encoder.*, d = attention_dim             */
+    const float *proj0_w, *proj0_b;                        /* walk_encoder.projection_layers.0    [attention_dim, D + P]        */
+    const float *proj1_w, *proj1_b;                        /* walk_encoder.projection_layers.1    [F_n, attention_dim]          */
+} dygnn_cawn_weights;
+
+typedef struct dygnn_cawn_hops {                           /* device arrays [n_sides, k^h], index h - 1; hop 2 NULL when W = 1   */
+    const int64_t* id[2];
+    const int64_t* eid[2];
+    const float* t[2];
+} dygnn_cawn_hops;
+
+/* Optional intermediates of the first min(rows, n_pairs) pairs (device buffers, each nullable); index 1 of the second axis is side a / b. */
+typedef struct dygnn_cawn_taps {
+    int64_t rows;
+    int64_t* walk_ids;                                     /* [rows, 2, M, W+1]                                                 */
+    float* counts;                                         /* [rows, 2, M, W+1, 2, W+1] the counts of every walk position       */
+    float* feature_out;                                    /* [rows, 2, M, D]   feature encoder output (D even)                 */
+    float* position_out;                                   /* [rows, 2, M, P]   position encoder output                         */
+    float* attn_in;                                        /* [rows, 2, M, attention_dim] projection_layers[0] output           */
+    float* attn_out;                                       /* [rows, 2, M, attention_dim] transformer output                    */
+} dygnn_cawn_taps;
+
+/* DYGNN_OK, or why dygnn_cawn_workspace_bytes returned 0 (message in dygnn_last_error) */
+int dygnn_cawn_check(const dygnn_cawn_config* cfg_host);
+/* Per pair: the position tables; per sequence (2 n_pairs): the LSTM states, the encoder outputs of the M walks, the transformer's
+ * activations.  0 = the configuration is refused. */
+size_t dygnn_cawn_workspace_bytes(const dygnn_cawn_config* cfg_host, int64_t n_sides, int64_t n_pairs);
+/* side_* and the hop arrays are device arrays; pair_a / pair_b are HOST arrays (checked against [0, n_sides) before any launch and copied). */
+int dygnn_cawn_forward(const dygnn_cawn_config* cfg_host, const dygnn_cawn_weights* w_host, const float* node_feat, const float* edge_feat,
+                       const int64_t* side_root /* [n_sides] */, const double* side_time /* [n_sides] */, const dygnn_cawn_hops* hops_host,
+                       int64_t n_sides, const int32_t* pair_a_host /* [n_pairs] */, const int32_t* pair_b_host /* [n_pairs] */, int64_t n_pairs,
+                       float* out_a /* [n_pairs, F_n] */, float* out_b /* [n_pairs, F_n] */, const dygnn_cawn_taps* taps_host /* or NULL */,
+                       void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
+
 /* Evaluation metrics on the device, replacing the scikit-learn host round trip of
  * get_link_prediction_metrics / get_node_classification_metrics (utils/metrics.py:5-34; called per batch at
  * evaluate_models_utils.py:139-150 and per evaluation at :245-249).  predicts / labels: [n_groups, group_size] float32
