@@ -253,6 +253,12 @@ SIGNATURES = {
     "dygnn_cawn_forward": (C.c_int, [C.POINTER(CawnConfig), C.POINTER(CawnWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CawnHops),
                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(CawnTaps), C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
+    "dygnn_cawn_train_workspace_bytes": (C.c_size_t, [C.POINTER(CawnConfig), C.c_int64]),
+    "dygnn_cawn_train_forward": (C.c_int, [C.POINTER(CawnConfig), C.POINTER(CawnWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(CawnHops), C.c_int64, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p]),
+    "dygnn_cawn_backward": (C.c_int, [C.POINTER(CawnConfig), C.POINTER(CawnWeights), C.POINTER(CawnWeights), C.c_void_p, C.c_void_p, C.c_int64,
+                                      C.c_float, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dygnn_merge_layer_sigmoid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dygnn_merge_layer_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,

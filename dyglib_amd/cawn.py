@@ -3,10 +3,14 @@
 signatures, same parameter names and shapes (a reference checkpoint loads with strict=True); the forward runs in libdygnn_hip.so
 (`dygnn_cawn_forward`, dyglib_amd/csrc/cawn.hip).
 
-Inference only: eval mode, or train mode under torch.no_grad() (the same forward: dropout belongs to the training path, which is not built);
-a call with autograd recording raises NotImplementedError.  All three neighbour sampling strategies work: the hops are sampled by
-`NeighborSampler.get_historical_neighbors_device` in the reference's call order (all hops of the sources, then all hops of the destinations,
-hop h >= 2 queried at the float32 times of hop h - 1) and handed to the library.
+Inference (eval mode, or train mode under torch.no_grad()) takes `dygnn_cawn_forward`.  Training is OPT-IN: after `enable_training()`, a call
+in train mode with autograd recording takes `dygnn_cawn_train_forward` / `dygnn_cawn_backward` (dyglib_amd/csrc/cawn_train.hip) through
+`_CawnTrainFunction`: dropout `self.dropout` from the counter-based generator of dropout.h, every parameter receives a gradient (the reverse
+directions' weight_hh an exactly zero one), the feature tables do not.  Without `enable_training()` a call with autograd recording raises
+NotImplementedError, as do, with or without it, eval mode, `compute_step_embeddings` and `taps=` with autograd recording.  All three
+neighbour sampling strategies work on both paths: the hops are sampled by `NeighborSampler.get_historical_neighbors_device` in the
+reference's call order (all hops of the sources, then all hops of the destinations, hop h >= 2 queried at the float32 times of hop h - 1)
+and handed to the library.
 
 In CAWN the source embedding depends on the destination it is paired with (the position features count appearances in both trees), so an
 evaluation step has FOUR results: `compute_step_embeddings` returns (src of the positive call, dst, src of the negative call, neg_dst)."""
@@ -24,6 +28,63 @@ from .modules import TimeEncoder
 from .neighbor_sampler import NeighborSampler
 from .tcl import TransformerEncoder
 from .tgat import _to_dev, _workspace
+
+
+class _CawnTrainFunction(torch.autograd.Function):
+    """compute_src_dst_node_temporal_embeddings with gradients: forward = dygnn_cawn_train_forward, backward = dygnn_cawn_backward.  The
+    parameters are passed as inputs only so that autograd routes their gradients; the workspace belongs to this one call (a training step
+    issues a negative and a positive call before one backward())."""
+
+    @staticmethod
+    def forward(ctx, model, sides, B, num_neighbors, dropout_p, seed, *params):
+        dev = model.walk_encoder.projection_layers[1].weight.device
+        d = model.node_feat_dim
+        out = (torch.empty((B, d), dtype=torch.float32, device=dev), torch.empty((B, d), dtype=torch.float32, device=dev))
+        ctx.model, ctx.B = model, B
+        if B == 0:                                                           # nothing to launch, here or in backward
+            return out
+        lib = model._lib
+        cfg, w = model._config(num_neighbors), model._weights()
+        nbytes = lib.dygnn_cawn_train_workspace_bytes(C.byref(cfg), B)
+        if nbytes == 0:                                  # AssertionError (bad argument) or NotImplementedError (unsupported) with the library's message
+            msg = lib.dygnn_last_error().decode("utf-8", "replace")
+            _capi.check(lib.dygnn_cawn_check(C.byref(cfg)))
+            raise NotImplementedError(msg) if "not supported" in msg else AssertionError(msg)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)          # lives until this call's backward
+        roots, tms, hops = sides
+        h = _capi.CawnHops()
+        for i, (n, e, t) in enumerate(hops):
+            h.id[i], h.eid[i], h.t[i] = n.data_ptr(), e.data_ptr(), t.data_ptr()
+        _capi.check(lib.dygnn_cawn_train_forward(C.byref(cfg), C.byref(w), model.node_raw_features.data_ptr(), model.edge_raw_features.data_ptr(),
+                                                 roots.data_ptr(), tms.data_ptr(), C.byref(h), B, float(dropout_p), int(seed), out[0].data_ptr(),
+                                                 out[1].data_ptr(), ws.data_ptr(), nbytes, _capi.current_stream_ptr()))
+        ctx.cfg, ctx.w, ctx.ws, ctx.dropout_p, ctx.seed = cfg, w, ws, float(dropout_p), int(seed)
+        ctx.param_versions = [(p.data_ptr(), p._version) for p in params]
+        return out
+
+    @staticmethod
+    def backward(ctx, g_src, g_dst):
+        model = ctx.model
+        params = list(model.parameters())
+        if ctx.B == 0:
+            return (None,) * (6 + len(params))
+        dev = ctx.ws.device
+        g_src = (g_src if g_src is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
+        g_dst = (g_dst if g_dst is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
+        # the backward pass re-reads the CURRENT parameter values: they must be the ones the forward used
+        if [(p.data_ptr(), p._version) for p in params] != ctx.param_versions:
+            raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
+                               "a CAWN parameter changed between this call's forward and its backward")
+        sizes = [p.numel() for p in params]
+        # one fill for all gradient buffers; every buffer starts at a multiple of 4 floats (the library's products read float4)
+        starts = np.cumsum([0] + [(n + 3) // 4 * 4 for n in sizes])
+        flat = torch.zeros(int(starts[-1]), dtype=torch.float32, device=dev)
+        grads = [flat[int(a):int(a) + n].view_as(p) for a, n, p in zip(starts, sizes, params)]
+        gstruct = model._weights({id(p): g for p, g in zip(params, grads)})
+        _capi.check(model._lib.dygnn_cawn_backward(C.byref(ctx.cfg), C.byref(ctx.w), C.byref(gstruct), g_src.data_ptr(), g_dst.data_ptr(), ctx.B,
+                                                   ctx.dropout_p, ctx.seed, ctx.ws.data_ptr(), ctx.ws.numel(), _capi.current_stream_ptr()))
+        ctx.ws = None
+        return (None,) * 6 + tuple(grads)
 
 
 class PositionEncoder(nn.Module):
@@ -92,6 +153,13 @@ class CAWN(nn.Module):
                                         dropout=dropout)
         self._lib = _capi.load()
         self._workspace: Dict[tuple, torch.Tensor] = {}
+        self._training_enabled = False
+
+    def enable_training(self, enabled: bool = True) -> "CAWN":
+        """Opt in to (or out of) the differentiable path: with it on, compute_src_dst_node_temporal_embeddings in train mode with autograd
+        recording runs dygnn_cawn_train_forward and records dygnn_cawn_backward.  Off by default; returns self."""
+        self._training_enabled = bool(enabled)
+        return self
 
     def set_neighbor_sampler(self, neighbor_sampler: NeighborSampler):
         """models/CAWN.py:166-175."""
@@ -106,10 +174,19 @@ class CAWN(nn.Module):
         """models/CAWN.py:48-80: two float32 tensors [B, node_feat_dim]; ONE library call on the sides [src ; dst] and the pairs (i, B + i).
         `taps` = r (not in the reference): also return the intermediates of the first r pairs, (src, dst, dict(walk_ids [r, 2, M, W + 1],
         counts [r, 2, M, W + 1, 2, W + 1], feature_out [r, 2, M, D], position_out [r, 2, M, P], attn_in / attn_out [r, 2, M, attention_dim]));
-        index 0 / 1 of the second axis is the source / destination side."""
-        (src, dst), tms = self._inputs((src_node_ids, dst_node_ids), node_interact_times, num_neighbors)
+        index 0 / 1 of the second axis is the source / destination side.
+        After enable_training(), in train mode with autograd recording, the call is differentiable (dropout self.dropout; `taps` are refused)."""
+        train = self._training_enabled and self.training and torch.is_grad_enabled()
+        if train and taps is not None:
+            raise NotImplementedError("cawn: taps are an inference facility; the training path does not return intermediates")
+        (src, dst), tms = self._inputs((src_node_ids, dst_node_ids), node_interact_times, num_neighbors, trainable=True)
         B = src.numel()
         sides = self._sample([src, dst], tms, num_neighbors)
+        if train:
+            seed = getattr(self, "_fixed_dropout_seed", None)             # tests pin the masks; normally torch.manual_seed governs them
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            return _CawnTrainFunction.apply(self, sides, B, int(num_neighbors), float(self.dropout), seed, *self.parameters())
         idx = np.arange(B, dtype=np.int32)
         return self._forward(sides, idx, idx + B, num_neighbors, taps)
 
@@ -132,13 +209,16 @@ class CAWN(nn.Module):
         return oa[:B], ob[:B], oa[B:], ob[B:]
 
     # ---- glue ------------------------------------------------------------------------------------------------------------------------
-    def _inputs(self, id_arrays, node_interact_times, num_neighbors):
-        """Refuse what is not built (autograd recording, a CPU model), validate host ids like the reference (IndexError; a target id of 0 is
-        an AssertionError: the reference fails on it in pack_padded_sequence, its walks having length 0), and move ids (int64) and times
-        (float64) to the model's device."""
-        if torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("dyglib_amd.CAWN is inference-only on the HIP path: call it under torch.no_grad() (the training path, "
-                                      "backward pass and dropout, is not built)")
+    def _inputs(self, id_arrays, node_interact_times, num_neighbors, trainable: bool = False):
+        """Refuse what is not built or not enabled (autograd recording outside the opted-in training call, a CPU model), validate host ids
+        like the reference (IndexError; a target id of 0 is an AssertionError: the reference fails on it in pack_padded_sequence, its walks
+        having length 0), and move ids (int64) and times (float64) to the model's device.  `trainable`: the caller has a differentiable path
+        for train mode."""
+        if (torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters()))
+                and not (trainable and self.training and self._training_enabled)):
+            raise NotImplementedError("this dyglib_amd.CAWN call is inference-only on the HIP path: call it under torch.no_grad().  Gradients flow "
+                                      "through compute_src_dst_node_temporal_embeddings in train mode after enable_training() only (eval mode, "
+                                      "compute_step_embeddings and taps have no backward pass)")
         self.neighbor_sampler._check_strategy()
         assert num_neighbors > 0, "Number of sampled neighbors for each node should be greater than 0!"          # utils/utils.py:157
         assert self.walk_length > 0, "Number of sampled hops should be greater than 0!"                          # utils/utils.py:228
@@ -186,12 +266,14 @@ class CAWN(nn.Module):
         return _capi.CawnConfig(self.node_feat_dim, self.edge_feat_dim, self.time_feat_dim, self.position_feat_dim, self.walk_length, int(num_neighbors),
                                 self.num_walk_heads, self.node_raw_features.shape[0], self.edge_raw_features.shape[0])
 
-    def _weights(self) -> "_capi.CawnWeights":
+    def _weights(self, replace: Optional[dict] = None) -> "_capi.CawnWeights":
+        """ctypes view of the parameters; `replace` maps id(parameter) to another tensor of the same shape (the gradient buffers of the
+        backward pass)."""
         for p in self.parameters():
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise _capi.DygnnError("parameters must be contiguous float32")
         w = _capi.CawnWeights()
-        p = lambda t: t.data_ptr()
+        p = (lambda t: t.data_ptr()) if replace is None else (lambda t: replace[id(t)].data_ptr())
         w.time_w, w.time_b = p(self.time_encoder.w.weight), p(self.time_encoder.w.bias)
         mlp = self.position_encoder.position_encode_layer
         w.pos_w0, w.pos_b0, w.pos_w1, w.pos_b1 = p(mlp[0].weight), p(mlp[0].bias), p(mlp[2].weight), p(mlp[2].bias)

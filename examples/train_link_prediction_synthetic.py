@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """End-to-end miniature of the reference's train_link_prediction.py on the HIP path, with synthetic dataset files in the
 reference's on-disk format: load (`get_link_prediction_data`), build the two samplers (train graph / full graph,
-train_link_prediction.py:40-45), train DyGFormer (or TGAT / TGN / TCL / GraphMixer, --model) + MergeLayer with Adam on BCE (:229-257), evaluate AP / AUC on the
+train_link_prediction.py:40-45), train DyGFormer (or TGAT / TGN / TCL / GraphMixer / CAWN, --model) + MergeLayer with Adam on BCE (:229-257), evaluate AP / AUC on the
 validation split with the fused inference kernel (evaluate_models_utils.py:49-152).  One process per GPU under
 torch.distributed.run averages gradients with one flat RCCL all-reduce per step.  TGN (:186-207, :242-292) carries a memory bank through
 the batches in chronological order: it is re-initialised at the start of every epoch, the negative call precedes the positive call,
@@ -21,7 +21,7 @@ import torch
 import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dyglib_amd import TCL, TGAT, DyGFormer, GraphMixer, MemoryModel, MergeLayer, get_link_prediction_data, get_neighbor_sampler, synthetic as syn  # noqa: E402
+from dyglib_amd import CAWN, TCL, TGAT, DyGFormer, GraphMixer, MemoryModel, MergeLayer, get_link_prediction_data, get_neighbor_sampler, synthetic as syn  # noqa: E402
 from dyglib_amd import distributed as D  # noqa: E402
 
 
@@ -45,9 +45,10 @@ def main():
     ap.add_argument("--items", type=int, default=60)
     ap.add_argument("--edges", type=int, default=20000)
     ap.add_argument("--lr", type=float, default=1e-4)
-    ap.add_argument("--model", choices=("DyGFormer", "TGAT", "TGN", "TCL", "GraphMixer"), default="DyGFormer")
+    ap.add_argument("--model", choices=("DyGFormer", "TGAT", "TGN", "TCL", "GraphMixer", "CAWN"), default="DyGFormer")
     ap.add_argument("--num-neighbors", type=int, default=20,
-                    help="TGAT / TGN: neighbours sampled per node and layer; TCL: per node (num_depths - 1); GraphMixer: per node (num_tokens)")
+                    help="TGAT / TGN: neighbours sampled per node and layer; TCL: per node (num_depths - 1); GraphMixer: per node (num_tokens); "
+                         "CAWN: per node and hop of a walk (one hop: num_neighbors walks per node, at most 64)")
     ap.add_argument("--time-gap", type=int, default=2000, help="GraphMixer: most recent neighbours the node encoder averages")
     args = ap.parse_args()
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -77,6 +78,9 @@ def main():
     elif args.model == "GraphMixer":
         model = GraphMixer(node_feat, edge_feat, train_sampler, time_feat_dim=100, num_tokens=args.num_neighbors, num_layers=2, dropout=0.1,
                            device=dev).to(dev)
+    elif args.model == "CAWN":                                # the reference's defaults but one hop; training is opt-in on this class
+        model = CAWN(node_feat, edge_feat, train_sampler, time_feat_dim=100, position_feat_dim=172, walk_length=1, num_walk_heads=8, dropout=0.1,
+                     device=dev).to(dev).enable_training()
     else:
         model = DyGFormer(node_feat, edge_feat, train_sampler, time_feat_dim=100, channel_embedding_dim=50, patch_size=1, num_layers=2,
                           num_heads=2, dropout=0.1, max_input_sequence_length=32, device=dev).to(dev)
@@ -98,7 +102,7 @@ def main():
             ps, pd = model.compute_src_dst_node_temporal_embeddings(src, dst, t, num_neighbors=args.num_neighbors)
             ns, nd = model.compute_src_dst_node_temporal_embeddings(src, neg, t, num_neighbors=args.num_neighbors)
             return ps, pd, ns, nd
-        if args.model == "TCL":                               # the source embedding depends on its partner: four results in evaluation too
+        if args.model in ("TCL", "CAWN"):                     # the source embedding depends on its partner: four results in evaluation too
             if not torch.is_grad_enabled():
                 return model.compute_step_embeddings(src, dst, neg, t, num_neighbors=args.num_neighbors)
             ps, pd = model.compute_src_dst_node_temporal_embeddings(src, dst, t, num_neighbors=args.num_neighbors)

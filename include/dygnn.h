@@ -709,6 +709,30 @@ int dygnn_cawn_forward(const dygnn_cawn_config* cfg_host, const dygnn_cawn_weigh
                        float* out_a /* [n_pairs, F_n] */, float* out_b /* [n_pairs, F_n] */, const dygnn_cawn_taps* taps_host /* or NULL */,
                        void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
 
+/* CAWN training (dyglib_amd/csrc/cawn_train.hip): the train-mode forward of one compute_src_dst_node_temporal_embeddings call and its
+ * backward pass.  The call's 2 batch sides are [src ; dst] (side_root, side_time and the hop arrays [2 batch, k^h]) and pair p is
+ * (side p, side batch + p): no index vector, no stream synchronisation.  Dropout (p in [0, 1)) on the attention probabilities, the
+ * attention block's output, relu(fc0) and the fc1 output of the walk encoder's transformer block, masks from the counter-based generator of
+ * dropout.h: sites 0 .. 3, sequence index q = 2 p + side, element ((q H + h) M + i) M + j (site 0), (q M + i) A + c (sites 1, 3),
+ * (q M + i) 4A + c (site 2), A = attention_dim.  dropout_p = 0 is the inference forward within fp32 rounding.  The workspace belongs to
+ * ONE forward / backward pair: it keeps the gathered input rows and every activation the backward pass reads (the feature tables and the
+ * hop arrays are not read again).  Configurations: those of dygnn_cawn_check with at most 64 walks (k^W <= 64; more: DYGNN_E_UNSUPPORTED,
+ * the message names the value).  workspace_bytes: 0 = the configuration or the batch is refused (message in dygnn_last_error).
+ * batch == 0: DYGNN_OK, nothing launched. */
+size_t dygnn_cawn_train_workspace_bytes(const dygnn_cawn_config* cfg_host, int64_t batch);
+int dygnn_cawn_train_forward(const dygnn_cawn_config* cfg_host, const dygnn_cawn_weights* w_host, const float* node_feat, const float* edge_feat,
+                             const int64_t* side_root /* [2 batch] */, const double* side_time /* [2 batch] */,
+                             const dygnn_cawn_hops* hops_host /* [2 batch, k^h] */, int64_t batch, float dropout_p, uint64_t seed,
+                             float* out_src /* [batch, F_n] */, float* out_dst /* [batch, F_n] */, void* workspace, size_t workspace_bytes,
+                             dygnn_stream_t stream);
+/* grads: a dygnn_cawn_weights of gradient buffers (same shapes as the weights), ZEROED by the caller: every tensor is accumulated into
+ * (feature[1].w_hh and position[1].w_hh, the reverse direction's hidden weights, are left at zero: that is their gradient).  Weight
+ * matrices are summed with float atomics (not bit-reproducible run to run); biases (b_ih and b_hh get the same sum), LayerNorm,
+ * time-encoder gradients and the position-feature scatter are fixed-order sums. */
+int dygnn_cawn_backward(const dygnn_cawn_config* cfg_host, const dygnn_cawn_weights* w_host, const dygnn_cawn_weights* grads_host,
+                        const float* grad_out_src /* [batch, F_n] */, const float* grad_out_dst /* [batch, F_n] */, int64_t batch, float dropout_p,
+                        uint64_t seed, void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
+
 /* Evaluation metrics on the device, replacing the scikit-learn host round trip of
  * get_link_prediction_metrics / get_node_classification_metrics (utils/metrics.py:5-34; called per batch at
  * evaluate_models_utils.py:139-150 and per evaluation at :245-249).  predicts / labels: [n_groups, group_size] float32
