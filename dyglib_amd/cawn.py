@@ -24,9 +24,8 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-from .modules import TimeEncoder
+from .modules import TimeEncoder, TransformerEncoder, fill_encoder_layer_weights
 from .neighbor_sampler import NeighborSampler
-from .tcl import TransformerEncoder
 from .tgat import _to_dev, _workspace
 
 
@@ -282,10 +281,7 @@ class CAWN(nn.Module):
             for d, suffix in enumerate(("", "_reverse")):
                 g = lambda name: p(getattr(enc.bilstm_encoder, name + suffix))
                 dst[d].w_ih, dst[d].w_hh, dst[d].b_ih, dst[d].b_hh = g("weight_ih_l0"), g("weight_hh_l0"), g("bias_ih_l0"), g("bias_hh_l0")
-        t, L, a = we.transformer_encoder, w.attn, we.transformer_encoder.multi_head_attention
-        L.in_proj_w, L.in_proj_b, L.out_proj_w, L.out_proj_b = p(a.in_proj_weight), p(a.in_proj_bias), p(a.out_proj.weight), p(a.out_proj.bias)
-        L.fc0_w, L.fc0_b, L.fc1_w, L.fc1_b = p(t.linear_layers[0].weight), p(t.linear_layers[0].bias), p(t.linear_layers[1].weight), p(t.linear_layers[1].bias)
-        L.norm0_w, L.norm0_b, L.norm1_w, L.norm1_b = p(t.norm_layers[0].weight), p(t.norm_layers[0].bias), p(t.norm_layers[1].weight), p(t.norm_layers[1].bias)
+        fill_encoder_layer_weights(w.attn, we.transformer_encoder, p)
         pl = we.projection_layers
         w.proj0_w, w.proj0_b, w.proj1_w, w.proj1_b = p(pl[0].weight), p(pl[0].bias), p(pl[1].weight), p(pl[1].bias)
         return w

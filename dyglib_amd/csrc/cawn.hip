@@ -14,13 +14,15 @@
 //                 last valid position (that is the reverse LSTM's output there).  The last forward step and the reverse cell write the
 //                 encoder output [rows][2 H] directly.
 //   k_cawn_proj   64 walk rows per workgroup: [feature encoder out | position encoder out] x projection_layers[0]     -> X, and in_proj -> Q, K, V
-//   k_cawn_attn / k_cawn_post   the rest of the TransformerEncoder over the M walks of a sequence, no mask: attention with M <= 128 keys and one
-//                 head of Q, K, V in LDS at stride 65; k_tcl_post (tcl.hip) with the width taken past 256 columns (NT column tiles per wave)  -> Y
+//   k_cawn_attn / k_encoder_post<NT, MT> (encoder_block.h, shared with tcl.hip)   the rest of the TransformerEncoder over the M walks of a
+//                 sequence, no mask: attention with M <= 128 keys and one head of Q, K, V in LDS at stride 65; the block tail with the width
+//                 taken past 256 columns (<4, 4>, <5, 2>, <8, 2>: NT column tiles per wave, 16 MT rows per workgroup), identity residual map -> Y
 //   k_cawn_out    4 sequences per workgroup: mean over the walks, projection_layers[1]                                  -> out_a, out_b
 // The K axis of every product that gathers its rows goes through LDS 128 columns at a time, so four workgroups share a CU.
 #include <vector>
 
 #include "common.h"
+#include "encoder_block.h"
 #include "mfma_tile.h"
 #include "tgat_attn.h"
 
@@ -28,9 +30,11 @@ namespace dygnn {
 namespace cawn {
 
 using attn::cos_time_t;
+using encoder::k_encoder_post;
 using tile::f4;
 using tile::kThreads;
 using tile::kWaves;
+using tile::lds_limit;
 using tile::mfma4;
 using tile::round16;
 using tile::wave_product;
@@ -41,11 +45,9 @@ constexpr int kMaxWalks = 128;      // M = k^W: two keys per lane in k_cawn_attn
 constexpr int kMaxTree = 136;       // T <= 1 + 128 (W = 1) or 1 + 11 + 121 (W = 2)
 constexpr int kSlots = 1024;        // hash slots of a pair: <= 2 T = 272 keys
 constexpr int kRows = 64;
-constexpr int kFfnChunk = 64;
 constexpr int kMaxHead = 64;        // attention_dim / heads: one output column per lane
 constexpr int kKChunk = 128;        // input columns of k_cawn_lstm / k_cawn_proj in LDS at a time: 33 KiB tiles, four workgroups per CU
 constexpr int kOutSeqs = 4;         // sequences per workgroup of k_cawn_out (rows 4 .. 15 of its MFMA tile are zero)
-constexpr float kLnEps = 1e-5f;
 constexpr unsigned long long kEmpty = ~0ull;
 
 struct Tree {                       // the hop arrays of all sides, as the sampler returns them (hop 2 NULL when W = 1)
@@ -466,17 +468,6 @@ __global__ __launch_bounds__(kThreads) void k_cawn_proj(const float* __restrict_
     }
 }
 
-// the rows r0 .. r0 + rows - 1 of X [R][d] into the LDS tile A [rows][lda], zero beyond d and beyond R
-__device__ __forceinline__ void load_rows(float* A, int lda, int rows, const float* __restrict__ X, int64_t r0, int64_t R, int d) {
-    const int d4 = d >> 2, lda4 = lda >> 2;
-    for (int i = threadIdx.x; i < rows * lda4; i += kThreads) {
-        const int r = i / lda4, c4 = i - r * lda4;
-        f4 v = z4();
-        if (c4 < d4 && r0 + r < R) v = *reinterpret_cast<const f4*>(X + (size_t)(r0 + r) * d + 4 * c4);
-        *reinterpret_cast<f4*>(A + r * lda + 4 * c4) = v;
-    }
-}
-
 // ---- self-attention over the M walks of one sequence, no mask (models/CAWN.py:352) ----------------------------------------------------------------------
 // Head by head: Q, K, V of the head in LDS at stride 65; wave w owns the query rows w, w + 4, ...; lane l scores the keys l and l + 64, the
 // wave does the softmax, then lane l sums head column l over the keys (the probabilities broadcast lane by lane).  LDS: 3 [M][65].
@@ -531,107 +522,6 @@ __global__ __launch_bounds__(kThreads) void k_cawn_attn(const float* __restrict_
             for (int j = 64; j < M; ++j) o = fmaf(__shfl(p1, j - 64), Vs[j * LD + col], o);
             if (lane < dh) O[base + (size_t)r * d + h * dh + lane] = o;
         }
-    }
-}
-
-// LayerNorm of the rows of the LDS tile A in place, one wave per row
-__device__ __forceinline__ void norm_rows(float* A, int lda, int rows, int d, const float* __restrict__ ln_w, const float* __restrict__ ln_b, int wave, int lane) {
-    for (int r = wave; r < rows; r += kWaves) {
-        float* row = A + r * lda;
-        float s = 0.f;
-        for (int f = lane; f < d; f += 64) s += row[f];
-        const float mean = wave_sum(s) / (float)d;
-        float v = 0.f;
-        for (int f = lane; f < d; f += 64) { const float x = row[f] - mean; v = fmaf(x, x, v); }
-        const float rstd = 1.0f / sqrtf(wave_sum(v) / (float)d + kLnEps);
-        for (int f = lane; f < d; f += 64) row[f] = fmaf((row[f] - mean) * rstd, ln_w[f], ln_b[f]);
-    }
-}
-
-// ---- the rest of the block (models/modules.py:257-264): out_proj + residual -> LayerNorm 0 -> d -> 4 d (ReLU) -> d, residual -> LayerNorm 1 ---------
-// As k_tcl_post (tcl.hip) with NT column tiles per wave and 16 MT rows per workgroup (MT = 2 past 256 columns: 50 KiB of LDS instead of
-// 100, three workgroups per CU instead of one).  LDS: A [16 MT][round16(d) + 4], Hc [16 MT][68]
-template <int NT, int MT>
-__global__ __launch_bounds__(kThreads) void k_cawn_post(const float* __restrict__ O, int64_t R, const float* __restrict__ Xres, dygnn_tcl_layer_weights w,
-                                                          int d, float* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lda = round16(d) + 4, ldh = kFfnChunk + 4, Hdim = 4 * d;
-    float* A = smem;
-    constexpr int rows = 16 * MT;
-    float* Hc = smem + rows * lda;
-    const int64_t r0 = (int64_t)blockIdx.x * rows;
-    const int c = lane & 15, g4 = 4 * (lane >> 4);
-    load_rows(A, lda, rows, O, r0, R, d);
-    __syncthreads();
-    f4 acc[NT][MT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[t][mt] = z4();
-    wave_product<NT, MT>(A, lda, w.out_proj_w, d, 0, d, d, wave, lane, acc);
-    __syncthreads();                                                 // every wave has read the attention rows
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        const int64_t r = r0 + 16 * mt + c;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int n = 16 * (wave + kWaves * t) + g4;
-            if (n >= d) continue;
-            f4 v = z4();
-            if (r < R) v = (acc[t][mt] + *reinterpret_cast<const f4*>(w.out_proj_b + n)) + *reinterpret_cast<const f4*>(Xres + (size_t)r * d + n);
-            *reinterpret_cast<f4*>(A + (16 * mt + c) * lda + n) = v;
-        }
-    }
-    __syncthreads();
-    norm_rows(A, lda, rows, d, w.norm0_w, w.norm0_b, wave, lane);
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[t][mt] = z4();
-    for (int h0 = 0; h0 < Hdim; h0 += kFfnChunk) {
-        const int hn = Hdim - h0 < kFfnChunk ? Hdim - h0 : kFfnChunk;      // live hidden columns of this chunk (a multiple of 16)
-        f4 hid[1][MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) hid[0][mt] = z4();
-        wave_product<1, MT>(A, lda, w.fc0_w + (size_t)h0 * d, d, 0, hn, d, wave, lane, hid);
-        {
-            const int hcol = 16 * wave + g4;
-            f4 b = z4();
-            if (hcol < hn) b = *reinterpret_cast<const f4*>(w.fc0_b + h0 + hcol);
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                f4 v = z4();
-                if (hcol < hn) {
-                    const f4 z = hid[0][mt] + b;
-                    v = f4{fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f)};
-                }
-                *reinterpret_cast<f4*>(Hc + (16 * mt + c) * ldh + hcol) = v;      // dead columns are zero: stage 2 runs over the whole chunk
-            }
-        }
-        __syncthreads();
-        wave_product<NT, MT>(Hc, ldh, w.fc1_w, Hdim, h0, d, hn, wave, lane, acc);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int n = 16 * (wave + kWaves * t) + g4;
-        if (n >= d) continue;
-        const f4 b = *reinterpret_cast<const f4*>(w.fc1_b + n);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            f4* p = reinterpret_cast<f4*>(A + (16 * mt + c) * lda + n);      // this lane's own elements
-            *p = (acc[t][mt] + b) + *p;
-        }
-    }
-    __syncthreads();
-    norm_rows(A, lda, rows, d, w.norm1_w, w.norm1_b, wave, lane);
-    __syncthreads();
-    const int d4 = d >> 2;
-    for (int i = threadIdx.x; i < rows * d4; i += kThreads) {
-        const int r = i / d4, c4 = i - r * d4;
-        if (r0 + r < R) *reinterpret_cast<f4*>(out + (size_t)(r0 + r) * d + 4 * c4) = *reinterpret_cast<const f4*>(A + r * lda + 4 * c4);
     }
 }
 
@@ -733,15 +623,9 @@ static Plan make_plan(const Dims& d, int64_t P) {
     return p;
 }
 
-template <typename Kern>
-static int lds_set(Kern kernel, size_t bytes) {
-    DYGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return DYGNN_OK;
-}
-
 static int launch_lstm(hipStream_t s, const LstmArgs& a) {
     const size_t lds = (size_t)kRows * (kKChunk + 4) * sizeof(float);
-    if (int rc = lds_set(k_cawn_lstm, lds)) return rc;
+    if (int rc = lds_limit(k_cawn_lstm, lds)) return rc;
     hipLaunchKernelGGL(k_cawn_lstm, dim3((unsigned)ceil_div(a.rows, kRows), (unsigned)ceil_div(a.H, kRows)), dim3(kThreads), lds, s, a);
     DYGNN_LAUNCH_CHECK();
     return DYGNN_OK;
@@ -752,12 +636,12 @@ static int transformer(hipStream_t s, const Dims& d, const dygnn_cawn_weights& w
                        float* Y) {
     const int A = d.A;
     const size_t lds_proj = (size_t)kRows * (kKChunk + 4) * sizeof(float);
-    const size_t lds_post = (size_t)16 * MT * (round16(A) + 4 + kFfnChunk + 4) * sizeof(float);
+    const size_t lds_post = encoder::post_lds_bytes(MT, A);
     const size_t lds_attn = (size_t)3 * d.M * (kMaxHead + 1) * sizeof(float);
     int rc;
-    if ((rc = lds_set(k_cawn_proj<NT>, lds_proj))) return rc;
-    if ((rc = lds_set(k_cawn_post<NT, MT>, lds_post))) return rc;
-    if ((rc = lds_set(k_cawn_attn, lds_attn))) return rc;
+    if ((rc = lds_limit(k_cawn_proj<NT>, lds_proj))) return rc;
+    if ((rc = lds_limit(k_encoder_post<NT, MT>, lds_post))) return rc;
+    if ((rc = lds_limit(k_cawn_attn, lds_attn))) return rc;
     const unsigned tiles = (unsigned)ceil_div(R, kRows);
     hipLaunchKernelGGL(k_cawn_proj<NT>, dim3(tiles), dim3(kThreads), lds_proj, s, EF, 2 * d.Hf, EP, 2 * d.Hp, R, w.proj0_w, w.proj0_b, A, X);
     DYGNN_LAUNCH_CHECK();
@@ -766,7 +650,8 @@ static int transformer(hipStream_t s, const Dims& d, const dygnn_cawn_weights& w
     hipLaunchKernelGGL(k_cawn_attn, dim3((unsigned)(R / d.M)), dim3(kThreads), lds_attn, s, QKV, QKV + (size_t)R * A, QKV + 2 * (size_t)R * A, d.M, A, d.heads,
                        1.0f / sqrtf((float)(A / d.heads)), O);
     DYGNN_LAUNCH_CHECK();
-    hipLaunchKernelGGL((k_cawn_post<NT, MT>), dim3((unsigned)ceil_div(R, 16 * MT)), dim3(kThreads), lds_post, s, O, R, X, w.attn, A, Y);
+    hipLaunchKernelGGL((k_encoder_post<NT, MT>), dim3((unsigned)ceil_div(R, 16 * MT)), dim3(kThreads), lds_post, s, O, R, X, encoder::ResMap{nullptr, d.M, d.M}, w.attn, A,
+                       Y);
     DYGNN_LAUNCH_CHECK();
     return DYGNN_OK;
 }
@@ -834,7 +719,7 @@ extern "C" int dygnn_cawn_forward(const dygnn_cawn_config* cfg, const dygnn_cawn
     const Tree tr{hops->id[0], hops->id[1], hops->eid[0], hops->eid[1], hops->t[0], hops->t[1]};
     int rc;
     const size_t lds_pos = pos_lds_bytes(d.Pd);
-    if ((rc = lds_set(k_cawn_pos, lds_pos))) return rc;
+    if ((rc = lds_limit(k_cawn_pos, lds_pos))) return rc;
     hipLaunchKernelGGL(k_cawn_pos, dim3((unsigned)P), dim3(kThreads), lds_pos, s, side_root, tr, own, w->pos_w0, w->pos_b0, w->pos_w1, w->pos_b1, d.k, d.W, d.M,
                        d.T, d.Pd, pidx, fp(pl.ct), fp(pl.pf));
     DYGNN_LAUNCH_CHECK();

@@ -27,14 +27,18 @@
 //
 // Kernels (k_cawnt_*): tree (ids, dt, valid per node), pos (counts and unique ids of a pair by all-pairs comparison in LDS: <= 146 ids),
 // poshid / mlp_bwd (the position MLP's first layer and its backward), gather (X rows), cell / cell_bwd / rev_bwd / child_sum (the LSTM cell,
-// elementwise on the product outputs), encout, attn_fwd / attn_bwd (one (sequence, head) per workgroup, M <= 64), res_ln / ln_bwd (width up to
-// 512), drop / hid_bwd, mean / bcast, time_part / time_fin (fp64 two-stage sums), pos_scatter (the position-feature gradients of a pair summed
-// per unique id in FIXED tree order by the row's one owner: no atomics), colsum_fin.  Dense products go through train::mm, weight gradients
+// elementwise on the product outputs), encout, attn_fwd / attn_bwd (one (sequence, head) per workgroup, M <= 64), mean / bcast, pos_scatter
+// (the position-feature gradients of a pair summed per unique id in FIXED tree order by the row's one owner: no atomics).  Shared with
+// tcl_train.hip: the block's launch sequence (train::encoder_block_forward / _backward, encoder_block_train.h; identity row map, site base 0)
+// and its row kernels (train_rows.h: train::k_res_ln<8> / k_res_ln_bwd<8> for widths up to 512, k_row_drop / k_hid_bwd, k_time_part /
+// k_time_fin, the fp64 two-stage sums), and the column sums' wave-per-column second stage (train::colsum, colsum.h; its second output gives
+// b_hh the sum of b_ih).  Dense products go through train::mm, weight gradients
 // through train::dw_grouped where its alignment rules hold and train::mm (transposed A, accumulating) where they do not (position_feat_dim
 // = 2 mod 4); bias, LayerNorm and time-encoder gradients are fixed-order column sums; b_ih and b_hh receive the same sum.
 #include "colsum.h"
 #include "common.h"
 #include "dropout.h"
+#include "encoder_block_train.h"
 #include "gemm.h"
 #include "mfma_tile.h"
 #include "tgat_attn.h"
@@ -44,13 +48,13 @@ namespace cawnt {
 
 using attn::cos_time_t;
 using tile::wave_sum;
+using train::colsum;
 
 constexpr int kMaxWalks = 64;       // M = k^W: one key per lane in the attention kernels
 constexpr int kMaxTree2 = 2 * (1 + 8 + 64);      // tree positions of a pair
 constexpr int kMaxHead = 64;
 constexpr int kLdh = kMaxHead + 1;
-constexpr float kLnEps = 1e-5f;
-constexpr int kNV = 8;              // columns per lane of a row: attention_dim <= 512
+constexpr int kNV = 8;              // columns per lane of a row (train_rows.h): attention_dim <= 512
 
 struct Dims {
     int Fn, Fe, Ft, Pd, W, k, M, T, D, Hf, Hp, A, heads, E;
@@ -390,84 +394,6 @@ __global__ __launch_bounds__(256) void k_cawnt_attn_bwd(const float* __restrict_
     }
 }
 
-// ---- residual + dropout + LayerNorm, one wave per row: pre = res + t * mask(site, r d + c); y = LN(pre) ------------------------------------------
-__global__ __launch_bounds__(256) void k_cawnt_res_ln(const float* __restrict__ t, const float* __restrict__ res, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, int64_t R, int d, train::Drop dr, uint32_t site,
-                                                        float* __restrict__ pre, float* __restrict__ mean_o, float* __restrict__ rstd_o, float* __restrict__ y) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= R) return;
-    float x[kNV];
-    float sum = 0.f;
-#pragma unroll
-    for (int u = 0; u < kNV; ++u) {
-        const int f = lane + 64 * u;
-        x[u] = 0.f;
-        if (f < d) {
-            x[u] = res[r * d + f] + t[r * d + f] * dr.mask(site, (uint64_t)r * d + f);
-            pre[r * d + f] = x[u];
-            sum += x[u];
-        }
-    }
-    const float mean = wave_sum(sum) / (float)d;
-    float var = 0.f;
-#pragma unroll
-    for (int u = 0; u < kNV; ++u)
-        if (lane + 64 * u < d) { const float c = x[u] - mean; var = fmaf(c, c, var); }
-    const float rstd = 1.0f / sqrtf(wave_sum(var) / (float)d + kLnEps);
-    if (lane == 0) { mean_o[r] = mean; rstd_o[r] = rstd; }
-#pragma unroll
-    for (int u = 0; u < kNV; ++u) {
-        const int f = lane + 64 * u;
-        if (f < d) y[r * d + f] = fmaf((x[u] - mean) * rstd, gamma[f], beta[f]);
-    }
-}
-// LayerNorm backward, one wave per row: g = dy gamma, dpre = rstd (g - mean(g) - xhat mean(g xhat)) -> dres, and through the redrawn mask -> dt;
-// dyx = dy xhat feeds the gamma gradient.
-__global__ __launch_bounds__(256) void k_cawnt_ln_bwd(const float* __restrict__ dy, const float* __restrict__ pre, const float* __restrict__ mean_in,
-                                                        const float* __restrict__ rstd_in, const float* __restrict__ gamma, int64_t R, int d, train::Drop dr,
-                                                        uint32_t site, float* __restrict__ dres, float* __restrict__ dt, float* __restrict__ dyx) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= R) return;
-    const float mean = mean_in[r], rstd = rstd_in[r];
-    float xh[kNV], g[kNV];
-    float sg = 0.f, sgx = 0.f;
-#pragma unroll
-    for (int u = 0; u < kNV; ++u) {
-        const int f = lane + 64 * u;
-        xh[u] = g[u] = 0.f;
-        if (f < d) {
-            xh[u] = (pre[r * d + f] - mean) * rstd;
-            const float v = dy[r * d + f];
-            g[u] = v * gamma[f];
-            dyx[r * d + f] = v * xh[u];
-            sg += g[u];
-            sgx = fmaf(g[u], xh[u], sgx);
-        }
-    }
-    sg = wave_sum(sg) / (float)d;
-    sgx = wave_sum(sgx) / (float)d;
-#pragma unroll
-    for (int u = 0; u < kNV; ++u) {
-        const int f = lane + 64 * u;
-        if (f < d) {
-            const float v = rstd * (g[u] - sg - xh[u] * sgx);
-            dres[r * d + f] = v;
-            dt[r * d + f] = v * dr.mask(site, (uint64_t)r * d + f);
-        }
-    }
-}
-// site 2: hid [R][4A] *= mask(2, e), one thread per element
-__global__ void k_cawnt_drop(float* __restrict__ hid, int64_t count, train::Drop dr, uint32_t site) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < count) hid[e] *= dr.mask(site, (uint64_t)e);
-}
-// the hidden gradient through dropout and ReLU: the stored rows are positive exactly where the ReLU was open AND the element was kept
-__global__ void k_cawnt_hid_bwd(float* __restrict__ g, const float* __restrict__ hid, int64_t count, float keep_scale) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < count) g[e] = hid[e] > 0.f ? g[e] * keep_scale : 0.f;
-}
 // YM[q][c] = mean over the M walks of Y[q M + j][c]
 __global__ void k_cawnt_mean(const float* __restrict__ Y, int64_t I, int M, int d, float* __restrict__ YM) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -565,36 +491,6 @@ __global__ void k_cawnt_child_sum(const float* __restrict__ G, int64_t base_chil
     SG[i] = s;
 }
 
-// ---- time encoder gradients: dw = sum -sin(pre) dt g, db = sum -sin(pre) g with the forward's pre = fma(dt, w, b), fp64 two-stage fixed-order
-// sums (tcl_train.hip: dt reaches 10^6 and the terms cancel).  part: [blocks][2][Ft] doubles.
-__global__ __launch_bounds__(256) void k_cawnt_time_part(const float* __restrict__ g, const float* __restrict__ DT, const float* __restrict__ tw,
-                                                           const float* __restrict__ tb, int64_t R, int Ft, double* __restrict__ part) {
-    const int64_t r0 = (int64_t)blockIdx.x * tgt::kColRows, r1 = r0 + tgt::kColRows < R ? r0 + tgt::kColRows : R;
-    for (int f = threadIdx.x; f < Ft; f += blockDim.x) {
-        const float w = tw[f], b = tb[f];
-        double sw = 0.0, sb = 0.0;
-        for (int64_t r = r0; r < r1; ++r) {
-            const float dt = DT[r];
-            const double t = (double)(-sinf(fmaf(dt, w, b))) * (double)g[r * Ft + f];
-            sb += t;
-            sw += t * (double)dt;
-        }
-        part[((size_t)blockIdx.x * 2) * Ft + f] = sw;
-        part[((size_t)blockIdx.x * 2 + 1) * Ft + f] = sb;
-    }
-}
-__global__ __launch_bounds__(256) void k_cawnt_time_fin(const double* __restrict__ part, int nblk, int Ft, float* __restrict__ gw, float* __restrict__ gb) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= Ft) return;
-    double sw = 0.0, sb = 0.0;
-    for (int b = 0; b < nblk; ++b) {
-        sw += part[((size_t)b * 2) * Ft + f];
-        sb += part[((size_t)b * 2 + 1) * Ft + f];
-    }
-    gw[f] += (float)sw;
-    gb[f] += (float)sb;
-}
-
 // ---- position features: dPF[p][u] = sum, in tree order, of dXP over the tree positions of pair p whose unique id is u ------------------------------
 // One workgroup per pair; every (u, column) has one owner thread that walks the 2 T positions in order: exact to rounding, the same bits run
 // to run, no atomics.
@@ -619,28 +515,6 @@ __global__ __launch_bounds__(256) void k_cawnt_pos_scatter(const float* __restri
     }
 }
 
-// stage 2 of the fixed-order column sums with one wave per column (tcl_train.hip's k_tclt_colsum_fin); out2 (b_hh beside b_ih) gets the same sum
-__global__ __launch_bounds__(256) void k_cawnt_colsum_fin(const float* __restrict__ part, int nblk, int cols, float* __restrict__ out, float* __restrict__ out2) {
-    const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= cols) return;                                           // wave-uniform
-    float s = 0.f;
-    for (int b = lane; b < nblk; b += 64) s += part[(size_t)b * cols + c];
-    s = wave_sum(s);
-    if (lane == 0) {
-        out[c] += s;
-        if (out2) out2[c] += s;
-    }
-}
-// out[c] += sum_r A[r][c] (and out2[c], the same sum);  part: ceil(rows / 32) * cols floats of scratch
-static int colsum(hipStream_t s, const float* A, int lda, int64_t rows, int cols, float* part, float* out, float* out2 = nullptr) {
-    if (rows <= 0) return DYGNN_OK;
-    const int nblk = (int)ceil_div(rows, tgt::kColRows);
-    hipLaunchKernelGGL(tgt::k_tt_colsum_part, dim3((unsigned)nblk), dim3(256), 0, s, A, lda, rows, cols, part);
-    DYGNN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_cawnt_colsum_fin, dim3((unsigned)ceil_div(cols, 4)), dim3(256), 0, s, part, nblk, cols, out, out2);
-    DYGNN_LAUNCH_CHECK();
-    return DYGNN_OK;
-}
 // C[m][n] += sum_k A[k][m] B[k][n]: the grouped split-K kernel where its alignment rules hold, the general product otherwise
 static int wgrad(hipStream_t s, int K, const float* A, int lda, int M, const float* B, int ldb, int N, float* C, int ldc) {
     const bool aligned = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 && lda % 4 == 0 && ldb % 4 == 0 && M % 4 == 0 &&
@@ -692,6 +566,13 @@ static Plan make_plan(const dygnn_cawn_config& c, int64_t B) {
     p.dpf = take(PR * d.Pd), p.dhs = take(PR * d.Pd), p.dp = take(2 * PR * d.Pd);
     p.total = o;
     return p;
+}
+
+// the buffers of the one transformer block (encoder_block_train.h)
+static train::BlockBufs bufs(const Plan& p, char* ws) {
+    auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    return {F32(p.qkv), F32(p.O), F32(p.pre0), F32(p.mean0), F32(p.rstd0), F32(p.y0), F32(p.hid), F32(p.pre1), F32(p.mean1), F32(p.rstd1), F32(p.y),
+            F32(p.tmp), F32(p.gA), F32(p.gB), F32(p.gC), F32(p.gD), F32(p.gE), F32(p.gF), F32(p.dhid), F32(p.dqkv), F32(p.part)};
 }
 
 static int check_lstm(const dygnn_cawn_lstm_weights* m, const char* what) {
@@ -804,31 +685,19 @@ extern "C" int dygnn_cawn_train_forward(const dygnn_cawn_config* cfg, const dygn
     hipLaunchKernelGGL(k_cawnt_encout, dim3(blocks(p.R * d.E)), dim3(256), 0, s, F32(p.enc[0].h), F32(p.enc[0].hr), F32(p.enc[1].h), F32(p.enc[1].hr), valid, L,
                        d.Hf, d.Hp, F32(p.eo));
     DYGNN_LAUNCH_CHECK();
-    // projection_layers[0], the transformer block over the M walks of a sequence
-    const dygnn_tcl_layer_weights& m = w->attn;
+    // projection_layers[0], the transformer block over the M walks of a sequence (sites 0 .. 3, every row draws as itself)
     const train::Drop dr = train::make_drop(dropout_p, seed);
     const float scale = 1.0f / sqrtf((float)(A / d.heads));
-    const unsigned row_blocks = (unsigned)ceil_div(p.R, 4);
     if (int rc = train::mm(s, F32(p.eo), d.E, false, w->proj0_w, d.E, true, F32(p.x0), A, R, A, d.E, w->proj0_b)) return rc;
-    if (int rc = train::mm(s, F32(p.x0), A, false, m.in_proj_w, A, true, F32(p.qkv), 3 * A, R, 3 * A, A, m.in_proj_b)) return rc;
-    const size_t lds_fwd = (size_t)3 * d.M * kLdh * sizeof(float);
-    DYGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cawnt_attn_fwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fwd));
-    hipLaunchKernelGGL(k_cawnt_attn_fwd, dim3((unsigned)p.I, (unsigned)d.heads), dim3(256), lds_fwd, s, F32(p.qkv), d.M, A, d.heads, scale, dr, F32(p.P),
-                       F32(p.O));
-    DYGNN_LAUNCH_CHECK();
-    if (int rc = train::mm(s, F32(p.O), A, false, m.out_proj_w, A, true, F32(p.tmp), A, R, A, A, m.out_proj_b)) return rc;
-    hipLaunchKernelGGL(k_cawnt_res_ln, dim3(row_blocks), dim3(256), 0, s, F32(p.tmp), F32(p.x0), m.norm0_w, m.norm0_b, p.R, A, dr, 1u, F32(p.pre0), F32(p.mean0),
-                       F32(p.rstd0), F32(p.y0));
-    DYGNN_LAUNCH_CHECK();
-    if (int rc = train::mm(s, F32(p.y0), A, false, m.fc0_w, A, true, F32(p.hid), 4 * A, R, 4 * A, A, m.fc0_b, 1.f, 0.f, 1, 1, 0, 0, 0, 0, 0, 0, true)) return rc;
-    if (dropout_p > 0.f) {
-        hipLaunchKernelGGL(k_cawnt_drop, dim3(blocks(p.R * 4 * A)), dim3(256), 0, s, F32(p.hid), p.R * 4 * A, dr, 2u);
+    const train::BlockBufs v = bufs(p, ws);
+    auto attn = [&]() -> int {
+        const size_t lds_fwd = (size_t)3 * d.M * kLdh * sizeof(float);
+        DYGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cawnt_attn_fwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fwd));
+        hipLaunchKernelGGL(k_cawnt_attn_fwd, dim3((unsigned)p.I, (unsigned)d.heads), dim3(256), lds_fwd, s, v.qkv, d.M, A, d.heads, scale, dr, F32(p.P), v.O);
         DYGNN_LAUNCH_CHECK();
-    }
-    if (int rc = train::mm(s, F32(p.hid), 4 * A, false, m.fc1_w, 4 * A, true, F32(p.tmp), A, R, A, 4 * A, m.fc1_b)) return rc;
-    hipLaunchKernelGGL(k_cawnt_res_ln, dim3(row_blocks), dim3(256), 0, s, F32(p.tmp), F32(p.y0), m.norm1_w, m.norm1_b, p.R, A, dr, 3u, F32(p.pre1), F32(p.mean1),
-                       F32(p.rstd1), F32(p.y));
-    DYGNN_LAUNCH_CHECK();
+        return DYGNN_OK;
+    };
+    if (int rc = train::encoder_block_forward<kNV>(s, A, p.R, F32(p.x0), w->attn, dr, dropout_p, 0u, train::RowMap{d.M, 0}, v, attn)) return rc;
     // mean over the walks, projection_layers[1]: sequence 2 p -> out_src[p], 2 p + 1 -> out_dst[p] (rows of stride 2 A)
     hipLaunchKernelGGL(k_cawnt_mean, dim3(blocks(p.I * A)), dim3(256), 0, s, F32(p.y), p.I, d.M, A, F32(p.ym));
     DYGNN_LAUNCH_CHECK();
@@ -861,10 +730,8 @@ extern "C" int dygnn_cawn_backward(const dygnn_cawn_config* cfg, const dygnn_caw
     const int32_t* pidx = reinterpret_cast<const int32_t*>(ws + p.pidx);
     const train::Drop dr = train::make_drop(dropout_p, seed);
     const float scale = 1.0f / sqrtf((float)(A / d.heads));
-    const unsigned row_blocks = (unsigned)ceil_div(p.R, 4);
-    float *gA = F32(p.gA), *gB = F32(p.gB), *gC = F32(p.gC), *gD = F32(p.gD), *gE = F32(p.gE), *gF = F32(p.gF), *dhid = F32(p.dhid), *dqkv = F32(p.dqkv),
-          *part = F32(p.part);
-    auto cs = [&](const float* Am, int cols, const float* out) { return colsum(s, Am, cols, p.R, cols, part, G(out)); };
+    float *gA = F32(p.gA), *part = F32(p.part);
+    auto cs = [&](const float* Am, int cols, const float* out) { return colsum(s, Am, cols, p.R, cols, part, out); };
 
     // 1. projection_layers[1] and the mean over the walks
     float* dym = F32(p.dym);
@@ -877,38 +744,18 @@ extern "C" int dygnn_cawn_backward(const dygnn_cawn_config* cfg, const dygnn_caw
     hipLaunchKernelGGL(k_cawnt_bcast, dim3(blocks(p.R * A)), dim3(256), 0, s, dym, p.R, d.M, A, gA);
     DYGNN_LAUNCH_CHECK();
 
-    // 2. the transformer block (tcl_train.hip's order)
+    // 2. the transformer block
     {
-        const dygnn_tcl_layer_weights& m = w->attn;
-        const dygnn_tcl_layer_weights& g = grads->attn;
-        hipLaunchKernelGGL(k_cawnt_ln_bwd, dim3(row_blocks), dim3(256), 0, s, gA, F32(p.pre1), F32(p.mean1), F32(p.rstd1), m.norm1_w, p.R, A, dr, 3u, gB, gC, gD);
-        DYGNN_LAUNCH_CHECK();
-        if (int rc = cs(gD, A, g.norm1_w)) return rc;
-        if (int rc = cs(gA, A, g.norm1_b)) return rc;
-        if (int rc = cs(gC, A, g.fc1_b)) return rc;
-        if (int rc = train::mm(s, gC, A, false, m.fc1_w, 4 * A, false, dhid, 4 * A, R, 4 * A, A)) return rc;
-        hipLaunchKernelGGL(k_cawnt_hid_bwd, dim3(blocks(p.R * 4 * A)), dim3(256), 0, s, dhid, F32(p.hid), p.R * 4 * A, dr.scale);
-        DYGNN_LAUNCH_CHECK();
-        if (int rc = cs(dhid, 4 * A, g.fc0_b)) return rc;
-        if (int rc = train::mm(s, dhid, 4 * A, false, m.fc0_w, A, false, gB, A, R, A, 4 * A, nullptr, 1.f, 1.f)) return rc;
-        hipLaunchKernelGGL(k_cawnt_ln_bwd, dim3(row_blocks), dim3(256), 0, s, gB, F32(p.pre0), F32(p.mean0), F32(p.rstd0), m.norm0_w, p.R, A, dr, 1u, gA, gE, gD);
-        DYGNN_LAUNCH_CHECK();
-        if (int rc = cs(gD, A, g.norm0_w)) return rc;
-        if (int rc = cs(gB, A, g.norm0_b)) return rc;
-        if (int rc = cs(gE, A, g.out_proj_b)) return rc;
-        if (int rc = train::mm(s, gE, A, false, m.out_proj_w, A, false, gF, A, R, A, A)) return rc;
-        const size_t lds_bwd = ((size_t)4 * d.M * kLdh + (size_t)2 * d.M * (d.M + 1)) * sizeof(float);
-        DYGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cawnt_attn_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bwd));
-        hipLaunchKernelGGL(k_cawnt_attn_bwd, dim3((unsigned)p.I, (unsigned)d.heads), dim3(256), lds_bwd, s, F32(p.qkv), F32(p.P), gF, d.M, A, d.heads, scale, dr,
-                           dqkv);
-        DYGNN_LAUNCH_CHECK();
-        if (int rc = cs(dqkv, 3 * A, g.in_proj_b)) return rc;
-        if (int rc = train::mm(s, dqkv, 3 * A, false, m.in_proj_w, A, false, gA, A, R, A, 3 * A, nullptr, 1.f, 1.f)) return rc;
-        const train::DwPair pairs[4] = {{dqkv, 3 * A, 3 * A, F32(p.x0), A, A, G(g.in_proj_w), A, nullptr},
-                                        {gE, A, A, F32(p.O), A, A, G(g.out_proj_w), A, nullptr},
-                                        {dhid, 4 * A, 4 * A, F32(p.y0), A, A, G(g.fc0_w), A, nullptr},
-                                        {gC, A, A, F32(p.hid), 4 * A, 4 * A, G(g.fc1_w), 4 * A, nullptr}};
-        if (int rc = train::dw_grouped(s, R, pairs, 4)) return rc;
+        const train::BlockBufs v = bufs(p, ws);
+        auto attn_bwd = [&]() -> int {
+            const size_t lds_bwd = ((size_t)4 * d.M * kLdh + (size_t)2 * d.M * (d.M + 1)) * sizeof(float);
+            DYGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cawnt_attn_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bwd));
+            hipLaunchKernelGGL(k_cawnt_attn_bwd, dim3((unsigned)p.I, (unsigned)d.heads), dim3(256), lds_bwd, s, v.qkv, F32(p.P), v.gF, d.M, A, d.heads, scale, dr,
+                               v.dqkv);
+            DYGNN_LAUNCH_CHECK();
+            return DYGNN_OK;
+        };
+        if (int rc = train::encoder_block_backward<kNV>(s, A, p.R, F32(p.x0), w->attn, grads->attn, dr, 0u, train::RowMap{d.M, 0}, v, attn_bwd)) return rc;
     }
 
     // 3. projection_layers[0]: gA = d X0 -> d [feature forward | feature reverse | position forward | position reverse]
@@ -957,12 +804,8 @@ extern "C" int dygnn_cawn_backward(const dygnn_cawn_config* cfg, const dygnn_caw
 
     // 5. the time encoder
     {
-        const int tblk = (int)ceil_div(p.NT, tgt::kColRows);
         double* tpart = reinterpret_cast<double*>(ws + p.tpart);
-        hipLaunchKernelGGL(k_cawnt_time_part, dim3((unsigned)tblk), dim3(256), 0, s, dxt, F32(p.dtv), w->time_w, w->time_b, p.NT, d.Ft, tpart);
-        DYGNN_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_cawnt_time_fin, dim3(blocks(d.Ft)), dim3(256), 0, s, tpart, tblk, d.Ft, G(grads->time_w), G(grads->time_b));
-        DYGNN_LAUNCH_CHECK();
+        if (int rc = train::time_grad(s, dxt, F32(p.dtv), w->time_w, w->time_b, p.NT, d.Ft, tpart, G(grads->time_w), G(grads->time_b))) return rc;
     }
 
     // 6. position features: the scatter onto the unique ids of a pair, then the MLP once per unique id

@@ -28,7 +28,7 @@
 //           k_gmt_gelu_drop / k_gmt_hid_bwd      GELU and the site-2 mask; the mask times the exact GELU derivative
 //           k_gmt_res / k_gmt_drop_bwd           site-3 mask and residual; the mask on the gradient
 //           k_gmt_cat / k_gmt_bcast              token mean | node part; the mean's gradient / K to the K rows
-//           k_gmt_colsum_fin                     stage 2 of the fixed-order column sums, into up to six tensors
+//           train::k_colsum_fin (colsum.h)       stage 2 of the fixed-order column sums, shared with the other backbones; into up to six tensors
 // Dense products (channel fc0, fc1, their transposes, output_layer) go through train::mm (fp32 MFMA, gemm.h), a block's two channel weight
 // gradients through ONE train::dw_grouped launch (float atomics), every vector gradient and the token half's matrices through fixed-order
 // two-stage column sums (colsum.h's first stage): those are the same bits run to run.
@@ -50,6 +50,7 @@ using gm::history;
 using gm::kLnEps;
 using gm::kMaxTokens;
 using tile::wave_sum;
+using train::colsum;
 
 constexpr int NV = 4;                 // columns per lane of a row: C <= 256
 
@@ -358,38 +359,6 @@ __global__ void k_gmt_bcast(const float* __restrict__ dmean, float* __restrict__
     g[e] = dmean[(r / K) * C + (e - r * C)] / (float)K;
 }
 
-// ---- fixed-order column sums ---------------------------------------------------------------------------------------------------------------
-// Stage 2 with one WAVE per column: lane l adds the partials of blocks l, l + 64, ... in order, then the lanes meet in wave_sum's fixed
-// butterfly (the same bits run to run).  Column c belongs to the first segment whose end exceeds it and is ADDED to that tensor.
-struct Segs { float* out[6]; int end[6]; };
-__global__ __launch_bounds__(256) void k_gmt_colsum_fin(const float* __restrict__ part, int nblk, int cols, Segs sg) {
-    const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= cols) return;                                           // wave-uniform
-    float s = 0.f;
-    for (int b = lane; b < nblk; b += 64) s += part[(size_t)b * cols + c];
-    s = wave_sum(s);
-    if (lane != 0) return;
-    int k = 0;
-    while (c >= sg.end[k]) ++k;
-    sg.out[k][c - (k ? sg.end[k - 1] : 0)] += s;
-}
-// out_k[c] += sum_r A[r][c] over the segments of A's columns;  part: ceil(rows / 32) * cols floats of scratch
-static int colsum(hipStream_t s, const float* A, int lda, int64_t rows, int cols, float* part, const Segs& sg) {
-    if (rows <= 0) return DYGNN_OK;
-    const int nblk = (int)ceil_div(rows, tgt::kColRows);
-    hipLaunchKernelGGL(tgt::k_tt_colsum_part, dim3((unsigned)nblk), dim3(256), 0, s, A, lda, rows, cols, part);
-    DYGNN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_gmt_colsum_fin, dim3((unsigned)ceil_div(cols, 4)), dim3(256), 0, s, part, nblk, cols, sg);
-    DYGNN_LAUNCH_CHECK();
-    return DYGNN_OK;
-}
-static int colsum(hipStream_t s, const float* A, int lda, int64_t rows, int cols, float* part, const float* out) {
-    Segs sg{};
-    sg.out[0] = const_cast<float*>(out);
-    sg.end[0] = cols;
-    return colsum(s, A, lda, rows, cols, part, sg);
-}
-
 // ---- workspace ------------------------------------------------------------------------------------------------------------------------------
 struct Layer { size_t x1, y, mean, rstd, hpre, hact; };
 struct Plan {
@@ -567,7 +536,7 @@ extern "C" int dygnn_graphmixer_backward(const dygnn_graphmixer_config* cfg, con
         hipLaunchKernelGGL(k_gmt_token_bwd, dim3((unsigned)n), dim3(256), lds_tok, s, F32(p.x[l]), gD, m.token_norm_w, m.token_norm_b, m.token_fc0_w,
                            m.token_fc0_b, m.token_fc1_w, K, Kh, C, dr, site, tpart);
         DYGNN_LAUNCH_CHECK();
-        Segs sg{};
+        train::ColSegs sg{};
         const int sizes[6] = {Kh * K, Kh, K * Kh, K, K, K};
         float* outs[6] = {G(g.token_fc0_w), G(g.token_fc0_b), G(g.token_fc1_w), G(g.token_fc1_b), G(g.token_norm_w), G(g.token_norm_b)};
         for (int k = 0, e = 0; k < 6; ++k) { e += sizes[k]; sg.out[k] = outs[k]; sg.end[k] = e; }

@@ -6,8 +6,8 @@
 //   k_tcl_qkv     64 token rows per workgroup, grid.y = {Q, K, V}: rows x in_proj (fp32 MFMA)                                       -> Q, K, V planes
 //   k_tcl_attn    one (query sequence, key sequence) per workgroup, head by head: scores over <= 64 head columns at a time from LDS,
 //                 masked softmax in LDS, weighted value sum                                                                          -> O
-//   k_tcl_post    64 token rows per workgroup: out_proj + residual, LayerNorm, d -> 4d (ReLU) -> d with the hidden rows in LDS 64 columns
-//                 at a time, residual, LayerNorm (all products fp32 MFMA)                                                            -> next X
+//   k_encoder_post<4, 4> (encoder_block.h, shared with cawn.hip)  64 token rows per workgroup: out_proj + residual, LayerNorm, d -> 4d (ReLU)
+//                 -> d with the hidden rows in LDS 64 columns at a time, residual, LayerNorm (all products fp32 MFMA)              -> next X
 //   k_tcl_out     16 rows per workgroup: output_layer on position 0 of every pair sequence                                          -> out_a, out_b
 // A layer is two stages (self, cross) of qkv + attn + post.  The first self stage runs on the sides (a side shared by several pairs is
 // computed once), and so does the Q / K / V product of the first cross stage; from there on everything runs on the 2 P sequences of the
@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "common.h"
+#include "encoder_block.h"
 #include "mfma_tile.h"
 #include "tcl.h"
 #include "tgat_attn.h"
@@ -24,6 +25,8 @@ namespace dygnn {
 namespace tcl {
 
 using attn::cos_time_t;
+using encoder::k_encoder_post;
+using encoder::load_rows;
 using tile::f4;
 using tile::kThreads;
 using tile::kWaves;
@@ -34,11 +37,9 @@ using tile::wave_sum;
 using tile::z4;
 
 constexpr int kMaxSeq = 64;       // S = K + 1 <= 64: one row of scores per lane set, four row tiles
-constexpr int kRows = 64;         // token rows per workgroup of k_tcl_qkv / k_tcl_post
-constexpr int kFfnChunk = 64;     // hidden columns in LDS at a time
+constexpr int kRows = 64;         // token rows per workgroup of k_tcl_qkv / k_encoder_post<4, 4>
 constexpr int kOutRows = 16;
 constexpr int kHeadChunk = 64;    // head columns of Q and K in LDS at a time
-constexpr float kLnEps = 1e-5f;
 
 // ---- encoder input (models/TCL.py:84-128, :156-177) ---------------------------------------------------------------------------------------------
 // LDS: A [16 MT][lda], lda = round16(max(Fn, Fe, Ft)) + 4, filled three times (node rows, edge rows, time encodings): the three products
@@ -110,17 +111,6 @@ __global__ __launch_bounds__(kThreads) void k_tcl_encode(const float* __restrict
     }
 }
 
-// the token rows r0 .. r0 + 63 of X [R][d] into the LDS tile A [64][lda], zero beyond d and beyond R
-__device__ __forceinline__ void load_rows(float* A, int lda, const float* __restrict__ X, int64_t r0, int64_t R, int d) {
-    const int d4 = d >> 2, lda4 = lda >> 2;
-    for (int i = threadIdx.x; i < kRows * lda4; i += kThreads) {
-        const int r = i / lda4, c4 = i - r * lda4;
-        f4 v = z4();
-        if (c4 < d4 && r0 + r < R) v = *reinterpret_cast<const f4*>(X + (size_t)(r0 + r) * d + 4 * c4);
-        *reinterpret_cast<f4*>(A + r * lda + 4 * c4) = v;
-    }
-}
-
 // ---- in_proj: Q, K, V of R token rows ---------------------------------------------------------------------------------------------------------------
 // blockIdx.y picks the plane: QKV + y R d = X in_proj_weight[y d : (y + 1) d]^T + in_proj_bias[y d : (y + 1) d].  LDS: A [64][round16(d) + 4].
 __global__ __launch_bounds__(kThreads) void k_tcl_qkv(const float* __restrict__ X, int64_t R, const float* __restrict__ W, const float* __restrict__ bias,
@@ -129,7 +119,7 @@ __global__ __launch_bounds__(kThreads) void k_tcl_qkv(const float* __restrict__ 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lda = round16(d) + 4, y = blockIdx.y;
     const int64_t r0 = (int64_t)blockIdx.x * kRows;
-    load_rows(smem, lda, X, r0, R, d);
+    load_rows(smem, lda, kRows, X, r0, R, d);
     __syncthreads();
     f4 acc[4][4];
 #pragma unroll
@@ -220,113 +210,6 @@ __global__ __launch_bounds__(kThreads) void k_tcl_attn(const float* __restrict__
             for (int j = 0; j < S; ++j) a = fmaf(Pm[r * LD + j], v[(size_t)j * d + h * dh + cc], a);
             o[(size_t)r * d + h * dh + cc] = a;
         }
-    }
-}
-
-// LayerNorm of the 64 rows of the LDS tile A in place, one wave per row
-__device__ __forceinline__ void norm_rows(float* A, int lda, int d, const float* __restrict__ ln_w, const float* __restrict__ ln_b, int wave, int lane) {
-    for (int r = wave; r < kRows; r += kWaves) {
-        float* row = A + r * lda;
-        float s = 0.f;
-        for (int f = lane; f < d; f += 64) s += row[f];
-        const float mean = wave_sum(s) / (float)d;
-        float v = 0.f;
-        for (int f = lane; f < d; f += 64) { const float x = row[f] - mean; v = fmaf(x, x, v); }
-        const float rstd = 1.0f / sqrtf(wave_sum(v) / (float)d + kLnEps);
-        for (int f = lane; f < d; f += 64) row[f] = fmaf((row[f] - mean) * rstd, ln_w[f], ln_b[f]);
-    }
-}
-
-// ---- the rest of the block for R = n nq token rows (models/modules.py:257-264) -----------------------------------------------------------------
-// Row r is query position r % nq of attention output sequence r / nq; its residual is that position of sequence res_seq[r / nq] (r / nq when
-// NULL) of Xres [.][S][d].  out_proj + bias + residual -> LayerNorm 0 -> A; linear 0, ReLU, linear 1 as in k_gm_ffn (graphmixer.hip): per
-// chunk of 64 hidden columns, wave w computes 16 of them for all rows into Hc, then every wave adds the chunk to its output tiles; + bias + A
-// -> LayerNorm 1 -> out [R][d].  LDS: A [64][round16(d) + 4], Hc [64][68].
-__global__ __launch_bounds__(kThreads) void k_tcl_post(const float* __restrict__ O, int64_t R, int nq, int S, const float* __restrict__ Xres,
-                                                         const int32_t* __restrict__ res_seq, dygnn_tcl_layer_weights w, int d,
-                                                         float* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lda = round16(d) + 4, ldh = kFfnChunk + 4, Hdim = 4 * d;
-    float* A = smem;
-    float* Hc = smem + kRows * lda;
-    const int64_t r0 = (int64_t)blockIdx.x * kRows;
-    const int c = lane & 15, g4 = 4 * (lane >> 4);
-    load_rows(A, lda, O, r0, R, d);
-    __syncthreads();
-    f4 acc[4][4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) acc[t][mt] = z4();
-    wave_product<4, 4>(A, lda, w.out_proj_w, d, 0, d, d, wave, lane, acc);
-    __syncthreads();                                                 // every wave has read the attention rows
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-        const int64_t r = r0 + 16 * mt + c;
-        const float* res = nullptr;
-        if (r < R) {
-            const int64_t seq = r / nq;
-            res = Xres + ((size_t)(res_seq ? res_seq[seq] : seq) * S + (r - seq * nq)) * d;
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int n = 16 * (wave + kWaves * t) + g4;
-            if (n >= d) continue;
-            f4 v = z4();
-            if (res) v = (acc[t][mt] + *reinterpret_cast<const f4*>(w.out_proj_b + n)) + *reinterpret_cast<const f4*>(res + n);
-            *reinterpret_cast<f4*>(A + (16 * mt + c) * lda + n) = v;
-        }
-    }
-    __syncthreads();
-    norm_rows(A, lda, d, w.norm0_w, w.norm0_b, wave, lane);
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) acc[t][mt] = z4();
-    for (int h0 = 0; h0 < Hdim; h0 += kFfnChunk) {
-        const int hn = Hdim - h0 < kFfnChunk ? Hdim - h0 : kFfnChunk;      // live hidden columns of this chunk (a multiple of 16)
-        f4 hid[1][4];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) hid[0][mt] = z4();
-        wave_product<1, 4>(A, lda, w.fc0_w + (size_t)h0 * d, d, 0, hn, d, wave, lane, hid);
-        {
-            const int hcol = 16 * wave + g4;                           // column inside the chunk
-            f4 b = z4();
-            if (hcol < hn) b = *reinterpret_cast<const f4*>(w.fc0_b + h0 + hcol);
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                f4 v = z4();
-                if (hcol < hn) {
-                    const f4 z = hid[0][mt] + b;
-                    v = f4{fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f)};
-                }
-                *reinterpret_cast<f4*>(Hc + (16 * mt + c) * ldh + hcol) = v;      // dead columns are zero: stage 2 runs over the whole chunk
-            }
-        }
-        __syncthreads();
-        wave_product<4, 4>(Hc, ldh, w.fc1_w, Hdim, h0, d, hn, wave, lane, acc);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int n = 16 * (wave + kWaves * t) + g4;
-        if (n >= d) continue;
-        const f4 b = *reinterpret_cast<const f4*>(w.fc1_b + n);
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            f4* p = reinterpret_cast<f4*>(A + (16 * mt + c) * lda + n);      // this lane's own elements: no other lane reads them before the barrier
-            *p = (acc[t][mt] + b) + *p;
-        }
-    }
-    __syncthreads();
-    norm_rows(A, lda, d, w.norm1_w, w.norm1_b, wave, lane);
-    __syncthreads();
-    const int d4 = d >> 2;
-    for (int i = threadIdx.x; i < kRows * d4; i += kThreads) {
-        const int r = i / d4, c4 = i - r * d4;
-        if (r0 + r < R) *reinterpret_cast<f4*>(out + (size_t)(r0 + r) * d + 4 * c4) = *reinterpret_cast<const f4*>(A + r * lda + 4 * c4);
     }
 }
 
@@ -509,10 +392,10 @@ extern "C" int dygnn_tcl_forward(const dygnn_tcl_config* cfg, const dygnn_tcl_we
         DYGNN_LAUNCH_CHECK();
     }
     const size_t lds_rows = (size_t)kRows * (round16(d) + 4) * sizeof(float);
-    const size_t lds_post = lds_rows + (size_t)kRows * (kFfnChunk + 4) * sizeof(float);
+    const size_t lds_post = encoder::post_lds_bytes(4, d);
     const size_t lds_out = (size_t)kOutRows * (round16(d) + 4) * sizeof(float);
     if ((rc = lds_limit(k_tcl_qkv, lds_rows))) return rc;
-    if ((rc = lds_limit(k_tcl_post, lds_post))) return rc;
+    if ((rc = lds_limit(k_encoder_post<4, 4>, lds_post))) return rc;
 
     // one stage: Q / K / V of the n_in input sequences, attention of n_at (query, key) sequence pairs, the rest of the block on their rows
     auto stage = [&](const dygnn_tcl_layer_weights& m, const float* Xin, int64_t n_in, int64_t n_at, const int32_t* q_seq, const int32_t* kv_seq,
@@ -523,7 +406,8 @@ extern "C" int dygnn_tcl_forward(const dygnn_tcl_config* cfg, const dygnn_tcl_we
         hipLaunchKernelGGL(k_tcl_attn, dim3((unsigned)n_at), dim3(kThreads), 0, s, QKV, QKV + (size_t)Rin * d, QKV + 2 * (size_t)Rin * d, q_seq, kv_seq,
                            kv_xor, mask_side, side_root, nbr_id, K, nq, d, H, scale, O);
         DYGNN_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_tcl_post, dim3((unsigned)ceil_div(R, kRows)), dim3(kThreads), lds_post, s, O, R, nq, S, Xin, q_seq, m, d, Xout);
+        hipLaunchKernelGGL((k_encoder_post<4, 4>), dim3((unsigned)ceil_div(R, kRows)), dim3(kThreads), lds_post, s, O, R, Xin, encoder::ResMap{q_seq, nq, S}, m, d,
+                           Xout);
         DYGNN_LAUNCH_CHECK();
         return DYGNN_OK;
     };

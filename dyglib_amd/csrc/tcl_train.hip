@@ -21,15 +21,18 @@
 //
 // Kernels:  k_tclt_attn_fwd / k_tclt_attn_bwd  one (query sequence, head) per workgroup, tiles in LDS as in k_tcl_attn; the backward's four
 //                                              products (dO V^T, dS K, dS^T Q, (P mask)^T dO) are fp32 MFMA on LDS tiles;
-//           k_tclt_res_ln / k_tclt_ln_bwd      residual + dropout + LayerNorm and its backward, one wave per row;
-//           k_tclt_drop / k_tclt_hid_bwd       site-2 dropout and the ReLU-and-dropout mask of the hidden gradient;
 //           k_tclt_enc_rows                     the encoder's gathered operand rows;
-//           k_tclt_time_part / k_tclt_time_fin  the time encoder's gradients, fixed-order fp64 column sums.
+//           shared (train_rows.h): train::k_res_ln<4> / k_res_ln_bwd<4>  residual + dropout + LayerNorm and its backward, one wave per row;
+//                                  train::k_row_drop / k_hid_bwd         site-2 dropout and the ReLU-and-dropout mask of the hidden gradient;
+//                                  train::k_time_part / k_time_fin       the time encoder's gradients, fixed-order fp64 column sums.
+// A stage's launch sequence, forward and backward, is train::encoder_block_forward / _backward (encoder_block_train.h, shared with
+// cawn_train.hip) with the row map {S, B} (side s draws as pair sequence 2 p + side) and the site base 8 layer + 4 stage.
 // Dense products (in_proj, out_proj, fc0, fc1, their transposes, output_layer) go through train::mm (fp32 MFMA, gemm.h), the weight gradients
-// of a stage through ONE train::dw_grouped launch, LayerNorm, bias and depth gradients through fixed-order two-stage column sums (colsum.h's first stage, k_tclt_colsum_fin).  Padded query positions are reachable only as masked keys (P = 0 exactly), so their gradient is exactly zero by construction.
+// of a stage through ONE train::dw_grouped launch, LayerNorm, bias and depth gradients through fixed-order two-stage column sums (train::colsum, colsum.h: one wave per column in the second stage).  Padded query positions are reachable only as masked keys (P = 0 exactly), so their gradient is exactly zero by construction.
 #include "colsum.h"
 #include "common.h"
 #include "dropout.h"
+#include "encoder_block_train.h"
 #include "gemm.h"
 #include "mfma_tile.h"
 #include "tcl.h"
@@ -44,14 +47,13 @@ using tile::mfma4;
 using tile::round16;
 using tile::wave_sum;
 using tile::z4;
+using train::colsum;
+using train::pair_seq;      // the dropout generator's sequence index of side s (train_rows.h)
 
 constexpr int kMaxSeq = 64;
 constexpr int kHeadChunk = 64;
-constexpr float kLnEps = 1e-5f;
-constexpr int NV = 4;                 // columns per lane of a row: d <= 256
+constexpr int NV = 4;                 // columns per lane of a row (train_rows.h): d <= 256
 
-// pair-sequence index of side s (the dropout generator's sequence index)
-__device__ __forceinline__ int64_t pair_seq(int64_t s, int64_t B) { return s < B ? 2 * s : 2 * (s - B) + 1; }
 
 // ---- attention forward of (query sequence s, head h) -------------------------------------------------------------------------------------
 // k_tcl_attn on the interleaved q | k | v rows (stride 3d), one head per workgroup; keys / values and the key mask come from sequence s
@@ -248,99 +250,6 @@ __global__ __launch_bounds__(256) void k_tclt_attn_bwd(const float* __restrict__
     }
 }
 
-// ---- residual + dropout + LayerNorm, one wave per row: pre = res + t * mask(site, (q S + i) d + c); y = LN(pre) --------------------------------
-__global__ __launch_bounds__(256) void k_tclt_res_ln(const float* __restrict__ t, const float* __restrict__ res, const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta, int64_t R, int S, int d, int64_t B, train::Drop dr, uint32_t site,
-                                                       float* __restrict__ pre, float* __restrict__ mean_o, float* __restrict__ rstd_o, float* __restrict__ y) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= R) return;
-    const int64_t sd = r / S;
-    const uint64_t e0 = (uint64_t)(pair_seq(sd, B) * S + (r - sd * S)) * d;
-    const uint32_t skey = dr.site_key(site);
-    float x[NV];
-    float sum = 0.f;
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-        const int f = lane + 64 * u;
-        x[u] = 0.f;
-        if (f < d) {
-            const uint64_t idx = e0 + f;
-            x[u] = res[r * d + f] + t[r * d + f] * dr.mask32(skey, (uint32_t)idx + 0x27d4eb2fU * (uint32_t)(idx >> 32));
-            pre[r * d + f] = x[u];
-            sum += x[u];
-        }
-    }
-    const float mean = wave_sum(sum) / (float)d;
-    float var = 0.f;
-#pragma unroll
-    for (int u = 0; u < NV; ++u)
-        if (lane + 64 * u < d) { const float c = x[u] - mean; var = fmaf(c, c, var); }
-    const float rstd = 1.0f / sqrtf(wave_sum(var) / (float)d + kLnEps);
-    if (lane == 0) { mean_o[r] = mean; rstd_o[r] = rstd; }
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-        const int f = lane + 64 * u;
-        if (f < d) y[r * d + f] = fmaf((x[u] - mean) * rstd, gamma[f], beta[f]);
-    }
-}
-
-// LayerNorm backward, one wave per row: g = dy gamma, dpre = rstd (g - mean(g) - xhat mean(g xhat)).  dpre reaches the residual (dres) and,
-// through the redrawn mask, the dropped-out term (dt); dyx = dy xhat feeds the gamma gradient.
-__global__ __launch_bounds__(256) void k_tclt_ln_bwd(const float* __restrict__ dy, const float* __restrict__ pre, const float* __restrict__ mean_in,
-                                                       const float* __restrict__ rstd_in, const float* __restrict__ gamma, int64_t R, int S, int d, int64_t B,
-                                                       train::Drop dr, uint32_t site, float* __restrict__ dres, float* __restrict__ dt,
-                                                       float* __restrict__ dyx) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= R) return;
-    const int64_t sd = r / S;
-    const uint64_t e0 = (uint64_t)(pair_seq(sd, B) * S + (r - sd * S)) * d;
-    const uint32_t skey = dr.site_key(site);
-    const float mean = mean_in[r], rstd = rstd_in[r];
-    float xh[NV], g[NV];
-    float sg = 0.f, sgx = 0.f;
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-        const int f = lane + 64 * u;
-        xh[u] = g[u] = 0.f;
-        if (f < d) {
-            xh[u] = (pre[r * d + f] - mean) * rstd;
-            const float v = dy[r * d + f];
-            g[u] = v * gamma[f];
-            dyx[r * d + f] = v * xh[u];
-            sg += g[u];
-            sgx = fmaf(g[u], xh[u], sgx);
-        }
-    }
-    sg = wave_sum(sg) / (float)d;
-    sgx = wave_sum(sgx) / (float)d;
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-        const int f = lane + 64 * u;
-        if (f < d) {
-            const uint64_t idx = e0 + f;
-            const float v = rstd * (g[u] - sg - xh[u] * sgx);
-            dres[r * d + f] = v;
-            dt[r * d + f] = v * dr.mask32(skey, (uint32_t)idx + 0x27d4eb2fU * (uint32_t)(idx >> 32));
-        }
-    }
-}
-
-// site 2: hid [R][4d] *= mask(site, (q S + i) 4d + c), one thread per element
-__global__ void k_tclt_drop(float* __restrict__ hid, int64_t R, int S, int W, int64_t B, train::Drop dr, uint32_t site) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= R * W) return;
-    const int64_t r = e / W, sd = r / S;
-    const uint64_t idx = (uint64_t)(pair_seq(sd, B) * S + (r - sd * S)) * W + (uint64_t)(e - r * W);
-    hid[e] *= dr.mask(site, idx);
-}
-// the hidden gradient through dropout and ReLU: the stored rows are positive exactly where the ReLU was open AND the element was kept
-__global__ void k_tclt_hid_bwd(float* __restrict__ g, const float* __restrict__ hid, int64_t count, float keep_scale) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < count) g[e] = hid[e] > 0.f ? g[e] * keep_scale : 0.f;
-}
-
 // ---- encoder backward operands: the rows the three projections read, regathered (k_tcl_encode's clamps and dt) -------------------------------
 // One side per workgroup: NF [R][Fn], EF [R][Fe], TF [R][Ft] = cos(fma(dt, w, b)), DT [R].  The feature tables are the forward's, whose
 // pointers wait in the workspace (the backward entry point does not take them).
@@ -385,60 +294,6 @@ __global__ __launch_bounds__(256) void k_tclt_enc_rows(const float* const* __res
         }
     }
 }
-// Time encoder gradients: dw = sum_r -sin(pre) dt g, db = sum_r -sin(pre) g with the forward's pre = fma(dt, w, b), as fixed-order column sums
-// (k_tt_colsum_part / _fin's two stages: 32 rows per workgroup, then the partials in block order).  dt reaches 10^6 and the terms cancel, so
-// the terms and both stages are fp64 (the reference's autograd sums this product in fp64 too: its time encoder input is a double).
-// part: [blocks][2][Ft] doubles.
-__global__ __launch_bounds__(256) void k_tclt_time_part(const float* __restrict__ g, const float* __restrict__ DT, const float* __restrict__ tw,
-                                                          const float* __restrict__ tb, int64_t R, int Ft, double* __restrict__ part) {
-    const int64_t r0 = (int64_t)blockIdx.x * tgt::kColRows, r1 = r0 + tgt::kColRows < R ? r0 + tgt::kColRows : R;
-    for (int f = threadIdx.x; f < Ft; f += blockDim.x) {
-        const float w = tw[f], b = tb[f];
-        double sw = 0.0, sb = 0.0;
-        for (int64_t r = r0; r < r1; ++r) {
-            const float dt = DT[r];
-            const double t = (double)(-sinf(fmaf(dt, w, b))) * (double)g[r * Ft + f];
-            sb += t;
-            sw += t * (double)dt;
-        }
-        part[((size_t)blockIdx.x * 2) * Ft + f] = sw;
-        part[((size_t)blockIdx.x * 2 + 1) * Ft + f] = sb;
-    }
-}
-__global__ __launch_bounds__(256) void k_tclt_time_fin(const double* __restrict__ part, int nblk, int Ft, float* __restrict__ gw, float* __restrict__ gb) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= Ft) return;
-    double sw = 0.0, sb = 0.0;
-    for (int b = 0; b < nblk; ++b) {
-        sw += part[((size_t)b * 2) * Ft + f];
-        sb += part[((size_t)b * 2 + 1) * Ft + f];
-    }
-    gw[f] += (float)sw;
-    gb[f] += (float)sb;
-}
-
-// Stage 2 of the fixed-order column sums with one WAVE per column: lane l adds the partials of blocks l, l + 64, ... in order, then the
-// lanes meet in wave_sum's fixed butterfly (the same bits run to run).  tgt::k_tt_colsum_fin walks the partials with one thread per
-// column: 57 us per call at this path's 263 row blocks, 76 calls per step.
-__global__ __launch_bounds__(256) void k_tclt_colsum_fin(const float* __restrict__ part, int nblk, int cols, float* __restrict__ out) {
-    const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= cols) return;                                           // wave-uniform
-    float s = 0.f;
-    for (int b = lane; b < nblk; b += 64) s += part[(size_t)b * cols + c];
-    s = wave_sum(s);
-    if (lane == 0) out[c] += s;
-}
-// out[c] += sum_r A[r][c];  part: ceil(rows / 32) * cols floats of scratch
-static int colsum(hipStream_t s, const float* A, int lda, int64_t rows, int cols, float* part, float* out) {
-    if (rows <= 0) return DYGNN_OK;
-    const int nblk = (int)ceil_div(rows, tgt::kColRows);
-    hipLaunchKernelGGL(tgt::k_tt_colsum_part, dim3((unsigned)nblk), dim3(256), 0, s, A, lda, rows, cols, part);
-    DYGNN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_tclt_colsum_fin, dim3((unsigned)ceil_div(cols, 4)), dim3(256), 0, s, part, nblk, cols, out);
-    DYGNN_LAUNCH_CHECK();
-    return DYGNN_OK;
-}
-
 // ---- workspace ------------------------------------------------------------------------------------------------------------------------------
 struct Stage { size_t qkv, P, O, pre0, mean0, rstd0, y0, hid, pre1, mean1, rstd1, out; };
 struct Plan {
@@ -481,6 +336,14 @@ static Plan make_plan(const dygnn_tcl_config& c, int64_t B) {
     p.tpart = take((size_t)ceil_div(p.R, tgt::kColRows) * 4 * p.Ft);      // [blocks][2][Ft] doubles
     p.total = o;
     return p;
+}
+
+// the block buffers of stage t (encoder_block_train.h)
+static train::BlockBufs bufs(const Plan& p, char* ws, int t) {
+    auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    const Stage& v = p.st[t];
+    return {F32(v.qkv), F32(v.O), F32(v.pre0), F32(v.mean0), F32(v.rstd0), F32(v.y0), F32(v.hid), F32(v.pre1), F32(v.mean1), F32(v.rstd1), F32(v.out),
+            F32(p.tmp), F32(p.gA), F32(p.gB), F32(p.gC), F32(p.gD), F32(p.gE), F32(p.gF), F32(p.dhid), F32(p.dqkv), F32(p.part)};
 }
 
 static int check_weights(const dygnn_tcl_weights* w, int L, const char* what) {
@@ -531,7 +394,7 @@ extern "C" int dygnn_tcl_train_forward(const dygnn_tcl_config* cfg, const dygnn_
     hipStream_t s = as_stream(stream);
     char* ws = static_cast<char*>(workspace);
     auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    const int K = p.K, S = p.S, d = p.d, H = p.H, R = (int)p.R;
+    const int K = p.K, S = p.S, d = p.d, H = p.H;
     const int64_t n = p.n, B = batch;
     int64_t* root = reinterpret_cast<int64_t*>(ws + p.root);
     double* tms = reinterpret_cast<double*>(ws + p.time);
@@ -548,31 +411,18 @@ extern "C" int dygnn_tcl_train_forward(const dygnn_tcl_config* cfg, const dygnn_
     if (int rc = tcl::encode(s, *cfg, *w, node_feat, edge_feat, root, tms, nid, neid, nt, n, F32(p.x0))) return rc;
     const train::Drop dr = train::make_drop(dropout_p, seed);
     const float scale = 1.0f / sqrtf((float)(d / H));
-    const unsigned row_blocks = (unsigned)ceil_div(p.R, 4);
     const float* X = F32(p.x0);
     for (int t = 0; t < 2 * p.L; ++t) {
-        const dygnn_tcl_layer_weights& m = w->layers[t / 2];
-        const Stage& v = p.st[t];
+        const train::BlockBufs v = bufs(p, ws, t);
         const uint32_t site = 8u * (uint32_t)(t / 2) + 4u * (uint32_t)(t & 1);
-        if (int rc = train::mm(s, X, d, false, m.in_proj_w, d, true, F32(v.qkv), 3 * d, R, 3 * d, d, m.in_proj_b)) return rc;
-        hipLaunchKernelGGL(k_tclt_attn_fwd, dim3((unsigned)n, (unsigned)H), dim3(256), 0, s, F32(v.qkv), B, t & 1, root, nid, K, d, H, scale, dr, site,
-                           F32(v.P), F32(v.O));
-        DYGNN_LAUNCH_CHECK();
-        if (int rc = train::mm(s, F32(v.O), d, false, m.out_proj_w, d, true, F32(p.tmp), d, R, d, d, m.out_proj_b)) return rc;
-        hipLaunchKernelGGL(k_tclt_res_ln, dim3(row_blocks), dim3(256), 0, s, F32(p.tmp), X, m.norm0_w, m.norm0_b, p.R, S, d, B, dr, site + 1, F32(v.pre0),
-                           F32(v.mean0), F32(v.rstd0), F32(v.y0));
-        DYGNN_LAUNCH_CHECK();
-        if (int rc = train::mm(s, F32(v.y0), d, false, m.fc0_w, d, true, F32(v.hid), 4 * d, R, 4 * d, d, m.fc0_b, 1.f, 0.f, 1, 1, 0, 0, 0, 0, 0, 0, true))
-            return rc;
-        if (dropout_p > 0.f) {
-            hipLaunchKernelGGL(k_tclt_drop, dim3((unsigned)ceil_div(p.R * 4 * d, 256)), dim3(256), 0, s, F32(v.hid), p.R, S, 4 * d, B, dr, site + 2);
+        float* P = F32(p.st[t].P);
+        auto attn = [&]() -> int {
+            hipLaunchKernelGGL(k_tclt_attn_fwd, dim3((unsigned)n, (unsigned)H), dim3(256), 0, s, v.qkv, B, t & 1, root, nid, K, d, H, scale, dr, site, P, v.O);
             DYGNN_LAUNCH_CHECK();
-        }
-        if (int rc = train::mm(s, F32(v.hid), 4 * d, false, m.fc1_w, 4 * d, true, F32(p.tmp), d, R, d, 4 * d, m.fc1_b)) return rc;
-        hipLaunchKernelGGL(k_tclt_res_ln, dim3(row_blocks), dim3(256), 0, s, F32(p.tmp), F32(v.y0), m.norm1_w, m.norm1_b, p.R, S, d, B, dr, site + 3,
-                           F32(v.pre1), F32(v.mean1), F32(v.rstd1), F32(v.out));
-        DYGNN_LAUNCH_CHECK();
-        X = F32(v.out);
+            return DYGNN_OK;
+        };
+        if (int rc = train::encoder_block_forward<NV>(s, d, p.R, X, w->layers[t / 2], dr, dropout_p, site, train::RowMap{S, B}, v, attn)) return rc;
+        X = v.out;
     }
     // output_layer on position 0 of every sequence: rows of stride S d
     if (int rc = train::mm(s, X, S * d, false, w->output_w, d, true, out_src, d, (int)B, d, d, w->output_b)) return rc;
@@ -601,10 +451,8 @@ extern "C" int dygnn_tcl_backward(const dygnn_tcl_config* cfg, const dygnn_tcl_w
     const int64_t n = p.n, B = batch;
     const train::Drop dr = train::make_drop(dropout_p, seed);
     const float scale = 1.0f / sqrtf((float)(d / H));
-    const unsigned row_blocks = (unsigned)ceil_div(p.R, 4);
-    float *gA = F32(p.gA), *gB = F32(p.gB), *gC = F32(p.gC), *gD = F32(p.gD), *gE = F32(p.gE), *gF = F32(p.gF), *dhid = F32(p.dhid), *dqkv = F32(p.dqkv),
-          *part = F32(p.part);
-    auto cs = [&](const float* A, int cols, const float* out) { return colsum(s, A, cols, p.R, cols, part, G(out)); };
+    float *gA = F32(p.gA), *part = F32(p.part);
+    auto cs = [&](const float* A, int cols, const float* out) { return colsum(s, A, cols, p.R, cols, part, out); };
 
     // output_layer: the gradient enters at position 0 of every sequence, every other row starts at zero
     const float* Z = F32(p.st[2 * p.L - 1].out);
@@ -619,43 +467,18 @@ extern "C" int dygnn_tcl_backward(const dygnn_tcl_config* cfg, const dygnn_tcl_w
         if (int rc = colsum(s, grad_out_dst, d, B, d, part, G(grads->output_b))) return rc;
     }
     for (int t = 2 * p.L - 1; t >= 0; --t) {
-        const dygnn_tcl_layer_weights& m = w->layers[t / 2];
-        const dygnn_tcl_layer_weights& g = grads->layers[t / 2];
-        const Stage& v = p.st[t];
+        const train::BlockBufs v = bufs(p, ws, t);
         const float* X = t == 0 ? F32(p.x0) : F32(p.st[t - 1].out);
         const uint32_t site = 8u * (uint32_t)(t / 2) + 4u * (uint32_t)(t & 1);
-        // LayerNorm 1, fc1 dropout: gA = d out -> gB = d y0 (residual part), gC = d (fc1 output)
-        hipLaunchKernelGGL(k_tclt_ln_bwd, dim3(row_blocks), dim3(256), 0, s, gA, F32(v.pre1), F32(v.mean1), F32(v.rstd1), m.norm1_w, p.R, S, d, B, dr, site + 3,
-                           gB, gC, gD);
-        DYGNN_LAUNCH_CHECK();
-        if (int rc = cs(gD, d, g.norm1_w)) return rc;
-        if (int rc = cs(gA, d, g.norm1_b)) return rc;
-        if (int rc = cs(gC, d, g.fc1_b)) return rc;
-        // fc1^T, ReLU and site-2 mask, fc0^T
-        if (int rc = train::mm(s, gC, d, false, m.fc1_w, 4 * d, false, dhid, 4 * d, R, 4 * d, d)) return rc;
-        hipLaunchKernelGGL(k_tclt_hid_bwd, dim3((unsigned)ceil_div(p.R * 4 * d, 256)), dim3(256), 0, s, dhid, F32(v.hid), p.R * 4 * d, dr.scale);
-        DYGNN_LAUNCH_CHECK();
-        if (int rc = cs(dhid, 4 * d, g.fc0_b)) return rc;
-        if (int rc = train::mm(s, dhid, 4 * d, false, m.fc0_w, d, false, gB, d, R, d, 4 * d, nullptr, 1.f, 1.f)) return rc;
-        // LayerNorm 0, attention block dropout: gB = d y0 -> gA = d X (residual part), gE = d (out_proj output)
-        hipLaunchKernelGGL(k_tclt_ln_bwd, dim3(row_blocks), dim3(256), 0, s, gB, F32(v.pre0), F32(v.mean0), F32(v.rstd0), m.norm0_w, p.R, S, d, B, dr, site + 1,
-                           gA, gE, gD);
-        DYGNN_LAUNCH_CHECK();
-        if (int rc = cs(gD, d, g.norm0_w)) return rc;
-        if (int rc = cs(gB, d, g.norm0_b)) return rc;
-        if (int rc = cs(gE, d, g.out_proj_b)) return rc;
-        // out_proj^T, attention, in_proj^T
-        if (int rc = train::mm(s, gE, d, false, m.out_proj_w, d, false, gF, d, R, d, d)) return rc;
-        hipLaunchKernelGGL(k_tclt_attn_bwd, dim3((unsigned)n, (unsigned)H), dim3(256), 0, s, F32(v.qkv), F32(v.P), gF, B, t & 1, K, d, H, scale, dr, site, dqkv);
-        DYGNN_LAUNCH_CHECK();
-        if (int rc = cs(dqkv, 3 * d, g.in_proj_b)) return rc;
-        if (int rc = train::mm(s, dqkv, 3 * d, false, m.in_proj_w, d, false, gA, d, R, d, 3 * d, nullptr, 1.f, 1.f)) return rc;
-        // the stage's weight gradients, grouped split-K over its R rows (both stages of a layer add into the same tensors)
-        const train::DwPair pairs[4] = {{dqkv, 3 * d, 3 * d, X, d, d, G(g.in_proj_w), d, nullptr},
-                                        {gE, d, d, F32(v.O), d, d, G(g.out_proj_w), d, nullptr},
-                                        {dhid, 4 * d, 4 * d, F32(v.y0), d, d, G(g.fc0_w), d, nullptr},
-                                        {gC, d, d, F32(v.hid), 4 * d, 4 * d, G(g.fc1_w), 4 * d, nullptr}};
-        if (int rc = train::dw_grouped(s, R, pairs, 4)) return rc;
+        const float* P = F32(p.st[t].P);
+        auto attn_bwd = [&]() -> int {
+            hipLaunchKernelGGL(k_tclt_attn_bwd, dim3((unsigned)n, (unsigned)H), dim3(256), 0, s, v.qkv, P, v.gF, B, t & 1, K, d, H, scale, dr, site, v.dqkv);
+            DYGNN_LAUNCH_CHECK();
+            return DYGNN_OK;
+        };
+        // both stages of a layer add into the same 12 tensors
+        if (int rc = train::encoder_block_backward<NV>(s, d, p.R, X, w->layers[t / 2], grads->layers[t / 2], dr, site, train::RowMap{S, B}, v, attn_bwd))
+            return rc;
     }
     // encoder: gA = d X0.  Biases and the depth embedding are column sums of it; the projections' operand rows are regathered
     float *NF = F32(p.nf), *EF = F32(p.ef), *TF = F32(p.tf), *DT = F32(p.dtv), *dtf = F32(p.dtf);
@@ -670,11 +493,7 @@ extern "C" int dygnn_tcl_backward(const dygnn_tcl_config* cfg, const dygnn_tcl_w
                        Ft, (int64_t)cfg->num_node_rows, (int64_t)cfg->num_edge_rows, NF, EF, TF, DT);
     DYGNN_LAUNCH_CHECK();
     if (int rc = train::mm(s, gA, d, false, w->proj_time_w, Ft, false, dtf, Ft, R, Ft, d)) return rc;
-    const int tblk = (int)ceil_div(p.R, tgt::kColRows);
-    hipLaunchKernelGGL(k_tclt_time_part, dim3((unsigned)tblk), dim3(256), 0, s, dtf, DT, w->time_w, w->time_b, p.R, Ft, tpart);
-    DYGNN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_tclt_time_fin, dim3((unsigned)ceil_div(Ft, 256)), dim3(256), 0, s, tpart, tblk, Ft, G(grads->time_w), G(grads->time_b));
-    DYGNN_LAUNCH_CHECK();
+    if (int rc = train::time_grad(s, dtf, DT, w->time_w, w->time_b, p.R, Ft, tpart, G(grads->time_w), G(grads->time_b))) return rc;
     const train::DwPair pairs[3] = {{gA, d, d, NF, d, d, G(grads->proj_node_w), d, nullptr},
                                     {gA, d, d, EF, Fe, Fe, G(grads->proj_edge_w), Fe, nullptr},
                                     {gA, d, d, TF, Ft, Ft, G(grads->proj_time_w), Ft, nullptr}};

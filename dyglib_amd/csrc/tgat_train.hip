@@ -12,7 +12,9 @@
 //   * every activation the backward pass reads stays in the call's workspace (TrainPlan).
 // K and V stay un-materialised: the attention kernels gather the k neighbour input rows x_ij = [h_lower | edge | cos(w dt + b)]
 // on the fly and work with W_k,h^T q_ih; the products go through the library's GEMMs (gemm.h), the weight gradients through one grouped
-// split-K launch per layer (train::dw_grouped).
+// split-K launch per layer (train::dw_grouped).  The LayerNorm backward with the residual_fc dropout is the shared train::k_res_ln_bwd<5>
+// (train_rows.h, with tcl_train.hip and cawn_train.hip; identity row map); the column sums keep colsum.h's one-thread-per-column second
+// stage (tgt::colsum), whose summation order the wave-per-column train::colsum does not have.
 #include "colsum.h"
 #include "common.h"
 #include "dropout.h"
@@ -20,18 +22,15 @@
 #include "tgat_attn.h"
 #include "tgat_levels.h"
 #include "tgat_train.h"
+#include "train_rows.h"
 
 namespace dygnn {
 namespace tgt {
 
 using f4 = __attribute__((ext_vector_type(4))) float;
 constexpr int NC = 4;                 // float4 columns per lane of an input row: Dkv <= 4 * 64 * 4 = 1024
+using tile::wave_sum;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 // TGN: the gradient row of a level-0 node, or NULL where the node passes no gradient on (no pending message; id 0, the padding, never has one)
 __device__ __forceinline__ float* feat0_row(const Feat0Grad& fg, int32_t node, int Fn) {
     if (!fg.d || node < 0 || node >= fg.N) return nullptr;
@@ -189,47 +188,6 @@ __global__ __launch_bounds__(256) void k_tt_post(const float* __restrict__ fc, c
 __global__ void k_tt_relu_bwd(float* __restrict__ g, const float* __restrict__ act, int64_t count) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e < count && !(act[e] > 0.f)) g[e] = 0.f;
-}
-
-// LayerNorm backward + residual_fc dropout, one wave per row: dpre = rstd (g - mean(g) - xhat mean(g xhat)), g = dy gamma.  dpre reaches
-// the residual q_in (dqin) and, through the dropout mask, the residual_fc output (dfc); dyx = dy xhat feeds the gamma gradient.
-__global__ __launch_bounds__(256) void k_tt_ln_bwd(const float* __restrict__ dy, const float* __restrict__ pre, const float* __restrict__ mean_in,
-                                                     const float* __restrict__ rstd_in, const float* __restrict__ gamma, int64_t n, int Dq, train::Drop dr,
-                                                     uint32_t site, float* __restrict__ dfc, float* __restrict__ dqin, float* __restrict__ dyx) {
-    constexpr int NV = 5;
-    const int lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n) return;
-    const float mean = mean_in[i], rstd = rstd_in[i];
-    float xh[NV], g[NV];
-    float sg = 0.f, sgx = 0.f;
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-        const int f = lane + 64 * u;
-        xh[u] = g[u] = 0.f;
-        if (f < Dq) {
-            const size_t idx = (size_t)i * Dq + f;
-            xh[u] = (pre[idx] - mean) * rstd;
-            const float d = dy[idx];
-            g[u] = d * gamma[f];
-            dyx[idx] = d * xh[u];
-            sg += g[u];
-            sgx = fmaf(g[u], xh[u], sgx);
-        }
-    }
-    sg = wave_sum(sg) / (float)Dq;
-    sgx = wave_sum(sgx) / (float)Dq;
-    const uint32_t skey = dr.site_key(site);
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-        const int f = lane + 64 * u;
-        if (f < Dq) {
-            const uint64_t idx = (uint64_t)i * Dq + f;
-            const float d = rstd * (g[u] - sg - xh[u] * sgx);
-            dqin[idx] = d;
-            dfc[idx] = d * dr.mask32(skey, (uint32_t)idx + 0x27d4eb2fU * (uint32_t)(idx >> 32));
-        }
-    }
 }
 
 // Attention backward of row i (one wave per row, every head).  With dz_ih = W_v,h^T datt_ih:
@@ -533,9 +491,10 @@ int train_backward(hipStream_t s, const dygnn_tgat_config& cfg, const dygnn_tgat
             hipLaunchKernelGGL(k_tt_feat0_rows, dim3((unsigned)ceil_div(n * Fn, 256)), dim3(256), 0, s, F32(p.datt), ids_lower, n, Fn, fg);
             DYGNN_LAUNCH_CHECK();
         }
-        // 2. LayerNorm + residual + residual_fc dropout
-        hipLaunchKernelGGL(k_tt_ln_bwd, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, s, F32(p.dy), F32(v.pre), F32(v.mean), F32(v.rstd), Lw.ln_w, n, Dq, dr, site_o,
-                           F32(p.dfc), F32(p.dqin), F32(p.dyx));
+        // 2. LayerNorm + residual + residual_fc dropout (train_rows.h, Dq <= 272: five columns per lane): dpre reaches the residual q_in (dqin)
+        //    and, through the dropout mask, the residual_fc output (dfc); dyx = dy xhat feeds the gamma gradient
+        hipLaunchKernelGGL(train::k_res_ln_bwd<5>, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, s, F32(p.dy), F32(v.pre), F32(v.mean), F32(v.rstd), Lw.ln_w, n, Dq,
+                           train::RowMap{0, 0}, dr, site_o, F32(p.dqin), F32(p.dfc), F32(p.dyx));
         DYGNN_LAUNCH_CHECK();
         if (int rc = colsum(s, F32(p.dyx), Dq, n, Dq, F32(p.part), W(G.ln_w))) return rc;
         if (int rc = colsum(s, F32(p.dy), Dq, n, Dq, F32(p.part), W(G.ln_b))) return rc;

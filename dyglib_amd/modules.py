@@ -25,6 +25,26 @@ class TimeEncoder(nn.Module):
             self.w.bias.requires_grad = False
 
 
+class TransformerEncoder(nn.Module):
+    """Parameters of models/modules.py:209-231 (TCL's layers, CAWN's walk encoder)."""
+
+    def __init__(self, attention_dim: int, num_heads: int, dropout: float = 0.1):
+        super().__init__()
+        self.multi_head_attention = nn.MultiheadAttention(embed_dim=attention_dim, num_heads=num_heads, dropout=dropout)
+        self.dropout = nn.Dropout(dropout)
+        self.linear_layers = nn.ModuleList([nn.Linear(attention_dim, 4 * attention_dim), nn.Linear(4 * attention_dim, attention_dim)])
+        self.norm_layers = nn.ModuleList([nn.LayerNorm(attention_dim), nn.LayerNorm(attention_dim)])
+
+
+def fill_encoder_layer_weights(L, t: TransformerEncoder, p) -> None:
+    """The twelve pointers of a `dygnn_tcl_layer_weights` (_capi.TclLayerWeights) from a TransformerEncoder; `p` maps a parameter to the address
+    to store (its own data, or its gradient buffer's)."""
+    a = t.multi_head_attention
+    L.in_proj_w, L.in_proj_b, L.out_proj_w, L.out_proj_b = p(a.in_proj_weight), p(a.in_proj_bias), p(a.out_proj.weight), p(a.out_proj.bias)
+    L.fc0_w, L.fc0_b, L.fc1_w, L.fc1_b = p(t.linear_layers[0].weight), p(t.linear_layers[0].bias), p(t.linear_layers[1].weight), p(t.linear_layers[1].bias)
+    L.norm0_w, L.norm0_b, L.norm1_w, L.norm1_b = p(t.norm_layers[0].weight), p(t.norm_layers[0].bias), p(t.norm_layers[1].weight), p(t.norm_layers[1].bias)
+
+
 class _MergeFunction(torch.autograd.Function):
     """logits = fc2(relu(fc1(cat(x1, x2)))) for output_dim 1 with its backward pass on the HIP library: one launch forward
     (dygnn_merge_layer_logits), one launch backward (dygnn_merge_layer_backward: two launches on the matrix cores; the hidden layer is recomputed, nothing is kept)."""

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi
-from .modules import TimeEncoder
+from .modules import TimeEncoder, TransformerEncoder, fill_encoder_layer_weights      # TransformerEncoder: re-exported (it used to live here)
 from .neighbor_sampler import NeighborSampler
 from .tgat import _to_dev, _workspace
 
@@ -77,17 +77,6 @@ class _TclTrainFunction(torch.autograd.Function):
                                                   ctx.dropout_p, ctx.seed, ctx.ws.data_ptr(), ctx.ws.numel(), _capi.current_stream_ptr()))
         ctx.ws = ctx.feats = None
         return (None,) * 6 + tuple(grads)
-
-
-class TransformerEncoder(nn.Module):
-    """Parameters of models/modules.py:209-231."""
-
-    def __init__(self, attention_dim: int, num_heads: int, dropout: float = 0.1):
-        super().__init__()
-        self.multi_head_attention = nn.MultiheadAttention(embed_dim=attention_dim, num_heads=num_heads, dropout=dropout)
-        self.dropout = nn.Dropout(dropout)
-        self.linear_layers = nn.ModuleList([nn.Linear(attention_dim, 4 * attention_dim), nn.Linear(4 * attention_dim, attention_dim)])
-        self.norm_layers = nn.ModuleList([nn.LayerNorm(attention_dim), nn.LayerNorm(attention_dim)])
 
 
 class TCL(nn.Module):
@@ -227,12 +216,7 @@ class TCL(nn.Module):
         w.proj_edge_w, w.proj_edge_b = p(pl["edge"].weight), p(pl["edge"].bias)
         w.proj_time_w, w.proj_time_b = p(pl["time"].weight), p(pl["time"].bias)
         for l, t in enumerate(self.transformers):
-            L, a = w.layers[l], t.multi_head_attention
-            L.in_proj_w, L.in_proj_b, L.out_proj_w, L.out_proj_b = p(a.in_proj_weight), p(a.in_proj_bias), p(a.out_proj.weight), p(a.out_proj.bias)
-            L.fc0_w, L.fc0_b, L.fc1_w, L.fc1_b = (p(t.linear_layers[0].weight), p(t.linear_layers[0].bias), p(t.linear_layers[1].weight),
-                                                  p(t.linear_layers[1].bias))
-            L.norm0_w, L.norm0_b, L.norm1_w, L.norm1_b = (p(t.norm_layers[0].weight), p(t.norm_layers[0].bias), p(t.norm_layers[1].weight),
-                                                          p(t.norm_layers[1].bias))
+            fill_encoder_layer_weights(w.layers[l], t, p)
         w.output_w, w.output_b = p(self.output_layer.weight), p(self.output_layer.bias)
         return w
 
