@@ -11,7 +11,8 @@ from .synthetic import InteractionData  # noqa: F401
 __all__ = ["DyGFormer", "TGAT", "MemoryModel", "GraphMixer", "TCL", "CAWN", "MergeLayer", "TimeEncoder", "NeighborSampler", "get_neighbor_sampler", "TemporalCSR",
            "count_nodes_appearances", "InteractionData", "Data", "get_link_prediction_data",
            "get_link_prediction_metrics", "get_node_classification_metrics", "link_prediction_metrics_device",
-           "NegativeEdgeSampler", "get_idx_data_loader", "evaluate_model_link_prediction"]
+           "NegativeEdgeSampler", "get_idx_data_loader", "evaluate_model_link_prediction",
+           "edge_bank_link_prediction", "evaluate_edge_bank_link_prediction"]
 
 
 def __getattr__(name):
@@ -49,6 +50,9 @@ def __getattr__(name):
     if name in ("NegativeEdgeSampler", "get_idx_data_loader", "evaluate_model_link_prediction"):
         from . import evaluate
         return getattr(evaluate, name)
+    if name in ("edge_bank_link_prediction", "evaluate_edge_bank_link_prediction"):
+        from . import edgebank
+        return getattr(edgebank, name)
     if name == "TemporalCSR":
         from .temporal_csr import TemporalCSR
         return TemporalCSR

@@ -147,6 +147,10 @@ class CawnTaps(C.Structure):
     _fields_ = [("rows", C.c_int64)] + [(n, C.c_void_p) for n in ("walk_ids", "counts", "feature_out", "position_out", "attn_in", "attn_out")]
 
 
+class EdgeBank(C.Structure):
+    _fields_ = [("buffer", C.c_void_p), ("buffer_bytes", C.c_size_t), ("max_edges", C.c_int64), ("num_edges", C.c_int64)]
+
+
 class DygformerTaps(C.Structure):
     _fields_ = [("seq_lens", C.c_void_p), ("encoder_input", C.c_void_p), ("layer_out", C.c_void_p * DYGNN_MAX_LAYERS),
                 ("phase_cycles", C.c_void_p), ("ev_kernel_start", C.c_void_p), ("ev_kernel_stop", C.c_void_p)]
@@ -269,6 +273,14 @@ SIGNATURES = {
     "dygnn_link_metrics_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "dygnn_link_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dygnn_edgebank_table_bytes": (C.c_size_t, [C.c_int64]),
+    "dygnn_edgebank_home_slot": (C.c_uint64, [C.c_int64, C.c_int64, C.c_int64]),
+    "dygnn_edgebank_reset": (C.c_int, [C.POINTER(EdgeBank), C.c_void_p]),
+    "dygnn_edgebank_insert": (C.c_int, [C.POINTER(EdgeBank), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "dygnn_edgebank_query": (C.c_int, [C.POINTER(EdgeBank), C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_double, C.c_void_p, C.c_void_p,
+                                       C.c_int64, C.c_void_p, C.c_void_p]),
+    "dygnn_edgebank_evaluate": (C.c_int, [C.POINTER(EdgeBank), C.c_void_p, C.c_void_p, C.c_void_p, c_i64p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -746,6 +746,51 @@ int dygnn_link_metrics(const float* predicts, const float* labels, int64_t group
                        double* average_precision, double* roc_auc, double* bce_loss, int32_t* status,
                        void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * EdgeBank (models/EdgeBank.py:7-121; evaluated at evaluate_models_utils.py:303-350): a directed edge (src, dst) scores 1.0 if its pair is
+ * in memory and 0.0 otherwise.  The history is a persistent hash table on the device that grows by position ranges of one edge list
+ * (src / dst int64, times float64, device arrays; position = index in them), so an evaluation inserts each edge once instead of
+ * rebuilding a set per batch.  Layout, hash and the argument for run-to-run bit-identical state: dyglib_amd/csrc/edgebank.hip.
+ *
+ * The caller owns the table: `buffer` is device memory of dygnn_edgebank_table_bytes(max_edges) bytes (0 = max_edges refused: negative or
+ * above 2^30), `num_edges` is written by reset / insert / evaluate and read by the checks (H against the edges inserted), all on the host.
+ * Ids must lie in [0, 2^31): the caller checks (the Python layer raises ValueError); the kernels skip other ids and set bit 0 of the int32
+ * word at byte 32 of the buffer (bit 1: table overfilled, bit 2: an inserted key was not found again; both impossible within max_edges).
+ *
+ * memory mode 0 unlimited_memory: the pair occurs in the history.  1 repeat_threshold_memory: count(pair) >= H / D in float64, D = distinct
+ * pairs.  2 time_window_memory: max time of the pair >= start, with window mode 0 fixed_proportion: start = start_time, which the caller
+ * computes (np.quantile(times[:H], 1 - proportion), EdgeBank.py:52), or 1 repeat_interval: start = max(times) - S / D computed on the device,
+ * S = sum over pairs with n > 1 occurrences of (t[last position] - t[first position]) / (n - 1) (EdgeBank.py:56-68, the mean of consecutive
+ * differences telescoped).  The window mode is looked at in memory mode 2 only.  Mode 2 on an empty history is refused (the reference's
+ * max() of an empty sequence raises ValueError).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct dygnn_edgebank {
+    void*   buffer;         /* device, dygnn_edgebank_table_bytes(max_edges) bytes              */
+    size_t  buffer_bytes;
+    int64_t max_edges;      /* the most edges the table will ever hold                          */
+    int64_t num_edges;      /* edges inserted so far = the history length H the table answers for */
+} dygnn_edgebank;
+
+size_t dygnn_edgebank_table_bytes(int64_t max_edges);
+/* Home slot of a pair in a table for max_edges (host; UINT64_MAX for refused arguments): what tests use to build colliding keys. */
+uint64_t dygnn_edgebank_home_slot(int64_t src, int64_t dst, int64_t max_edges);
+/* Empties the table (two memsets on `stream`). */
+int dygnn_edgebank_reset(dygnn_edgebank* table_host, dygnn_stream_t stream);
+/* Inserts positions [first, last) of the edge arrays; first must equal table_host->num_edges (the table holds a prefix). */
+int dygnn_edgebank_insert(dygnn_edgebank* table_host, const int64_t* src, const int64_t* dst, const double* times, int64_t first,
+                          int64_t last, dygnn_stream_t stream);
+/* out[i] = score of (q_src[i], q_dst[i]) against the H = table_host->num_edges edges inserted (another H is refused).  `times` = the edge
+ * list's times, needed by repeat_interval only.  Never inserts. */
+int dygnn_edgebank_query(const dygnn_edgebank* table_host, const double* times, int32_t mode, int32_t window_mode, int64_t H,
+                         double start_time, const int64_t* q_src, const int64_t* q_dst, int64_t n, float* out, dygnn_stream_t stream);
+/* A whole evaluation with no host synchronisation: for batch b, insert the edges up to hist_len_host[b] (non-decreasing, starting at or above
+ * table_host->num_edges), then score its queries q_src / q_dst [n_batches, queries_per_batch] into out (same shape) with
+ * start_times[b] (device, [n_batches]; fixed_proportion only, else may be NULL). */
+int dygnn_edgebank_evaluate(dygnn_edgebank* table_host, const int64_t* src, const int64_t* dst, const double* times,
+                            const int64_t* hist_len_host, const double* start_times, const int64_t* q_src, const int64_t* q_dst,
+                            int64_t n_batches, int64_t queries_per_batch, int32_t mode, int32_t window_mode, float* out,
+                            dygnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
