@@ -25,6 +25,17 @@ static int check_weights(const Dims& d, const dygnn_dygformer_weights* w) {
     return DYGNN_OK;
 }
 
+// The head's ReLU: a NaN pre-activation stays NaN as in torch.relu (fmaxf(x, 0) would turn a diverged model's NaN embeddings into
+// sigmoid(fc2.bias), a normal-looking score).  Forward kernels only.  IEEE 754-2019 maximum is one v_maximum3_f32 on gfx950; the select
+// form is a compare and a v_cndmask.
+__device__ __forceinline__ float relu_nan(float x) {
+#if __has_builtin(__builtin_elementwise_maximum)
+    return __builtin_elementwise_maximum(x, 0.f);
+#else
+    return x < 0.f ? 0.f : x;
+#endif
+}
+
 // sigmoid(fc2(relu(fc1(cat(a,b)))))   models/modules.py:57-68 + evaluate_models_utils.py:140-141
 __global__ __launch_bounds__(256) void k_merge_sigmoid(const float* __restrict__ a, const float* __restrict__ b, int dim, int hidden,
                                                          const float* __restrict__ w1, const float* __restrict__ b1,
@@ -41,8 +52,7 @@ __global__ __launch_bounds__(256) void k_merge_sigmoid(const float* __restrict__
         float acc = 0.f;
         const float* wr = w1 + (size_t)j * 2 * dim;
         for (int k = 0; k < 2 * dim; ++k) acc = fmaf(x[k], wr[k], acc);
-        acc = fmaxf(acc + b1[j], 0.f);
-        part = fmaf(acc, w2[j], part);
+        part = fmaf(relu_nan(acc + b1[j]), w2[j], part);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
@@ -95,7 +105,7 @@ __global__ __launch_bounds__(256) void k_merge_sigmoid_mfma(const float* __restr
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int n = n0 + 16 * i + 4 * g + r;
-                if (n < hidden) z = fmaf(fmaxf(acc[i][r] + b1[n], 0.f), w2[n], z);
+                if (n < hidden) z = fmaf(relu_nan(acc[i][r] + b1[n]), w2[n], z);
             }
     }
     z += __shfl_xor(z, 16, 64);
@@ -126,7 +136,8 @@ __global__ __launch_bounds__(1024) void k_merge_sigmoid_rows4(const float* __res
     const int64_t r0 = (int64_t)blockIdx.x * R;
     const int n_lane = 16 * wave + 4 * ng + j;
     const bool rowok = n_lane < hidden;
-    const float* wp = w1 + (size_t)(rowok ? n_lane : 0) * K + 4 * ks;
+    // a lane whose k-slice lies beyond a short row (K = 8: ks = 2, 3) multiplies zeros; its loads stay at the start of its row, inside fc1
+    const float* wp = w1 + (size_t)(rowok ? n_lane : 0) * K + (4 * ks < K ? 4 * ks : 0);
     constexpr int PF = 4;
     mf4 ring[PF];
 #pragma unroll
@@ -172,7 +183,7 @@ __global__ __launch_bounds__(1024) void k_merge_sigmoid_rows4(const float* __res
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int n = 16 * wave + 4 * ng + e;
-            if (n < hidden) z = fmaf(fmaxf(acc[m][e] + b1[n], 0.f), w2[n], z);
+            if (n < hidden) z = fmaf(relu_nan(acc[m][e] + b1[n]), w2[n], z);
         }
         z += __shfl_xor(z, 16, 64);
         z += __shfl_xor(z, 32, 64);
@@ -447,35 +458,52 @@ extern "C" int dygnn_dygformer_forward(const dygnn_dygformer_config* cfg, const 
                                           workspace, workspace_bytes, taps, impl, stream, 0);
 }
 
+// Which forward kernel a call takes: 0 = G (k_merge_sigmoid, one workgroup per row), 1 = R1 (k_merge_sigmoid_rows4<1>, 4 rows per workgroup),
+// 2 = R4 (k_merge_sigmoid_rows4<4>, 16 rows), 3 = M (k_merge_sigmoid_mfma, one wave per 16 rows).  The row-block forms stage R rows of cat(a, b)
+// in LDS: the widest one that fits is taken, a size that fits none falls through to M (no LDS) and G (one row), so every (dim, hidden) whose
+// single row G can stage (2 dim + 4 floats within 64 KB) is answered at every n.  (M also takes longer rows, from 2048 rows on.)
+static int64_t merge_ldx(int64_t dim) { const int64_t k16 = (2 * dim + 15) & ~(int64_t)15; return (k16 & 16) ? k16 : k16 + 16; }      // row stride % 32 == 16: the four rows on distinct banks
+static size_t merge_rows_lds(int R, int64_t dim, int64_t hidden) { return ((size_t)R * (size_t)merge_ldx(dim) + (size_t)R * (size_t)((hidden + 15) / 16)) * sizeof(float); }
+constexpr size_t kMergeLdsMax = 64 * 1024;
+
+extern "C" int32_t dygnn_merge_layer_forward_path(int64_t n, int32_t dim, int32_t hidden) {
+    DYGNN_REQUIRE(n >= 0 && dim > 0 && hidden > 0, "merge_layer: bad sizes");
+    DYGNN_REQUIRE(dim <= (INT32_MAX - 16) / 2, "merge_layer: dim too large");      // the kernels index a row's 2 dim features, rounded up to 16, in int
+    const bool vec = dim % 4 == 0;
+    if (vec && hidden <= 256 && n >= 64) {      // an evaluation step's worth of rows (4 per workgroup) or thousands of them (16 per workgroup)
+        if (n >= 2048 && merge_rows_lds(16, dim, hidden) <= kMergeLdsMax) return 2;
+        if (merge_rows_lds(4, dim, hidden) <= kMergeLdsMax) return 1;
+    }
+    if (vec && n >= 2048) return 3;             // hidden > 256, or rows too long to stage: the wave-per-16-rows form
+    DYGNN_REQUIRE((size_t)(2 * (int64_t)dim + 4) * sizeof(float) <= kMergeLdsMax, "merge_layer: dim too large");
+    return 0;
+}
+
 static int merge_forward(const float* a, const float* b, int64_t n, int32_t dim, int32_t hidden, const float* fc1_w, const float* fc1_b, const float* fc2_w,
                          const float* fc2_b, float* out, int sig, dygnn_stream_t stream) {
     DYGNN_REQUIRE(n >= 0 && dim > 0 && hidden > 0, "merge_layer: bad sizes");
     DYGNN_REQUIRE(n == 0 || (a && b && fc1_w && fc1_b && fc2_w && fc2_b && out), "merge_layer: null pointer");
     if (n == 0) return DYGNN_OK;
-    if (dim % 4 == 0 && hidden <= 256 && n >= 64) {     // an evaluation step's worth of rows (4 per workgroup) or thousands of them (16 per workgroup)
-        const int tiles = (hidden + 15) / 16, k16 = (2 * dim + 15) & ~15, ldx = (k16 & 16) ? k16 : k16 + 16;      // row stride % 32 == 16: the four rows on distinct banks
-        const int R = n >= 2048 ? 16 : 4;
-        const size_t lds4 = ((size_t)R * ldx + (size_t)R * tiles) * sizeof(float);
-        DYGNN_REQUIRE(lds4 <= 64 * 1024, "merge_layer: dim too large");
-        if (R == 16)
-            hipLaunchKernelGGL(k_merge_sigmoid_rows4<4>, dim3((unsigned)ceil_div(n, 16)), dim3(64 * tiles), lds4, as_stream(stream), a, b, n, dim, hidden,
-                               fc1_w, fc1_b, fc2_w, fc2_b, out, sig, ldx);
-        else
-            hipLaunchKernelGGL(k_merge_sigmoid_rows4<1>, dim3((unsigned)ceil_div(n, 4)), dim3(64 * tiles), lds4, as_stream(stream), a, b, n, dim, hidden,
-                               fc1_w, fc1_b, fc2_w, fc2_b, out, sig, ldx);
-        DYGNN_LAUNCH_CHECK();
-        return DYGNN_OK;
-    }
-    if (dim % 4 == 0 && n >= 2048) {        // (hidden > 256) the wave-per-16-rows form
+    const int path = dygnn_merge_layer_forward_path(n, dim, hidden);
+    if (path < 0) return path;
+    const int tiles = (hidden + 15) / 16, ldx = (int)merge_ldx(dim);
+    switch (path) {
+    case 2:
+        hipLaunchKernelGGL(k_merge_sigmoid_rows4<4>, dim3((unsigned)ceil_div(n, 16)), dim3(64 * tiles),
+                           merge_rows_lds(16, dim, hidden), as_stream(stream), a, b, n, dim, hidden, fc1_w, fc1_b, fc2_w, fc2_b, out, sig, ldx);
+        break;
+    case 1:
+        hipLaunchKernelGGL(k_merge_sigmoid_rows4<1>, dim3((unsigned)ceil_div(n, 4)), dim3(64 * tiles),
+                           merge_rows_lds(4, dim, hidden), as_stream(stream), a, b, n, dim, hidden, fc1_w, fc1_b, fc2_w, fc2_b, out, sig, ldx);
+        break;
+    case 3:
         hipLaunchKernelGGL(k_merge_sigmoid_mfma, dim3((unsigned)ceil_div(n, 64)), dim3(256), 0, as_stream(stream), a, b, n, dim, hidden,
                            fc1_w, fc1_b, fc2_w, fc2_b, out, sig);
-        DYGNN_LAUNCH_CHECK();
-        return DYGNN_OK;
+        break;
+    default:
+        hipLaunchKernelGGL(k_merge_sigmoid, dim3((unsigned)n), dim3(256), (size_t)(2 * dim + 4) * sizeof(float), as_stream(stream), a, b, dim, hidden, fc1_w,
+                           fc1_b, fc2_w, fc2_b, out, sig);
     }
-    const size_t lds = (size_t)(2 * dim + 4) * sizeof(float);
-    DYGNN_REQUIRE(lds <= 64 * 1024, "merge_layer: dim too large");
-    hipLaunchKernelGGL(k_merge_sigmoid, dim3((unsigned)n), dim3(256), lds, as_stream(stream), a, b, dim, hidden, fc1_w, fc1_b, fc2_w,
-                       fc2_b, out, sig);
     DYGNN_LAUNCH_CHECK();
     return DYGNN_OK;
 }

@@ -463,6 +463,11 @@ int dygnn_tgn_backward(const dygnn_tgat_config* cfg_host, const dygnn_tgat_weigh
 int dygnn_merge_layer_sigmoid(const float* a, const float* b, int64_t n, int32_t dim, int32_t hidden,
                               const float* fc1_w, const float* fc1_b, const float* fc2_w, const float* fc2_b,
                               float* out, dygnn_stream_t stream);
+/* Which forward kernel dygnn_merge_layer_sigmoid / dygnn_merge_layer_logits run for these sizes (host only, nothing is launched):
+ * 0 = one workgroup per row, 1 = 4 rows per workgroup, 2 = 16 rows per workgroup, 3 = one wave per 16 rows on the matrix cores;
+ * < 0 = the sizes are refused (DYGNN_E_INVALID, message in dygnn_last_error).  The forward takes any dim and hidden whose single row
+ * (2 dim + 4 floats) fits 64 KB of LDS, at every n. */
+int32_t dygnn_merge_layer_forward_path(int64_t n, int32_t dim, int32_t hidden);
 /* The same head for the TRAINING step (train_link_prediction.py:241-257): the logits z = MergeLayer(a, b) [n] (output_dim 1) and their
  * backward pass.  grad_logits = dL/dz [n]; grad_a, grad_b [n,dim] are written; the four parameter gradients are ACCUMULATED into buffers the
  * caller has zeroed; `workspace` = n * hidden floats, 16-byte aligned like a and b.  dim and hidden multiples of 4, hidden <= 192. */
