@@ -5,6 +5,14 @@
 
 namespace dygnn {
 
+namespace v3 {
+// the packed form (fused3_body, PK): untapped launches of pairs of <= 64 tokens that defer their tail.  A kernel name of its own: the
+// template list of k_dygformer_fused3 is what the resource tests match.
+__global__ __launch_bounds__(512, 2) void k_dygformer_fused3_packed(const Args a) {
+    fused3_body<4, false, 8, 3, true>(a);
+}
+}  // namespace v3
+
 // table_flags (dygnn_dygformer_forward_tables): the stored fragment sequence is [node | time | edge | cooc], every channel in whole
 // groups of four slots (build_proj).  A channel whose table is all zero leaves the walk: its chunk count becomes 0 and the prologue's
 // DMA steps over its stored fragments.
@@ -41,7 +49,14 @@ int forward_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_
     // workgroups on PL = 3 followed by k_pooled_tail, which gives the same bits (dygformer_pooled_tail.hip).
     const bool tap_last = taps && taps->layer_out[d.NL - 1] != nullptr;
     if (!tap_last) { a.stream = packed + pl.fused3 + f.stream_p; a.nstages = f.nstages_p; }
-    const bool small = f.np == 2 && a.pair_stride == 0 && B <= kSmallBatchPairs && !small_off();      // a small call: one pair per four-wave workgroup
+    // The packed form (fused3_plan.h): untapped launches of pairs of <= 64 tokens.  By default wherever the tail is deferred; DYGNN_PACK_PAIRS = 1
+    // puts every such launch on it, a small one included (and defers its tail), 0 none.
+    bool untapped = !tap_last && !(taps && (taps->encoder_input || taps->phase_cycles));
+    for (int l = 0; l < d.NL; ++l) untapped = untapped && !(taps && taps->layer_out[l]);
+    const int pk_env = pack_pairs_env();
+    const size_t plan_off = plan_offset(B, G);       // 0: the workspace has no room for this call's plan (dygformer_layout.h)
+    const bool pack_ok = untapped && f.np == 2 && f.scr_floats8 > 0 && B <= INT32_MAX && plan_off > 0 && pk_env != 0;
+    const bool small = f.np == 2 && a.pair_stride == 0 && B <= kSmallBatchPairs && !small_off() && !(pack_ok && pk_env == 1);      // a small call: one pair per four-wave workgroup
     const unsigned grid = small || f.np != 2 ? (unsigned)B : (unsigned)(a.pair_stride ? a.pair_stride : (B + 1) / 2);
     auto launch = [&](auto kern, unsigned threads) -> int {
         // per device and cheap: set on every call (a process may drive several GPUs, or call from several threads)
@@ -49,9 +64,18 @@ int forward_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_
         hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), kLdsBytes, s, a);
         return DYGNN_OK;
     };
-    const bool tail = !tap_last && pooled_tail_wanted(grid);
+    // (the size rule looks at the UNPACKED workgroup count: a launch keeps its form whatever the plan makes of it)
+    const bool tail = !tap_last && (pooled_tail_wanted(grid) || (pack_ok && pk_env == 1));
+    const bool pack_it = pack_ok && !small && tail;
     int rc;
-    if (tail) rc = small ? launch(k_dygformer_fused3<4, false, 4, 3>, 256) : f.np == 2 ? launch(k_dygformer_fused3<4, false, 8, 3>, 512) : launch(k_dygformer_fused3<8, false, 8, 3>, 512);
+    if (pack_it) {
+        // the plan is part of the launch: inside the timed pair of events, on the same stream, no host synchronisation.  The grid stays the
+        // unpacked one (the plan never needs more); workgroups beyond the plan's count return at once.
+        if (int rcp = pack_plan_device(d, B, G, ws, wl, s)) return rcp;
+        a.plan = reinterpret_cast<const int32_t*>(ws + wl.dims + plan_off);
+        a.pair_stride = 0; a.scr_floats = f.scr_floats8; a.slab_chunks = f.slab_chunks8; a.tab_off = 0; a.tab_slots = 0; a.tab_bits = 0;
+        rc = launch(k_dygformer_fused3_packed, 512);
+    } else if (tail) rc = small ? launch(k_dygformer_fused3<4, false, 4, 3>, 256) : f.np == 2 ? launch(k_dygformer_fused3<4, false, 8, 3>, 512) : launch(k_dygformer_fused3<8, false, 8, 3>, 512);
     else if (small) rc = tap_last ? launch(k_dygformer_fused3<4, false, 4, 2>, 256) : launch(k_dygformer_fused3<4, false, 4, 1>, 256);
     else if (f.np == 2) rc = tap_last ? launch(k_dygformer_fused3<4, false, 8, 2>, 512) : launch(k_dygformer_fused3<4, false, 8, 1>, 512);
     else rc = tap_last ? launch(k_dygformer_fused3<8, false, 8, 2>, 512) : launch(k_dygformer_fused3<8, false, 8, 1>, 512);

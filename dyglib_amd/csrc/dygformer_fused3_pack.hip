@@ -274,6 +274,7 @@ PackLayout3 make_layout3(const Dims& d) {
     // prologue LDS split: pairs per workgroup, window arrays (5 x 2 sides x Smax ints per pair), projection slab
     const int per_pair = 5 * 2 * ((d.Smax + 3) & ~3);
     f.np = 0; f.slab_in_ring = 0; f.scr_floats = 0; f.slab_chunks = 0; f.tab_off = 0; f.tab_slots = 0; f.tab_bits = 0;
+    f.scr_floats8 = 0; f.slab_chunks8 = 0;
     if (d.Tmax <= 64 && 2 * per_pair + 8 * 4 * kFrag <= kScratchFloats) f.np = 2;
     else if (d.Tmax <= 128 && per_pair + 8 * 4 * kFrag <= kScratchFloats) f.np = 1;
     else if (d.Tmax <= 128 && per_pair <= kScratchFloats) { f.np = 1; f.slab_in_ring = 1; }
@@ -288,6 +289,11 @@ PackLayout3 make_layout3(const Dims& d) {
         int bits = 0;
         while ((2 << (bits + 1)) <= words) ++bits;          // slots = 2^bits, two words per slot
         if (positions >= 512 && (1 << bits) >= 2 * positions) { f.tab_slots = 1 << bits; f.tab_bits = bits; }
+        // the packed kernel: up to eight pairs per workgroup, counts by the scan (short windows only), the slab behind eight sets of arrays
+        if (f.np == 2 && positions < 512 && 8 * per_pair + 8 * 4 * kFrag <= kScratchFloats) {
+            f.scr_floats8 = 8 * per_pair;
+            f.slab_chunks8 = (kScratchFloats - f.scr_floats8) / (4 * kFrag) / 8 * 4;
+        }
     }
     f.total = o;
     return f;

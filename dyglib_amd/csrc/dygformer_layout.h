@@ -76,13 +76,24 @@ struct CallDims { int32_t maxw_s, maxw_d, S_s, S_d, T_s, T_d, T, pad; };
 
 // ---- workspace (byte offsets) -------------------------------------------------------------------
 struct WorkspaceLayout {
-    size_t dims;        // CallDims[groups]: max_window_src, max_window_dst, S_s, S_d, T_s, T_d, T, -
+    size_t dims;        // CallDims[groups]: max_window_src, max_window_dst, S_s, S_d, T_s, T_d, T, -.  One slot per PAIR is reserved; behind the
+                        // slots of the call's groups a packed fused launch keeps its plan (plan_offset below)
     size_t hist_len;    // int32[2B]
     size_t end_pos;     // int64[2B]
     size_t pooled;      // float[2B][4 D + D padded to 16]: per-side token means of a fused launch whose epilogue is deferred (k_pooled_tail)
     size_t X, Xn, QKV, Hid;   // generic path activations, token stride Tmax
     size_t total;
 };
+
+// The packing plan of a packed fused launch (fused3_plan.h: one int32 pair id per wave of ceil(B / 2) workgroups = 32 B per workgroup)
+// lives in the part of the `dims` section that the call's groups leave free: the section reserves a CallDims per pair, a call of
+// groups of G >= 2 pairs uses at most half of them.  Returns its byte offset from the section's start, or 0 where it does not fit
+// (one group per pair; an odd batch of groups of two whose section has no padding left): such a launch is not packed.
+inline size_t plan_offset(int64_t B, int64_t G) {
+    const size_t section = (((size_t)(B > 0 ? B : 1) * sizeof(CallDims)) + 255) & ~size_t(255);
+    const size_t groups = (size_t)((B + G - 1) / G) * sizeof(CallDims), plan = (size_t)((B + 1) / 2) * 8 * sizeof(int32_t);
+    return groups + plan <= section ? groups : 0;
+}
 
 inline WorkspaceLayout make_workspace_layout(const Dims& d, int64_t B) {
     WorkspaceLayout w;

@@ -428,6 +428,29 @@ __device__ __forceinline__ void s_like(f4 (&sa)[TPW], const float* base, const f
         }
     }
 }
+// the first N <= 4 row tiles only (the packed forward: a pair of N token tiles); every sa[kt] is the chain s_like runs for it
+template <int N>
+__device__ __forceinline__ void s_like_n(f4 (&sa)[4], const float* base, const f4 (&q)[7], int c, int g) {
+    static_assert(N >= 1 && N <= 4, "one chunk of row tiles");
+    const float q6 = kpack4(q[6]);
+    const float* kbase = base + c * kKV + 4 * g;
+    f4 kf[2][N];
+#pragma unroll
+    for (int kt = 0; kt < N; ++kt) kf[0][kt] = lds4(kbase + 16 * kt * kKV);
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        if (j + 1 < 6) {
+#pragma unroll
+            for (int kt = 0; kt < N; ++kt) kf[(j + 1) & 1][kt] = lds4(kbase + 16 * kt * kKV + 16 * (j + 1));
+        } else if (j + 1 == 6) {
+#pragma unroll
+            for (int kt = 0; kt < N; ++kt) kf[0][kt].x = kbase[16 * kt * kKV + 96 - 3 * g];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (j == 6) mma_group1<N>(&sa[0], kf[0], q6); else mma_group<N>(&sa[0], kf[j & 1], q[j]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
 template <int TPW>
 __device__ __forceinline__ void pv_like(f4 (&oa)[7], const float* base, const f4 (&p)[TPW], int c, int g) {     // oa += rows(base)^T . p   (forward: O^T = V^T P^T)
     // the rows as the A operand: sub-steps (row tile kt, d-tiles 0..3 | 4..6), read one sub-step ahead (8 fragments live, not 14)

@@ -6,6 +6,7 @@
 #include "dropout.h"
 #include "fused3_device.h"
 #include "fused3_host.h"
+#include "fused3_plan.h"
 
 namespace dygnn {
 namespace v3 {
@@ -34,6 +35,7 @@ struct Args {
     LayerP layer[DYGNN_MAX_LAYERS];
     const float *outT, *outb;     // output layer: transposed [200][Fn], bias [Fn]
     float *out_src, *out_dst;
+    const int32_t* plan;          // packed form: the pair of every wave, [workgroup][8] (fused3_plan.h; workspace)
     float* pooled_rows;           // deferred epilogue (PL = 3): [2 B][kPoolRow] token means, row 2 * pair + side (workspace)
     float* tap_enc; float* tap_layer[DYGNN_MAX_LAYERS];
     unsigned long long* stamps;
@@ -55,14 +57,22 @@ __device__ __forceinline__ void gelu_tiles(f4 (&t)[2]) {
     }
 }
 template <int TPW>
-__device__ __forceinline__ void tap_store(const f4 (&x)[kNT], float* base, int64_t b, int Tmax, int T, int tt, int c, int g) {
+__device__ __forceinline__ void tap_store(const f4 (&x)[kNT], float* base, int64_t b, int Tmax, const TokOrder& o, int tt, int c, int g) {
     if (base == nullptr) return;
     const int tok = 16 * tt + c;
-    if (tok >= T) return;
+    if (tok >= o.T) return;
+    auto put = [&](int row) {
 #pragma unroll
-    for (int i = 0; i < kNT; ++i) {
-        const int n = 16 * i + 4 * g;
-        if (n < kD) *reinterpret_cast<f4*>(base + ((size_t)b * Tmax + tok) * kD + n) = x[i];
+        for (int i = 0; i < kNT; ++i) {
+            const int n = 16 * i + 4 * g;
+            if (n < kD) *reinterpret_cast<f4*>(base + ((size_t)b * Tmax + row) * kD + n) = x[i];
+        }
+    };
+    // rows of the padded [B][Tmax] layout: source token k -> k, destination token k -> Tsf + k, the padding token -> every padding row
+    if (tok != o.padtok) put(tok < o.Ts ? tok : o.Tsf + (tok - o.Ts));
+    else {
+        for (int row = o.Ts; row < o.Tsf; ++row) put(row);
+        for (int row = o.Tsf + (o.padtok - o.Ts); row < o.Tf; ++row) put(row);
     }
 }
 
@@ -103,11 +113,12 @@ __device__ __forceinline__ void residual_dropped(f4 (&x)[kNT], const float* xin,
 }
 
 // per-side sums over the 16 tokens of this wave's tile of the 13 register tiles: pool[wave][side][208] (lane c == 0 of every row stores)
-__device__ __forceinline__ void pool_sides(const f4 (&x)[kNT], float* pool, int wave, int c, int g, bool in_src, bool in_dst) {
+// wsrc / wdst: how often this lane's token counts on either side (0, 1, or the padding token's multiplicity; x * 1 is x)
+__device__ __forceinline__ void pool_sides(const f4 (&x)[kNT], float* pool, int wave, int c, int g, float wsrc, float wdst) {
 #pragma unroll
     for (int i = 0; i < kNT; ++i) {
-        f4 vs = in_src ? x[i] : zero4();
-        f4 vd = in_dst ? x[i] : zero4();
+        f4 vs = wsrc != 0.f ? x[i] * wsrc : zero4();
+        f4 vd = wdst != 0.f ? x[i] * wdst : zero4();
 #pragma unroll
         for (int r = 0; r < 4; ++r) { vs[r] = row_sum16_dpp(vs[r]); vd[r] = row_sum16_dpp(vd[r]); }
         if (c == 0) {
@@ -138,46 +149,100 @@ static_assert(8 * 2 * kHid <= kLdsV && kLdsMeanG + 4 * kHid <= kLdsRing, "the po
 //      PL = 1 bit for bit — and, for the tap alone, the per-token W2 product from the full stream
 //   3  the deferred form of 1 for large launches: the kernel ends with the token means, written as dense rows (Args.pooled_rows) instead of
 //      LDS columns; k_pooled_tail (dygformer_pooled_tail.hip) runs the W2 product and the output layer once per launch, same chains
-template <int TPW, bool TR, int NW = 8, int PL = 0>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(const Args a) {
+// PK (inference, deferred tail only): the PACKED form.  A workgroup's eight waves hold up to eight pairs of 1 .. 4 token tiles each, as the
+// plan kernel (dygformer_pack_plan.hip) laid them out: every wave reads its (pair, first wave, tiles) from Args.plan.  The arithmetic per
+// pair is that of the unpacked kernels, chain for chain: a pair's bits do not depend on the form that computed it.
+template <int TPW, bool TR, int NW, int PL, bool PK>
+__device__ __forceinline__ void fused3_body(const Args& a) {
     static_assert(!(TR && PL != 0), "the training forward keeps the per-token form: its backward reads the per-token activations");
-    constexpr int NP = NW / TPW;                 // pairs per workgroup
-    constexpr int PT = 64 * NW / NP;             // threads per pair
+    static_assert(!PK || (TPW == 4 && NW == 8 && PL == 3 && !TR), "the packed form: eight waves, pairs of <= 64 tokens, deferred tail");
+    constexpr int NP = PK ? 8 : NW / TPW;        // pairs per workgroup (packed: at most)
     constexpr int NTHR = 64 * NW;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int pi = wave / TPW, tt = wave % TPW;
     const int c = lane & 15, g = lane >> 4;
-    const bool paired = NP == 2 && a.pair_stride > 0;
-    const int64_t b = paired ? (int64_t)blockIdx.x + pi * a.pair_stride : (int64_t)blockIdx.x * NP + pi;
-    const bool pair_ok = paired ? blockIdx.x < a.pair_stride && b < a.B : b < a.B;
-    const int ptid = tid - pi * PT;
+    const bool paired = !PK && NP == 2 && a.pair_stride > 0;
+    int pi, tt, nwv, PT;                         // pair slot, token tile, waves of this pair, threads of this pair
+    int64_t b;
+    bool pair_ok;
+    if constexpr (PK) {
+        // the eight entries of this workgroup (fused3_plan.h): this wave's pair, its first wave = the first entry that names it, its tiles = how many do
+        const int32_t* e = a.plan + (size_t)blockIdx.x * 8;
+        int pr = -1, any = -1;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int id = __builtin_amdgcn_readfirstlane(e[j]);
+            pr = j == wave ? id : pr;
+            any = id >= 0 ? id : any;
+        }
+        if (any < 0) return;                     // the grid is the unpacked one: a workgroup beyond the plan's count
+        int first = 8, cnt = 0;
+#pragma unroll
+        for (int j = 7; j >= 0; --j) {
+            const bool same = __builtin_amdgcn_readfirstlane(e[j]) == pr;
+            first = same ? j : first;
+            cnt += same ? 1 : 0;
+        }
+        pair_ok = pr >= 0;
+        b = pair_ok ? pr : 0;
+        pi = pair_ok ? first : wave;             // the pair's first wave names its slot
+        nwv = pair_ok ? cnt : 1;
+        tt = wave - pi;
+        PT = 64 * nwv;
+    } else {
+        pi = wave / TPW; tt = wave % TPW; nwv = TPW; PT = 64 * NW / NP;
+        b = paired ? (int64_t)blockIdx.x + pi * a.pair_stride : (int64_t)blockIdx.x * NP + pi;
+        pair_ok = paired ? blockIdx.x < a.pair_stride && b < a.B : b < a.B;
+    }
+    const int wave0 = PK ? pi : pi * TPW;        // this pair's first wave
+    const int ptid = tid - 64 * wave0;
 
     TDECL;
     CallDims cd{};
     if (pair_ok) cd = a.cd[b / a.G];
-    const int Ss = cd.S_s, Sd = cd.S_d, Ts = cd.T_s, T = cd.T;
+    const int Ss = cd.S_s, Sd = cd.S_d, Tsf = cd.T_s, Tf = cd.T;
+    // Inference computes every DISTINCT token once.  A patch made of padding positions only has a constant encoder input, so all such
+    // tokens of a pair stay identical through every layer: the pair runs its real source tokens, its real destination tokens and ONE
+    // padding token (order: source, destination, padding), whose softmax weight as a key and whose share of the per-side means count
+    // it m_s + m_d and m_s / m_d times.  Ts, T: source tokens and tokens of the compact order; Tsf, Tf: of the padded call (divisors, taps).
+    int Ts = Tsf, T = Tf, ms = 0, md = 0;
+    if constexpr (!TR) {
+        if (pair_ok) {
+            const PairTokens pk = pair_tokens(a.hist_len[b], a.hist_len[a.B + b], a.L, a.P, Tsf, Tf - Tsf);
+            Ts = pk.Rs; T = pk.Tc; ms = pk.ms; md = pk.md;
+        }
+    }
+    const int padtok = ms + md > 0 ? T - 1 : -1; // the padding token (compact order), or none
     const int SsA = (Ss + 3) & ~3, SdA = (Sd + 3) & ~3, SA = SsA + SdA;
-    const bool active = 16 * tt < T;             // wave-uniform: this token tile holds real tokens
-    const int tokbase = pi * (16 * TPW);         // this pair's first K/V row
+    const bool active = pair_ok && 16 * tt < T;  // wave-uniform: this token tile holds tokens
+    const int tokbase = 16 * wave0;              // this pair's first K/V row
+    const TokOrder ord{T, Ts, Tf, Tsf, padtok};
+    const float padw = (float)(ms + md);
+    // how often token `tok` of the compact order counts in the source / destination mean
+    auto side_weights = [&](int tok, float& wsrc, float& wdst) {
+        const bool pad = tok == padtok;
+        wsrc = pad ? (float)ms : tok < Ts ? 1.f : 0.f;
+        wdst = pad ? (float)md : (tok >= Ts && tok < T) ? 1.f : 0.f;
+    };
     // f4 (caller-side fusion, train_link_prediction.py:166 / evaluate_models_utils.py:62-63): the second pair of the workgroup is the
     // NEGATIVE call of the first pair's edge when it has the same source, the same time and the same padded source length.  Its token
     // tiles that hold source tokens only then take the node / edge / time rows of the residual stream from the first pair's same tile
     // instead of gathering and projecting them again (rows of one channel receive non-zero terms from that channel only, so the bits are
     // those of a separate call); the co-occurrence rows and the destination side are its own.  Anything else: the plain path.
     bool src_shared = false;
-    if (NP == 2) {
+    if (!PK && NP == 2) {
         if (paired && pi == 1 && pair_ok) {
             const int64_t b0 = blockIdx.x;
             const CallDims cd0 = a.cd[b0 / a.G];
+            // (inference: Ts counts the REAL source tokens; an equal window length and an equal padded length make both pairs' compact source sides equal)
             src_shared = a.src[b0] == a.src[b] && __double_as_longlong(a.times[b0]) == __double_as_longlong(a.times[b]) && cd0.S_s == Ss &&
-                         16 * (tt + 1) <= Ts;
+                         (TR || a.hist_len[b0] == a.hist_len[b]) && 16 * (tt + 1) <= Ts;
         }
         src_shared = __builtin_amdgcn_readfirstlane((int)src_shared) != 0;
     }
-    const bool donor = NP == 2 && paired && pi == 0 && 16 * (tt + 1) <= Ts;     // first-pair tiles a shared tile may copy from (checked by the taker)
+    const bool donor = !PK && NP == 2 && paired && pi == 0 && 16 * (tt + 1) <= Ts;     // first-pair tiles a shared tile may copy from (checked by the taker)
 
     // ---- weights start moving at once: the first four stages of the layer stream into the ring, the first two halves of
     // projection fragments into the K/V region behind the window arrays (all of it lands during the window phase)
@@ -308,7 +373,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
     {
         const int tok = 16 * tt + c;
         const bool tv = tok < T;
-        const int pos0 = tv ? (tok < Ts ? tok * a.P : SsA + (tok - Ts) * a.P) : 0;
+        // the padding token reads the first all-padding patch of the pair: on the source side if it has one (m_s > 0), else on the destination side,
+        // where it follows the last real destination token as in the padded order
+        const int pos0 = tv ? (tok < Ts ? tok * a.P : (tok == padtok && ms > 0) ? Ts * a.P : SsA + (tok - Ts) * a.P) : 0;
         const int P = a.P;
         // Round 3: the whole phase is written WITHOUT branches around loads.  hipcc counts the loads in flight (s_waitcnt vmcnt / lgkmcnt (N))
         // only while every path through the code issues the same loads: with the earlier form — gathers skipped for absent rows, the
@@ -624,7 +691,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
     }
     // K, V and the slack behind them: rows of absent tokens are read as MFMA operands and must be finite
     for (int i = tid; i < kLdsRing / 4; i += NTHR) reinterpret_cast<f4*>(lds)[i] = zero4();
-    tap_store<TPW>(x, a.tap_enc, b, a.Tmax, T, tt, c, g);
+    tap_store<TPW>(x, a.tap_enc, b, a.Tmax, ord, tt, c, g);
 
     float* Kb = lds + kLdsK;
     float* Vb = lds + kLdsV;
@@ -730,7 +797,15 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
                 f4 sa[TPW];
 #pragma unroll
                 for (int kt = 0; kt < TPW; ++kt) sa[kt] = zero4();
-                s_like<TPW>(sa, Kb + tokbase * kKV, qa, c, g);       // S^T[key][query] = sum_d K[key][d] * Q^T[d][query]
+                // S^T[key][query] = sum_d K[key][d] * Q^T[d][query].  The packed form leaves out key tiles its pair does not have, by halves: a
+                // pair of one or two tiles runs two, any other four (a form of its own per tile count — four copies of both products — spills
+                // 28 VGPRs; this one needs no scratch).  The rows of a tile the pair does not have belong to its neighbours in the workgroup, or
+                // lie up to 16 rows past the region in what follows it (V, the weight ring: filled since the prologue); they are finite, the
+                // scores are masked below, and P V adds weight zero times a finite row: the bits are those of the unpacked kernels.
+                if constexpr (PK) {
+                    if (nwv <= 2) s_like_n<2>(sa, Kb + tokbase * kKV, qa, c, g);
+                    else s_like_n<4>(sa, Kb + tokbase * kKV, qa, c, g);
+                } else s_like<TPW>(sa, Kb + tokbase * kKV, qa, c, g);
                 // softmax over keys (rows 16kt + 4g + r); keys >= T do not exist
                 float mx = -INFINITY;
 #pragma unroll
@@ -744,10 +819,22 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
                 mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
                 mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
                 float sum = 0.f;
+                // The padding key stands for m_s + m_d identical keys: its weight counts that often in the row sum and in P V (times 1 is exact:
+                // every other key, and a pair without padding, is untouched).  Key 16 kt + 4 g + r is the padding token where kt is its tile
+                // (a scalar) and r == dq.  dq is made opaque per head: left to itself hipcc forms the 4 TPW factors once, outside the layer
+                // loop, and keeps them in registers through the whole kernel (16 VGPRs: the 128-token kernels spill).
+                int dq = (padtok & 15) - 4 * g;
+                if constexpr (!TR) asm volatile("" : "+v"(dq));
 #pragma unroll
-                for (int kt = 0; kt < TPW; ++kt)
+                for (int kt = 0; kt < TPW; ++kt) {
+                    const float wk = (!TR && (padtok >> 4) == kt) ? padw : 1.0f;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) { sa[kt][r] = __expf(sa[kt][r] - mx); sum += sa[kt][r]; }
+                    for (int r = 0; r < 4; ++r) {
+                        sa[kt][r] = __expf(sa[kt][r] - mx);
+                        if constexpr (!TR) sa[kt][r] *= (dq == r) ? wk : 1.0f;
+                        sum += sa[kt][r];
+                    }
+                }
                 sum += __shfl_xor(sum, 16, 64);
                 sum += __shfl_xor(sum, 32, 64);
                 const float inv = 1.0f / sum;
@@ -778,7 +865,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
                     }
                 }
                 // O^T[d][query] = sum_key V[key][d] * P^T[key][query]  (rows >= 100 are junk x zero weight columns)
-                pv_like<TPW>(oa, Vb + tokbase * kKV, sa, c, g);
+                if constexpr (PK) {
+                    if (nwv <= 2) pv_like<2>(oa, Vb + tokbase * kKV, reinterpret_cast<const f4 (&)[2]>(sa), c, g);
+                    else pv_like<4>(oa, Vb + tokbase * kKV, sa, c, g);
+                } else pv_like<TPW>(oa, Vb + tokbase * kKV, sa, c, g);
             }
             if constexpr (TR) {
                 if (tokv) {
@@ -827,20 +917,32 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
         if (last) {
             // Every wave has passed the stage barriers of the last out-projection: K and V are dead.  The residual's per-side sums are
             // taken here (x1: what the per-token form adds the FFN output to).
-            pool_sides(x, lds + kLdsPool, wave, c, g, ptok < Ts, ptok >= Ts && ptok < T);
+            float wsrc, wdst;
+            int ptk = ptok;
+            if constexpr (!TR) asm volatile("" : "+v"(ptk));      // (the weights are formed here, not kept through the layers)
+            side_weights(ptk, wsrc, wdst);
+            pool_sides(x, lds + kLdsPool, wave, c, g, wsrc, wdst);
         }
-        const bool straddle = 16 * tt < Ts && Ts < 16 * (tt + 1);      // wave-uniform: the tile holds tokens of both sides
+        // wave-uniform: the tile holds tokens of both sides, or the padding token (which counts on both)
+        const bool straddle = (16 * tt < Ts && Ts < 16 * (tt + 1)) || (16 * tt <= padtok && padtok < 16 * (tt + 1));
         const bool dst_tile = 16 * tt >= Ts;
         // sums of gelu(h) over the tile's tokens of either side (DPP row sums, as pool_sides); a tile of one side sums once: the other
         // side's sum of zeros is zero, so the bits do not depend on which form ran
+        const bool g_pad = ptok == padtok;
+        const bool g_src = ptok < Ts || (g_pad && ms > 0), g_dst = (ptok >= Ts && ptok < T && !g_pad) || (g_pad && md > 0);
+        const float msf = (float)ms, mdf = (float)md;
         auto gelu_sums = [&](const f4 (&h)[2], int p) {
             float* gp = lds + kLdsGPool + wave * 2 * kHid + 32 * p + 4 * g;
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 f4 vs, vd;
                 if (straddle) {
-                    vs = ptok < Ts ? h[u] : zero4();
-                    vd = ptok >= Ts && ptok < T ? h[u] : zero4();
+                    // (the weights are formed here from lane masks and scalars: kept in two VGPRs through the FFN loop they spill)
+                    float one = 1.0f;
+                    asm volatile("" : "+v"(one));
+                    const float wsrc = g_pad ? msf : one, wdst = g_pad ? mdf : one;
+                    vs = g_src ? h[u] * wsrc : zero4();
+                    vd = g_dst ? h[u] * wdst : zero4();
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { vs[r] = row_sum16_dpp(vs[r]); vd[r] = row_sum16_dpp(vd[r]); }
                 } else {
@@ -901,7 +1003,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
         }
         ws.advance(1);
         TACC(T_FFN);
-        tap_store<TPW>(x, a.tap_layer[l], b, a.Tmax, T, tt, c, g);
+        tap_store<TPW>(x, a.tap_layer[l], b, a.Tmax, ord, tt, c, g);
         }
     }
 
@@ -914,19 +1016,22 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
         int lane4 = lane * 4;
         if constexpr (PL != 0) asm volatile("" : "+v"(lane4));
         if constexpr (PL == 0) {
-            pool_sides(x, pool, wave, c, g, tok < Ts, tok >= Ts && tok < T);
+            float wsrc, wdst;
+            side_weights(tok, wsrc, wdst);
+            pool_sides(x, pool, wave, c, g, wsrc, wdst);
             TACC(T_POOL1);
             __syncthreads();
         }
         TACC(T_POOL2);
         // mean[col][208], col = 2*pair + side (4 columns of the 16-wide B operand are used; the rest multiply zeros)
         float* mean = lds + kLdsMean;
-        const int Tse = Ts, Td = T - Ts;
+        const int Tse = Tsf, Td = Tf - Tsf;      // the means are over the tokens of the padded call
+        const int npw = PK ? nwv : TPW;          // waves of this pair
         for (int i = ptid; i < 2 * kDP; i += PT) {
             const int side = i / kDP, n = i % kDP;
             float s = 0.f;
 #pragma unroll
-            for (int w = 0; w < TPW; ++w) s += pool[((pi * TPW + w) * 2 + side) * kDP + n];
+            for (int w = 0; w < npw; ++w) s += pool[((wave0 + w) * 2 + side) * kDP + n];
             const float mv = n < kD ? s / (float)(side ? Td : Tse) : 0.f;
             if constexpr (PL == 3) { if (pair_ok) a.pooled_rows[(2 * b + side) * kPoolRow + kHid + n] = mv; }
             else mean[pi * 2 * kDP + i] = mv;
@@ -940,7 +1045,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
                 const int side = i / kHid, n = i % kHid;
                 float s = 0.f;
 #pragma unroll
-                for (int w = 0; w < TPW; ++w) if (16 * w < T) s += gpool[((pi * TPW + w) * 2 + side) * kHid + n];      // a wave without tokens wrote nothing
+                for (int w = 0; w < npw; ++w) if (16 * w < T) s += gpool[((wave0 + w) * 2 + side) * kHid + n];      // a wave without tokens wrote nothing
                 const float mg = s / (float)(side ? Td : Tse);
                 if constexpr (PL == 3) { if (pair_ok) a.pooled_rows[(2 * b + side) * kPoolRow + n] = mg; }
                 else meang[pi * 2 * kHid + i] = mg;
@@ -1003,6 +1108,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(c
     }
     TACC(T_POOL);
     TSTORE();
+}
+
+template <int TPW, bool TR, int NW = 8, int PL = 0>
+__global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void k_dygformer_fused3(const Args a) {
+    fused3_body<TPW, TR, NW, PL, false>(a);
 }
 
 }  // namespace v3

@@ -22,6 +22,7 @@ struct PackLayout3 {       // float offsets relative to PackedLayout.fused3
     int scr_floats, slab_chunks;                   // LDS split of the K/V region during the prologue
     int np, slab_in_ring;                          // pairs per workgroup (0: shape unsupported); slab placed in the weight ring
     int tab_off, tab_slots, tab_bits;              // co-occurrence table (long windows): LDS word offset, slots per pair
+    int scr_floats8, slab_chunks8;                 // the same split with the window arrays of EIGHT pairs (the packed kernel); 0: they do not fit
     size_t bwd[DYGNN_MAX_LAYERS]; int bwd_nstages;  // per layer: the backward stream of its FFN block (training only)
     size_t bwa[DYGNN_MAX_LAYERS]; int bwa_nstages; int64_t bwa_frags;      // ... and of its attention block
     size_t stream_p; int64_t nfrag_p; int nstages_p;       // ring stream of the pooled inference kernels (build_stream, pooled)
@@ -50,6 +51,16 @@ inline bool pooled_tail_wanted(int64_t workgroups) {
     if (e && (e[0] == '0' || e[0] == '1') && e[1] == '\0') return e[0] == '1';
     return workgroups >= kPooledTailMinWorkgroups;
 }
+
+// Untapped launches of pairs of <= 64 tokens that defer their tail run the PACKED kernel: pairs of 1 .. 4 token tiles laid eight tiles to
+// a workgroup by the plan kernel (dygformer_pack_plan.hip, fused3_plan.h).  DYGNN_PACK_PAIRS = 0 / 1: never / on every eligible shape (1 also
+// defers the tail); anything else: wherever the tail is deferred.  Read on every call.  Returns -1 (unset), 0 or 1.
+inline int pack_pairs_env() {
+    const char* e = getenv("DYGNN_PACK_PAIRS");
+    return (e && (e[0] == '0' || e[0] == '1') && e[1] == '\0') ? e[0] - '0' : -1;
+}
+// dygformer_pack_plan.hip: the plan of a launch, written to the workspace by one small kernel on stream s
+int pack_plan_device(const Dims& d, int64_t B, int64_t G, char* ws, const WorkspaceLayout& wl, hipStream_t s);
 
 // Projected feature tables (dygformer_proj_tables.hip): one (table row, patch slot) segment = the channel's four x tiles, kProjRow floats
 constexpr int kProjRow = 64;

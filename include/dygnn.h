@@ -180,6 +180,13 @@ size_t dygnn_dygformer_workspace_bytes(const dygnn_dygformer_config* cfg_host, i
  * results, the generic path also its activation buffers; dygnn_dygformer_workspace_bytes is the size that serves every impl */
 size_t dygnn_dygformer_workspace_bytes_for(const dygnn_dygformer_config* cfg_host, int64_t batch, int32_t impl);
 
+/* Host arithmetic of the fused inference kernels' token compaction and pair packing (tests; no GPU).  pair_tokens: a pair of a call
+ * padded to T_s + T_d tokens whose windows hold len_s / len_d neighbours -> out = {R_s, R_d, m_s, m_d, Tc}: real tokens and all-padding
+ * tokens per side, tokens computed (real ones + one padding token).  pack_plan: pairs of tiles[i] (1 .. 4) token tiles laid eight tiles
+ * to a workgroup by the plan kernel's own arithmetic -> wg[i], first_wave[i]; returns the workgroups used, -1 on a bad tile count. */
+void dygnn_dygformer_pair_tokens_host(int32_t len_s, int32_t len_d, int32_t L, int32_t P, int32_t T_s, int32_t T_d, int32_t* out);
+int64_t dygnn_dygformer_pack_plan_host(const int32_t* tiles, int64_t n, int32_t* wg, int32_t* first_wave);
+
 /* One launch sequence for `batch` (src,dst,t) pairs.  group_size = G splits the pairs into consecutive
  * groups of G that are padded independently (each group has its own S_src/S_dst, models/DyGFormer.py:219-226):
  * the result of every group is bit-identical to a separate reference call on that group, so several
