@@ -12,7 +12,8 @@ __all__ = ["DyGFormer", "TGAT", "MemoryModel", "GraphMixer", "TCL", "CAWN", "Mer
            "count_nodes_appearances", "InteractionData", "Data", "get_link_prediction_data",
            "get_link_prediction_metrics", "get_node_classification_metrics", "link_prediction_metrics_device",
            "NegativeEdgeSampler", "get_idx_data_loader", "evaluate_model_link_prediction",
-           "edge_bank_link_prediction", "evaluate_edge_bank_link_prediction"]
+           "edge_bank_link_prediction", "evaluate_edge_bank_link_prediction",
+           "JODIE", "DyRep", "compute_src_dst_node_time_shifts", "evaluate_memory_model_link_prediction"]
 
 
 def __getattr__(name):
@@ -23,6 +24,9 @@ def __getattr__(name):
     if name == "MemoryModel":
         from .memory_model import MemoryModel
         return MemoryModel
+    if name in ("JODIE", "DyRep", "compute_src_dst_node_time_shifts"):
+        from . import memory_variants
+        return getattr(memory_variants, name)
     if name == "TGAT":
         from .tgat import TGAT
         return TGAT
@@ -47,7 +51,7 @@ def __getattr__(name):
     if name in ("get_link_prediction_metrics", "get_node_classification_metrics", "link_prediction_metrics_device"):
         from . import metrics
         return getattr(metrics, name)
-    if name in ("NegativeEdgeSampler", "get_idx_data_loader", "evaluate_model_link_prediction"):
+    if name in ("NegativeEdgeSampler", "get_idx_data_loader", "evaluate_model_link_prediction", "evaluate_memory_model_link_prediction"):
         from . import evaluate
         return getattr(evaluate, name)
     if name in ("edge_bank_link_prediction", "evaluate_edge_bank_link_prediction"):

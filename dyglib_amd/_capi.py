@@ -80,6 +80,10 @@ class GruGrads(GruWeights):
     """dygnn_gru_grads: the layout of GruWeights, its pointers writable gradient buffers (zero on entry)."""
 
 
+class RnnWeights(GruWeights):
+    """dygnn_rnn_weights: the layout of GruWeights with one gate (nn.RNNCell)."""
+
+
 class TgnState(C.Structure):
     _fields_ = [("num_nodes", C.c_int64)] + [(n, C.c_void_p) for n in ("memory", "last_update", "msg", "msg_time", "has_msg")]
 
@@ -216,6 +220,17 @@ SIGNATURES = {
     "dygnn_tgn_forward_levels": (C.c_int, [C.POINTER(TgatConfig), C.POINTER(TgatWeights), C.POINTER(GruWeights), C.POINTER(TgatLevels), C.c_void_p, C.c_void_p,
                                            C.POINTER(TgnState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dygnn_dyrep_workspace_bytes": (C.c_size_t, [C.POINTER(TgatConfig), C.c_int64, C.c_int64]),
+    "dygnn_dyrep_forward_step": (C.c_int, [C.POINTER(TgatConfig), C.POINTER(TgatWeights), C.POINTER(RnnWeights), C.POINTER(Csr), C.c_void_p, C.c_void_p,
+                                           C.POINTER(TgnState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dygnn_dyrep_forward_levels": (C.c_int, [C.POINTER(TgatConfig), C.POINTER(TgatWeights), C.POINTER(RnnWeights), C.POINTER(TgatLevels), C.c_void_p, C.c_void_p,
+                                             C.POINTER(TgnState), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "dygnn_jodie_workspace_bytes": (C.c_size_t, [C.POINTER(TgatConfig), C.c_int64, C.c_int64]),
+    "dygnn_jodie_forward_step": (C.c_int, [C.POINTER(TgatConfig), C.c_void_p, C.c_void_p, C.POINTER(RnnWeights), C.c_void_p, C.c_void_p,
+                                           C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.POINTER(TgnState), C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "dygnn_dygformer_train_workspace_bytes": (C.c_size_t, [C.POINTER(DygformerConfig), C.c_int64]),
     "dygnn_dygformer_train_forward": (C.c_int, [C.POINTER(DygformerConfig), C.POINTER(DygformerWeights), C.POINTER(Csr), C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p,

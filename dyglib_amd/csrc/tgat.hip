@@ -14,6 +14,7 @@
 #include "tgat_chain.h"
 #include "tgat_attn.h"
 #include "tgat_levels.h"
+#include "memory_rnn.h"
 
 namespace dygnn {
 
@@ -1060,4 +1061,124 @@ extern "C" int dygnn_tgn_forward_step(const dygnn_tgat_config* cfg, const dygnn_
                                       float* out_dst, void* workspace, size_t workspace_bytes, dygnn_stream_t stream) {
     return tgn_forward_impl(cfg, w, gru, csr, node_feat, edge_feat, st, src, dst, times, edge_ids, batch, n_positive, out_src, out_dst, workspace,
                             workspace_bytes, stream);
+}
+
+// ================================================================================================
+// DyRep (reference models/MemoryModel.py with model_name == 'DyRep'): TGN's modules with nn.RNNCell in place of nn.GRUCell, and two twists
+// on the data flow (:163-166, :225-227): a call RETURNS the updated memories of its roots, and in a positive call the attention embedding
+// of the other endpoint of a pair takes the place of its memory in the new raw message.  So only the positive pairs need the attention:
+//   1. chain::pack_rnn + k_rnn_rows (memory_rnn.hip) over all roots [src ; dst] of the batch, without the time projection: the returned
+//      rows -- gathered from updated memory BEFORE the commit, which runs last -- and the per-root scratch of the commit.  A negative call
+//      (n_positive = 0) ends here: its attention would be thrown away (the reference still computes it).
+//   2. TGN's pipeline on the first n_positive pairs: levels (sampled here, or the caller's), owner slots, list pass + layer packing,
+//      k_rnn_list (the cell over the listed level-0 nodes, row count on the device) -> feat0 = updated memory + raw, the layers as chains
+//      -> attention rows [2 n_positive][Fn] in the workspace.
+//   3. chain::memory_commit with those rows as the "other endpoint" part of the messages.
+// ================================================================================================
+namespace dygnn {
+struct DyrepPlan { size_t tgn, rpk, upd, lu, pend, att, total; };
+static DyrepPlan make_dyrep_plan(const dygnn_tgat_config& c, int64_t N, int64_t B) {
+    DyrepPlan p{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~size_t(255); return r; };
+    const int Fn = c.node_feat_dim, Dm = 2 * Fn + c.time_feat_dim + c.edge_feat_dim;
+    p.tgn = take(make_tgn_plan(c, N, B).total);                  // room for every n_positive <= B
+    p.rpk = take(chain::pack_bytes(chain::plan_pack_rnn(Fn, Dm)));
+    p.upd = take((size_t)2 * B * Fn * sizeof(float));
+    p.lu = take((size_t)2 * B * sizeof(float));
+    p.pend = take((size_t)2 * B * sizeof(int32_t));
+    p.att = take((size_t)2 * B * Fn * sizeof(float));
+    p.total = o;
+    return p;
+}
+
+static int dyrep_forward_impl(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_rnn_weights* rnn, const dygnn_csr* csr,
+                              const dygnn_tgat_levels* levels, const float* node_feat, const float* edge_feat, const dygnn_tgn_state* st,
+                              const int64_t* src, const int64_t* dst, const double* times, const int64_t* edge_ids, int64_t batch, int64_t n_pos,
+                              float* out_src, float* out_dst, void* workspace, size_t workspace_bytes, dygnn_stream_t stream) {
+    if (int rc = check_tgat(cfg)) return rc;
+    if (int rc = chain::check_rnn_dims("dyrep", cfg->node_feat_dim, cfg->edge_feat_dim, cfg->time_feat_dim)) return rc;
+    DYGNN_REQUIRE(n_pos >= 0 && n_pos <= batch, "dyrep: n_positive must be in [0, batch]");
+    DYGNN_REQUIRE(rnn && rnn->weight_ih && rnn->weight_hh && rnn->bias_ih && rnn->bias_hh, "dyrep: null RNN weights");
+    DYGNN_REQUIRE(st && st->memory && st->last_update && st->msg && st->msg_time && st->has_msg && st->num_nodes >= 1, "dyrep: bad state");
+    DYGNN_REQUIRE(batch >= 0 && node_feat && edge_feat && workspace && w && w->time_w && w->time_b, "dyrep: bad arguments");
+    DYGNN_REQUIRE(batch == 0 || (src && dst && times && out_src && out_dst), "dyrep: null pointer");
+    DYGNN_REQUIRE(n_pos == 0 || edge_ids != nullptr, "dyrep: edge_ids required for positive edges");   // MemoryModel.py:140
+    DYGNN_REQUIRE(batch == 0 || out_dst == out_src + (size_t)batch * cfg->node_feat_dim, "dyrep: out_dst must follow out_src (one [2, batch, dim] block)");
+    if (batch == 0) return DYGNN_OK;
+    const int64_t N = st->num_nodes;
+    const int Fn = cfg->node_feat_dim, Fe = cfg->edge_feat_dim, Ft = cfg->time_feat_dim, Dm = 2 * Fn + Ft + Fe;
+    const DyrepPlan p = make_dyrep_plan(*cfg, N, batch);
+    if (workspace_bytes < p.total) { set_error("dyrep: workspace too small (%zu < %zu bytes)", workspace_bytes, p.total); return DYGNN_E_WORKSPACE; }
+    hipStream_t s = as_stream(stream);
+    char* ws = static_cast<char*>(workspace);
+    float* rpk = reinterpret_cast<float*>(ws + p.rpk);
+    float* upd = reinterpret_cast<float*>(ws + p.upd);
+    float* lu = reinterpret_cast<float*>(ws + p.lu);
+    int32_t* pend = reinterpret_cast<int32_t*>(ws + p.pend);
+    float* att_src = reinterpret_cast<float*>(ws + p.att);
+    float* att_dst = att_src + (size_t)n_pos * Fn;
+    // 1. the returned rows: the updated memories of the roots, before anything is committed
+    const chain::RnnPackPlan rp = chain::plan_pack_rnn(Fn, Dm);
+    if (int rc = chain::pack_rnn(s, rp, Fn, Dm, rnn, rpk)) return rc;
+    chain::RnnRowArgs ra{src, dst, times, batch, N, st->msg, st->memory, st->last_update, st->msg_time, st->has_msg, rpk, rp.ih, rp.hh,
+                         rnn->bias_ih, rnn->bias_hh, nullptr, nullptr, {0.f, 0.f}, {1.f, 1.f}, out_src, upd, lu, pend, Dm, Fn};
+    if (int rc = chain::launch_rnn_rows(s, ra)) return rc;
+    if (n_pos == 0) return DYGNN_OK;
+    // 2. the attention embeddings of the positive pairs, over updated memory + raw features (TGN's pipeline with the RNN cell)
+    const TgnPlan tn = make_tgn_plan(*cfg, N, n_pos);
+    char* wn = ws + p.tgn;
+    float* Mnew = reinterpret_cast<float*>(wn + tn.Mnew);
+    float* feat0 = reinterpret_cast<float*>(wn + tn.feat0);
+    int32_t* owner = reinterpret_cast<int32_t*>(wn + tn.owner);
+    int32_t* pendf = reinterpret_cast<int32_t*>(wn + tn.pendf);
+    int32_t* list = reinterpret_cast<int32_t*>(wn + tn.list);
+    int32_t* count = reinterpret_cast<int32_t*>(wn + tn.count);
+    int32_t* list2 = reinterpret_cast<int32_t*>(wn + tn.list2);
+    int32_t* count2 = reinterpret_cast<int32_t*>(wn + tn.count2);
+    char* wt = wn + tn.tgat;
+    const TgatRoots roots{src, dst, times, n_pos, false};
+    if (int rc = check_tgat_args(cfg, w, csr, levels, feat0, edge_feat, roots, att_src, att_dst, wt, tn.total - tn.tgat)) return rc;
+    const TgatPlan tp = make_tgat_plan(*cfg, n_pos);
+    DYGNN_REQUIRE(chain::fits(tp.Fn, tp.Ft, tp.Dkv, tp.H), "dyrep: feature dims do not fit the row-block kernels");
+    const TgatStages c{tp, wt, s, tgat_dedup_active(tp, levels != nullptr)};
+    const TgnTouch touch{owner, count, N};
+    if (int rc = tgat_levels(c, csr, roots, levels, &touch)) return rc;
+    const chain::PackPlan pp = chain::plan_pack(tp.L, tp.Fn, tp.Ft, tp.Dkv, tp.H, 0);
+    float* pk = reinterpret_cast<float*>(wt + tp.pack);
+    const int32_t* live = c.dedup ? reinterpret_cast<const int32_t*>(wt + tp.dd_count) : nullptr;
+    const chain::ListArgs la{reinterpret_cast<const int32_t*>(wt + tp.ids[0]), live, owner, st->has_msg, pendf, count, list, count2, list2, tp.n[1], N, tp.k};
+    if (int rc = chain::pack(s, pp, tp.L, tp.Fn, tp.Ft, tp.Dkv, tp.H, w, nullptr, 0, pk, &la)) return rc;
+    const int64_t ub = N < tp.n[0] ? N : tp.n[0];
+    const chain::GruArgs ga{list, count, list2, count2, st->msg, st->memory, node_feat, rpk, rp.ih, rp.hh, rnn->bias_ih, rnn->bias_hh, Mnew, feat0, ub, Dm, Fn};
+    if (int rc = chain::launch_rnn_list(s, ga)) return rc;
+    if (int rc = tgat_layers(c, w, feat0, edge_feat, att_src, att_dst, true)) return rc;
+    // 3. persist and store: the other endpoint's part of a message is its attention row (MemoryModel.py:225-227)
+    return chain::memory_commit(s, src, dst, times, edge_ids, n_pos, batch, upd, lu, pend, att_src, att_dst, st, edge_feat, w->time_w, w->time_b, Fn, Fe, Ft);
+}
+}  // namespace dygnn
+
+extern "C" size_t dygnn_dyrep_workspace_bytes(const dygnn_tgat_config* cfg, int64_t num_nodes, int64_t batch) {
+    if (check_tgat(cfg) != DYGNN_OK || batch < 0 || num_nodes < 1) return 0;
+    if (chain::check_rnn_dims("dyrep", cfg->node_feat_dim, cfg->edge_feat_dim, cfg->time_feat_dim) != DYGNN_OK) return 0;
+    return make_dyrep_plan(*cfg, num_nodes, batch).total;
+}
+
+extern "C" int dygnn_dyrep_forward_step(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_rnn_weights* rnn, const dygnn_csr* csr,
+                                        const float* node_feat, const float* edge_feat, const dygnn_tgn_state* st, const int64_t* src, const int64_t* dst,
+                                        const double* times, const int64_t* edge_ids, int64_t batch, int64_t n_positive, float* out_src,
+                                        float* out_dst, void* workspace, size_t workspace_bytes, dygnn_stream_t stream) {
+    return dyrep_forward_impl(cfg, w, rnn, csr, nullptr, node_feat, edge_feat, st, src, dst, times, edge_ids, batch, n_positive, out_src, out_dst, workspace,
+                              workspace_bytes, stream);
+}
+
+// dygnn_dyrep_forward_step on PRE-SAMPLED levels of the first n_positive pairs (dygnn_tgn_forward_levels' layout with batch = n_positive;
+// not read when n_positive = 0)
+extern "C" int dygnn_dyrep_forward_levels(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_rnn_weights* rnn,
+                                          const dygnn_tgat_levels* levels, const float* node_feat, const float* edge_feat, const dygnn_tgn_state* st,
+                                          const int64_t* src, const int64_t* dst, const double* times, const int64_t* edge_ids, int64_t batch,
+                                          int64_t n_positive, float* out_src, float* out_dst, void* workspace, size_t workspace_bytes, dygnn_stream_t stream) {
+    DYGNN_REQUIRE(n_positive <= 0 || levels != nullptr, "dyrep_forward_levels: levels is NULL");
+    return dyrep_forward_impl(cfg, w, rnn, nullptr, levels, node_feat, edge_feat, st, src, dst, times, edge_ids, batch, n_positive, out_src, out_dst, workspace,
+                              workspace_bytes, stream);
 }

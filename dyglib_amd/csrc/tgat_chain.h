@@ -36,6 +36,12 @@ struct ListArgs {
 int pack(hipStream_t s, const PackPlan& p, int L, int Fn, int Ft, int Dkv, int H, const dygnn_tgat_weights* w, const dygnn_gru_weights* gru, int gru_Dm,
          float* dst, const ListArgs* lists = nullptr);
 
+// nn.RNNCell (JODIE / DyRep, memory_rnn.hip): weight_ih [Fn][Dm] and weight_hh [Fn][Fn] in the same fragment form, one gate; a buffer of its own
+struct RnnPackPlan { uint32_t ih, hh, total; };
+RnnPackPlan plan_pack_rnn(int Fn, int Dm);
+inline size_t pack_bytes(const RnnPackPlan& p) { return (size_t)p.total * 1024; }
+int pack_rnn(hipStream_t s, const RnnPackPlan& p, int Fn, int Dm, const dygnn_rnn_weights* rnn, float* dst);
+
 // rows i < n (or < *n_live): q_in = [h(self) | cos(b)] -> q = W_q q_in -> qk[i][h][:] = W_k,h^T q_ih          (models/modules.py:150-170)
 struct PreArgs {
     const float* h_lower;          // layer >= 2: rows of the level below ([.][Fn]); NULL: layer 1 reads node_feat[lower_ids[i]]

@@ -15,21 +15,11 @@
 // fragment form (k_pack), zero-padded to whole tiles / chunks so no step needs a mask; LDS rows are zero-padded to the 16-k chunk.
 #include <cstdlib>
 #include "tgat_chain.h"
+#include "chain_stream.h"      // the weight stream of a wave (shared with memory_rnn.hip)
 #include "tgat_attn.h"
 
 namespace dygnn {
 namespace chain {
-
-using f4 = __attribute__((ext_vector_type(4))) float;
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
-
-constexpr int kWaves = 8;
-constexpr int kThreads = kWaves * 64;
-__host__ __device__ inline int r16(int K) { return (K + 15) & ~15; }
-__host__ __device__ inline int pad_ld(int K) {           // smallest row stride >= K with stride % 32 == 16: the four rows of an operand read fall on distinct banks
-    const int l = r16(K);
-    return (l & 16) ? l : l + 16;
-}
 
 // ---- packing ----------------------------------------------------------------------------------------------------------------------
 struct PackDesc {
@@ -152,110 +142,25 @@ int pack(hipStream_t s, const PackPlan& p, int L, int Fn, int Ft, int Dkv, int H
     return DYGNN_OK;
 }
 
-// ---- the weight stream of a wave ------------------------------------------------------------------------------------------------
-// A stage gives wave w the tiles t = w, w + 8, ... < T.  Their fragments form ONE sequence of steps (tile by tile, chunk by chunk) that
-// runs through a ring of U float4 registers filled U steps ahead -- across tile boundaries, so the stream only drains at the end of a
-// stage.  Steady state is branch-free but for the tile epilogue (refills are always issued; beyond the stream they re-read the wave's
-// first tile), so the compiler counts the loads in flight (s_waitcnt vmcnt(U-1)) instead of draining them.  The LDS operands of step
-// s+1 are read before the MFMAs of step s.
-// AF: act(t) = LDS base of the activation operand of tile t.  Ep(t, acc): the finished tile -- every lane holds the sums of
-// Out[4m + j][16t + 4ng .. +3] in acc[m]; the ks == 0 lanes store.
-#ifndef DYGNN_CHAIN_U
-#define DYGNN_CHAIN_U 4      // ring depth: the chains run at the rate a CU streams fragments through its vector L1 (~35 B/clk measured), 4 .. 16 deep gave the same time per step; 4 is the least code
-#endif
-constexpr int U = DYGNN_CHAIN_U;
+// nn.RNNCell: the one-gate form of the GRU part above (one "head" of Fn rows per matrix), nothing else in the buffer
+RnnPackPlan plan_pack_rnn(int Fn, int Dm) {
+    RnnPackPlan p{};
+    p.ih = 0;
+    p.hh = kc_frags(Fn, Dm);
+    p.total = p.hh + kc_frags(Fn, Fn);
+    return p;
+}
 
-struct IdTile { __device__ __forceinline__ int operator()(int t) const { return t; } };
-// TM: local tile index -> tile index in the packed stage (a workgroup that owns a slice of a stage's tiles).
-// start() issues the first U fragment loads -- they depend on nothing the kernel computes, so a stage's ring is started BEFORE the
-// previous stage runs (its loads are then older than that stage's refills and have landed when it ends); run() consumes.
-template <class TM>
-struct WStream {
-    const f4* pk;
-    int T, nch, wave, lane, pt, pch, adv;
-    const f4* pp;
-    TM tmap;
-    f4 ring[U];
-    __device__ __forceinline__ WStream(const f4* pk_, int T_, int nch_, int wave_, int lane_, TM tm) : pk(pk_), T(T_), nch(nch_), wave(wave_), lane(lane_), pt(wave_), pch(0), tmap(tm) {
-        adv = wave < T ? 64 : 0;
-        pp = wave < T ? pk + (size_t)tmap(wave) * nch * 64 + lane : pk;
-#pragma unroll
-        for (int u = 0; u < U; ++u) fetch(ring[u]);
-    }
-    // Behind the wave's last fragment every lane re-reads ONE address (a single 16-byte request): the refill stays unconditional -- the
-    // compiler keeps counting the loads in flight -- without fetching a junk KiB per step (U junk fragments per stage and wave were 10-70 %
-    // of these short streams' traffic).
-    __device__ __forceinline__ void fetch(f4& dst) {
-        dst = *pp;
-        pp += adv;
-        if (++pch == nch) {
-            pch = 0; pt += kWaves;
-            if (pt < T) pp = pk + (size_t)tmap(pt) * nch * 64 + lane;
-            else { pp = pk; adv = 0; }
-        }
-    }
-    template <int MT, class AF, class Ep>
-    __device__ __forceinline__ void run(int lda, AF actf, Ep ep) {
-        if (wave >= T) return;
-        const int j = lane & 3, ks = (lane >> 2) & 3;
-        const int S = ((T - wave + kWaves - 1) / kWaves) * nch;
-        const f4 zero = f4{0.f, 0.f, 0.f, 0.f};
-        int ct = wave, cch = 0;                                           // consume cursor
-        const float* ab = actf(ct) + j * lda + 4 * ks;
-        f4 acc[MT], bn[MT];
-#pragma unroll
-        for (int m = 0; m < MT; ++m) { acc[m] = zero; bn[m] = *reinterpret_cast<const f4*>(ab + m * 4 * lda); }
-        auto step = [&](f4& slot, bool refill) {
-            const f4 w = slot;
-            f4 b[MT];
-#pragma unroll
-            for (int m = 0; m < MT; ++m) b[m] = bn[m];
-            const bool tile_end = cch + 1 == nch;
-            const int nt = tile_end ? ct + kWaves : ct, nc = tile_end ? 0 : cch + 1;
-            const float* nab = tile_end ? actf(nt < T ? nt : ct) + j * lda + 4 * ks : ab;
-#pragma unroll
-            for (int m = 0; m < MT; ++m) bn[m] = *reinterpret_cast<const f4*>(nab + m * 4 * lda + 16 * nc);      // (behind the last step: a valid, unused read)
-#pragma unroll
-            for (int m = 0; m < MT; ++m) acc[m] = mfma4(w.x, b[m].x, acc[m]);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) acc[m] = mfma4(w.y, b[m].y, acc[m]);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) acc[m] = mfma4(w.z, b[m].z, acc[m]);
-#pragma unroll
-            for (int m = 0; m < MT; ++m) acc[m] = mfma4(w.w, b[m].w, acc[m]);
-            if (refill) fetch(slot);
-            if (tile_end) {
-                f4 r[MT];
-#pragma unroll
-                for (int m = 0; m < MT; ++m) {          // k-slices 0 + 1, 2 + 3, then the pairs: fixed order
-                    f4 v = acc[m];                      // rotations inside the row of 16 lanes (DPP row_ror 4, then 8): no LDS
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float x = v[e];
-                        x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x124, 0xf, 0xf, false));
-                        x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x128, 0xf, 0xf, false));
-                        v[e] = x;
-                    }
-                    r[m] = v;
-                    acc[m] = zero;
-                }
-                ep(ct, r);
-            }
-            ct = nt; cch = nc; ab = nab;
-        };
-        int s0 = 0;
-        for (; s0 + U <= S; s0 += U) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) step(ring[u], true);
-        }
-#pragma unroll
-        for (int u = 0; u < U - 1; ++u)
-            if (s0 + u < S) step(ring[u], false);
-    }
-};
-template <class TM>
-__device__ __forceinline__ WStream<TM> wstream(const f4* pk, int T, int nch, int wave, int lane, TM tm) { return WStream<TM>(pk, T, nch, wave, lane, tm); }
-__device__ __forceinline__ WStream<IdTile> wstream(const f4* pk, int T, int nch, int wave, int lane) { return WStream<IdTile>(pk, T, nch, wave, lane, IdTile()); }
+int pack_rnn(hipStream_t s, const RnnPackPlan& p, int Fn, int Dm, const dygnn_rnn_weights* rnn, float* dst) {
+    PackTable tb{};
+    const int tph = (Fn + 15) / 16;
+    tb.d[tb.n++] = PackDesc{rnn->weight_ih, Dm, Fn, Dm, 0, tph, 0, p.ih, (uint32_t)tph, (uint32_t)((Dm + 15) / 16)};
+    tb.d[tb.n++] = PackDesc{rnn->weight_hh, Fn, Fn, Fn, 0, tph, 0, p.hh, (uint32_t)tph, (uint32_t)((Fn + 15) / 16)};
+    tb.total = p.total;
+    hipLaunchKernelGGL(k_pack, dim3((tb.total + 3) / 4), dim3(256), 0, s, tb, reinterpret_cast<f4*>(dst), ListArgs{}, 0u);
+    DYGNN_LAUNCH_CHECK();
+    return DYGNN_OK;
+}
 
 // query-input rows [h(self) | cos(w*0 + b)] of the block's rows (zero rows beyond the live count; zero padding columns).
 // A wave owns rows wave, wave + 8, ...: load() takes their indices, then their feature rows (and, for k_tgat_post, the raw feature rows
@@ -643,31 +548,11 @@ __global__ __launch_bounds__(kThreads) void k_tgn_gru_chain(const GruArgs a) {
 
 static size_t pre_lds(int Fn, int Ft, int H, int MT) { return (size_t)4 * MT * (pad_ld(Fn + Ft) + pad_ld((Fn + Ft) / H)) * sizeof(float); }
 static size_t post_lds(int Fn, int Ft, int Dkv, int H, int MT, int KC = 0) { return (size_t)post_layout(4 * MT, Fn, Ft, Dkv, H, KC).total * sizeof(float); }
-static int gru_slices() {          // DYGNN_GRU_SLICES = 1 .. 6: tuning override (read per call)
-    const char* e = getenv("DYGNN_GRU_SLICES");
-    return (e && e[0] >= '1' && e[0] <= '6' && e[1] == 0) ? e[0] - '0' : kGruSlices;
-}
+static int gru_slices() { return env_slices("DYGNN_GRU_SLICES", kGruSlices); }
 static size_t gru_lds(const GruArgs& a, int MT) {
     const int per = ((a.Fn + 15) / 16 + gru_slices() - 1) / gru_slices();
     return (size_t)4 * MT * (pad_ld(a.Dm) + pad_ld(a.Fn) + 2 * 3 * per * 16) * sizeof(float);
 }
-constexpr size_t kLdsMax = 160 * 1024;
-
-template <class K>
-static int set_lds(K kernel, size_t bytes) {
-    if (bytes > 64 * 1024) DYGNN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return DYGNN_OK;
-}
-// Rows per workgroup = 4 MT.  Small levels take few rows so that they still spread over the chip (the weights are re-streamed from L2 by
-// every workgroup: 4 rows at 800 rows = 200 workgroups); large levels take 32 rows (every weight fragment feeds 32 MFMAs).  A row's
-// bits do not depend on the choice.
-static int pick_mt(int64_t n) { return n <= 2048 ? 1 : n <= 8192 ? 2 : 4; }
-static int env_mt(const char* name, int mt) {          // DYGNN_CHAIN_MT / DYGNN_GRU_MT = 1 | 2 | 4 | 8: tuning override (read per call)
-    const char* e = getenv(name);
-    if (e && (e[0] == '1' || e[0] == '2' || e[0] == '4' || e[0] == '8') && e[1] == 0) return e[0] - '0';
-    return mt;
-}
-
 bool fits(int Fn, int Ft, int Dkv, int H) {
     if (H < 1 || (Fn + Ft) % H || Fn % 4 || Ft % 4 || Dkv % 4 || ((Fn + Ft) / H) % 4) return false;
     if (pad_ld(Fn + Ft) > 64 * kNQ || pad_ld(Fn + Ft + Fn) - (Fn + Ft) > 64 * kNQ) return false;      // RowRegs

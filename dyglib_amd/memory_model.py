@@ -3,11 +3,12 @@
 edges_are_positive, num_neighbors)`, `set_neighbor_sampler`, `memory_bank.__init_memory_bank__ / backup_memory_bank /
 reload_memory_bank`, and the same state_dict keys.  The forward, the GRU memory update and the raw-message bookkeeping run
 in libdygnn_hip.so (`dygnn_tgn_forward`).  In training mode with autograd recording the call is differentiable
-(`_TgnTrainFunction`: `dygnn_tgn_train_forward` / `dygnn_tgn_backward`).  JODIE / DyRep are not built (not in BASELINE.json's configs)."""
+(`_TgnTrainFunction`: `dygnn_tgn_train_forward` / `dygnn_tgn_backward`).  The JODIE and DyRep arms of the reference class are `dyglib_amd.JODIE`
+and `dyglib_amd.DyRep` (memory_variants.py, inference only); this class keeps refusing model_name 'JODIE' / 'DyRep'."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Tuple
+from typing import Tuple
 
 import numpy as np
 import torch
@@ -149,6 +150,63 @@ class GraphAttentionEmbedding(nn.Module):
                                                       hidden_dim=node_feat_dim, output_dim=node_feat_dim) for _ in range(num_layers)])
 
 
+def _init_memory_model(model, node_raw_features, edge_raw_features, time_feat_dim, model_name, num_layers, num_heads, dropout, device, updater_cls):
+    """What the three arms of the reference class share (MemoryModel.py:28-66): feature tables, dims, time encoder, memory bank and the memory
+    updater (`updater_cls`: GRUMemoryUpdater, or memory_variants.RNNMemoryUpdater), registered in the reference's order; the embedding module
+    is the caller's."""
+    model.node_raw_features = torch.from_numpy(np.ascontiguousarray(node_raw_features, dtype=np.float32)).to(device)
+    model.edge_raw_features = torch.from_numpy(np.ascontiguousarray(edge_raw_features, dtype=np.float32)).to(device)
+    model.node_feat_dim, model.edge_feat_dim = model.node_raw_features.shape[1], model.edge_raw_features.shape[1]
+    model.time_feat_dim, model.num_layers, model.num_heads, model.dropout, model.device = time_feat_dim, num_layers, num_heads, dropout, device
+    model.model_name = model_name
+    model.num_nodes = model.node_raw_features.shape[0]
+    model.memory_dim = model.node_feat_dim
+    model.message_dim = model.memory_dim + model.memory_dim + model.time_feat_dim + model.edge_feat_dim
+    model.time_encoder = TimeEncoder(time_dim=time_feat_dim)
+    model.memory_bank = MemoryBank(model.num_nodes, model.memory_dim, model.message_dim)
+    model.memory_updater = updater_cls(model.memory_bank, model.message_dim, model.memory_dim)
+    model._lib = _capi.load()
+    model._workspace = {}
+
+
+def _memory_call_inputs(model, src_node_ids, dst_node_ids, node_interact_times, edge_ids, edges_are_positive, _n_positive, csr):
+    """The head of compute_src_dst_node_temporal_embeddings for every arm: device and tables, id checks (IndexError like the reference's
+    memory_bank indexing, MemoryModel.py:336; `csr`: the sampler's graph, checked against the tables once, or None for a model without
+    neighbours), the inputs as device tensors and the number of positive pairs.  -> (dev, src, dst, tms, eids, B, n_pos)"""
+    dev = model.memory_bank.node_memories.device
+    if dev.type != "cuda":
+        raise _capi.DygnnError(f"dyglib_amd.{type(model).__name__} runs on an MI355X only; there is no CPU fallback")
+    if model.node_raw_features.device != dev:
+        model.node_raw_features, model.edge_raw_features = model.node_raw_features.to(dev), model.edge_raw_features.to(dev)
+    model.memory_bank._alloc()
+    if csr is not None:
+        if getattr(model, "_validated_csr", None) is not csr:          # once per sampler: graph ids inside the tables and the memory bank
+            csr.check_tables(min(model.node_raw_features.shape[0], model.num_nodes), model.edge_raw_features.shape[0])
+            model._validated_csr = csr
+        csr.check_query_ids(src_node_ids, limit=model.num_nodes)
+        csr.check_query_ids(dst_node_ids, limit=model.num_nodes)
+    else:
+        for ids in (src_node_ids, dst_node_ids):
+            if not isinstance(ids, torch.Tensor) and len(ids):
+                a = np.asarray(ids)
+                if int(a.min()) < 0 or int(a.max()) >= model.num_nodes:
+                    raise IndexError(f"node id {int(a.min()) if int(a.min()) < 0 else int(a.max())} is out of bounds for a memory bank with {model.num_nodes} rows")
+    if edge_ids is not None and not isinstance(edge_ids, torch.Tensor) and len(edge_ids):
+        e = np.asarray(edge_ids)
+        if int(e.min()) < 0 or int(e.max()) >= model.edge_raw_features.shape[0]:
+            raise IndexError(f"edge id out of bounds for edge_raw_features with {model.edge_raw_features.shape[0]} rows")
+    src, dst, tms = _to_dev(src_node_ids, torch.int64, dev), _to_dev(dst_node_ids, torch.int64, dev), _to_dev(node_interact_times, torch.float64, dev)
+    B = src.numel()
+    assert dst.numel() == B and tms.numel() == B
+    if edges_are_positive:
+        assert edge_ids is not None                                                        # MemoryModel.py:140
+    eids = _to_dev(edge_ids, torch.int64, dev) if edge_ids is not None else None
+    n_pos = (B if edges_are_positive else 0) if _n_positive is None else int(_n_positive)
+    if eids is not None and eids.numel() < n_pos:
+        raise AssertionError("edge_ids must cover the positive edges")
+    return dev, src, dst, tms, eids, B, n_pos
+
+
 class MemoryModel(nn.Module):
 
     def __init__(self, node_raw_features: np.ndarray, edge_raw_features: np.ndarray, neighbor_sampler: NeighborSampler,
@@ -160,21 +218,9 @@ class MemoryModel(nn.Module):
             raise NotImplementedError(f"model_name {model_name} is not built on the HIP path (BASELINE config 5 is TGN)")
         if model_name != "TGN":
             raise ValueError(f"Not implemented error for model_name {model_name}!")           # MemoryModel.py:63
-        self.node_raw_features = torch.from_numpy(np.ascontiguousarray(node_raw_features, dtype=np.float32)).to(device)
-        self.edge_raw_features = torch.from_numpy(np.ascontiguousarray(edge_raw_features, dtype=np.float32)).to(device)
-        self.node_feat_dim, self.edge_feat_dim = self.node_raw_features.shape[1], self.edge_raw_features.shape[1]
-        self.time_feat_dim, self.num_layers, self.num_heads, self.dropout, self.device = time_feat_dim, num_layers, num_heads, dropout, device
-        self.model_name = model_name
-        self.num_nodes = self.node_raw_features.shape[0]
-        self.memory_dim = self.node_feat_dim
-        self.message_dim = self.memory_dim + self.memory_dim + self.time_feat_dim + self.edge_feat_dim
-        self.time_encoder = TimeEncoder(time_dim=time_feat_dim)
-        self.memory_bank = MemoryBank(self.num_nodes, self.memory_dim, self.message_dim)
-        self.memory_updater = GRUMemoryUpdater(self.memory_bank, self.message_dim, self.memory_dim)
+        _init_memory_model(self, node_raw_features, edge_raw_features, time_feat_dim, model_name, num_layers, num_heads, dropout, device, GRUMemoryUpdater)
         self.embedding_module = GraphAttentionEmbedding(self.node_feat_dim, self.edge_feat_dim, self.time_feat_dim, num_layers, num_heads,
                                                         dropout, neighbor_sampler, self.time_encoder)
-        self._lib = _capi.load()
-        self._workspace: Dict[tuple, torch.Tensor] = {}
 
     def set_neighbor_sampler(self, neighbor_sampler: NeighborSampler):
         """MemoryModel.py:253-263."""
@@ -229,31 +275,8 @@ class MemoryModel(nn.Module):
         random_strategy = sampler.sample_neighbor_strategy != "recent"
         if random_strategy and _n_positive is not None:
             raise NotImplementedError("a joint [positives ; negatives] step needs `recent` sampling (a random strategy draws per call)")
-        dev = self.memory_bank.node_memories.device
-        if dev.type != "cuda":
-            raise _capi.DygnnError("dyglib_amd.MemoryModel runs on an MI355X only; there is no CPU fallback")
-        if self.node_raw_features.device != dev:
-            self.node_raw_features, self.edge_raw_features = self.node_raw_features.to(dev), self.edge_raw_features.to(dev)
-        self.memory_bank._alloc()
-        csr = sampler.csr
-        if getattr(self, "_validated_csr", None) is not csr:          # once per sampler: graph ids inside the tables and the memory bank
-            csr.check_tables(min(self.node_raw_features.shape[0], self.num_nodes), self.edge_raw_features.shape[0])
-            self._validated_csr = csr
-        csr.check_query_ids(src_node_ids, limit=self.num_nodes)        # IndexError like the reference's memory_bank indexing (MemoryModel.py:336)
-        csr.check_query_ids(dst_node_ids, limit=self.num_nodes)
-        if edge_ids is not None and not isinstance(edge_ids, torch.Tensor) and len(edge_ids):
-            e = np.asarray(edge_ids)
-            if int(e.min()) < 0 or int(e.max()) >= self.edge_raw_features.shape[0]:
-                raise IndexError(f"edge id out of bounds for edge_raw_features with {self.edge_raw_features.shape[0]} rows")
-        src, dst, tms = _to_dev(src_node_ids, torch.int64, dev), _to_dev(dst_node_ids, torch.int64, dev), _to_dev(node_interact_times, torch.float64, dev)
-        B = src.numel()
-        assert dst.numel() == B and tms.numel() == B
-        if edges_are_positive:
-            assert edge_ids is not None                                                        # MemoryModel.py:140
-        eids = _to_dev(edge_ids, torch.int64, dev) if edge_ids is not None else None
-        n_pos = (B if edges_are_positive else 0) if _n_positive is None else int(_n_positive)
-        if eids is not None and eids.numel() < n_pos:
-            raise AssertionError("edge_ids must cover the positive edges")
+        dev, src, dst, tms, eids, B, n_pos = _memory_call_inputs(self, src_node_ids, dst_node_ids, node_interact_times, edge_ids, edges_are_positive, _n_positive,
+                                                                 sampler.csr)
         if train and B > 0:
             p_drop, seed = self._dropout_and_seed()
             levels = None

@@ -282,6 +282,62 @@ def make_tgn_params(seed: int, num_nodes: int, num_layers: int = 1) -> Dict[str,
     return out
 
 
+def jodie_param_shapes(num_nodes: int, node_feat_dim: int = NODE_FEAT_DIM, edge_feat_dim: int = NODE_FEAT_DIM, time_feat_dim: int = 100
+                       ) -> Dict[str, Tuple[int, ...]]:
+    """state_dict of the reference MemoryModel('JODIE') (models/MemoryModel.py:43-72, :504-532): nn.RNNCell has one gate; the memory bank is
+    registered twice (memory_bank.* and memory_updater.memory_bank.*, same tensors)."""
+    Fn = node_feat_dim
+    Dm = 2 * Fn + time_feat_dim + edge_feat_dim
+    return {"time_encoder.w.weight": (time_feat_dim, 1), "time_encoder.w.bias": (time_feat_dim,),
+            "memory_bank.node_memories": (num_nodes, Fn), "memory_bank.node_last_updated_times": (num_nodes,),
+            "memory_updater.memory_bank.node_memories": (num_nodes, Fn), "memory_updater.memory_bank.node_last_updated_times": (num_nodes,),
+            "memory_updater.memory_updater.weight_ih": (Fn, Dm), "memory_updater.memory_updater.weight_hh": (Fn, Fn),
+            "memory_updater.memory_updater.bias_ih": (Fn,), "memory_updater.memory_updater.bias_hh": (Fn,),
+            "embedding_module.linear_layer.weight": (Fn, 1), "embedding_module.linear_layer.bias": (Fn,)}
+
+
+def make_jodie_params(seed: int, node_feat_dim: int = NODE_FEAT_DIM, edge_feat_dim: int = NODE_FEAT_DIM, time_feat_dim: int = 100) -> Dict[str, np.ndarray]:
+    """Trainable JODIE parameters (the memory bank starts at zero and is not part of this set): the RNNCell in torch's default range, the
+    time projection wide enough that 1 + w * delta + b differs visibly from row to row."""
+    rs = np.random.RandomState(seed)
+    Fn, Dm = node_feat_dim, 2 * node_feat_dim + time_feat_dim + edge_feat_dim
+    out: Dict[str, np.ndarray] = {}
+    base = (1.0 / 10 ** np.linspace(0, 9, time_feat_dim, dtype=np.float32)).reshape(time_feat_dim, 1)
+    out["time_encoder.w.weight"] = (base * (1.0 + 0.01 * rs.uniform(-1, 1, size=(time_feat_dim, 1)))).astype(np.float32)
+    out["time_encoder.w.bias"] = (0.1 * rs.uniform(-1, 1, size=(time_feat_dim,))).astype(np.float32)
+    b = 1.0 / np.sqrt(Fn)
+    out["memory_updater.memory_updater.weight_ih"] = rs.uniform(-b, b, (Fn, Dm)).astype(np.float32)
+    out["memory_updater.memory_updater.weight_hh"] = rs.uniform(-b, b, (Fn, Fn)).astype(np.float32)
+    out["memory_updater.memory_updater.bias_ih"] = rs.uniform(-b, b, (Fn,)).astype(np.float32)
+    out["memory_updater.memory_updater.bias_hh"] = rs.uniform(-b, b, (Fn,)).astype(np.float32)
+    out["embedding_module.linear_layer.weight"] = (0.3 * rs.uniform(-1, 1, (Fn, 1))).astype(np.float32)
+    out["embedding_module.linear_layer.bias"] = (0.3 * rs.uniform(-1, 1, (Fn,))).astype(np.float32)
+    return out
+
+
+def dyrep_param_shapes(num_nodes: int, node_feat_dim: int = NODE_FEAT_DIM, edge_feat_dim: int = NODE_FEAT_DIM, time_feat_dim: int = 100,
+                       num_layers: int = 1) -> Dict[str, Tuple[int, ...]]:
+    """state_dict of the reference MemoryModel('DyRep'): TGN's (tgn_param_shapes) with nn.RNNCell's one gate in the memory updater."""
+    shapes = tgn_param_shapes(num_nodes, node_feat_dim, edge_feat_dim, time_feat_dim, num_layers)
+    for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
+        s = shapes["memory_updater.memory_updater." + k]
+        shapes["memory_updater.memory_updater." + k] = (s[0] // 3,) + s[1:]
+    return shapes
+
+
+def make_dyrep_params(seed: int, num_nodes: int, num_layers: int = 1) -> Dict[str, np.ndarray]:
+    """Trainable DyRep parameters: make_tgn_params' attention / merge / time-encoder tensors, and an RNNCell in torch's default range."""
+    out = make_tgn_params(seed, num_nodes, num_layers=num_layers)
+    rs = np.random.RandomState(seed + 77)
+    Fn, Dm = NODE_FEAT_DIM, 2 * NODE_FEAT_DIM + 100 + NODE_FEAT_DIM
+    b = 1.0 / np.sqrt(Fn)
+    out["memory_updater.memory_updater.weight_ih"] = rs.uniform(-b, b, (Fn, Dm)).astype(np.float32)
+    out["memory_updater.memory_updater.weight_hh"] = rs.uniform(-b, b, (Fn, Fn)).astype(np.float32)
+    out["memory_updater.memory_updater.bias_ih"] = rs.uniform(-b, b, (Fn,)).astype(np.float32)
+    out["memory_updater.memory_updater.bias_hh"] = rs.uniform(-b, b, (Fn,)).astype(np.float32)
+    return out
+
+
 def graphmixer_param_shapes(num_tokens: int, node_feat_dim: int = NODE_FEAT_DIM, edge_feat_dim: int = NODE_FEAT_DIM, time_feat_dim: int = 100,
                             num_layers: int = 2, token_dim_expansion_factor: float = 0.5,
                             channel_dim_expansion_factor: float = 4.0) -> Dict[str, Tuple[int, ...]]:

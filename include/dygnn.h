@@ -383,6 +383,54 @@ int dygnn_tgn_forward_levels(const dygnn_tgat_config* cfg_host, const dygnn_tgat
                              const int64_t* edge_ids /* [n_positive] */, int64_t batch, int64_t n_positive, float* out_src, float* out_dst,
                              void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * JODIE: MemoryModel.compute_src_dst_node_temporal_embeddings with model_name == 'JODIE' (models/MemoryModel.py:87-168, :519-545):
+ * nn.RNNCell memory update from the last pending raw message (RNNMemoryUpdater :504-515: h' = tanh(W_ih m + b_ih + W_hh h + b_hh)) and
+ * the time-projection embedding  emb = updated_memory * (1 + linear_layer(delta)),  delta = (float32(t) - updated_last_update - mean) / std
+ * in float32, the source pair of shift constants for source rows and the destination pair for destination rows (:111-124).  No
+ * neighbours, no sampler.  State, message layout and the commit of the positive pairs are TGN's (dygnn_tgn_state).
+ * A call reads only its roots: rows [src ; dst] of the batch, every row computed on its own (duplicates repeat the same bits), so the
+ * workspace does not depend on the number of nodes.  n_positive as in dygnn_tgn_forward_step: the first n_positive pairs persist their
+ * updated memories / last-update times and leave new raw messages (edge_ids [n_positive]); batch = a positive call, 0 = a negative call.
+ * Rows and state are bit-identical to the negative call followed by the positive call.  At most three launches (weight packing, the
+ * row kernel, the commit); inference only.
+ * Dimensions: node_feat_dim (= memory dim), time_feat_dim, edge_feat_dim multiples of 4 whose four-row block fits the LDS; others
+ * DYGNN_E_UNSUPPORTED, the message names the value.  cfg->num_layers / num_heads / num_neighbors are not read.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct dygnn_rnn_weights {          /* memory_updater.memory_updater.{weight_ih,weight_hh,bias_ih,bias_hh} of nn.RNNCell: one gate */
+    const float *weight_ih, *weight_hh;     /* [F_n, 2F_n+F_t+F_e], [F_n, F_n]                                                  */
+    const float *bias_ih, *bias_hh;         /* [F_n], [F_n]                                                                     */
+} dygnn_rnn_weights;
+
+size_t dygnn_jodie_workspace_bytes(const dygnn_tgat_config* cfg_host, int64_t num_nodes /* not used: the size depends on batch only */, int64_t batch);
+int dygnn_jodie_forward_step(const dygnn_tgat_config* cfg_host, const float* time_w, const float* time_b, const dygnn_rnn_weights* rnn_host,
+                             const float* proj_w /* embedding_module.linear_layer.weight [F_n, 1] */, const float* proj_b /* [F_n] */,
+                             double src_mean_time_shift, double src_std_time_shift, double dst_mean_time_shift, double dst_std_time_shift,
+                             const float* edge_feat, const dygnn_tgn_state* state_host, const int64_t* src, const int64_t* dst, const double* times,
+                             const int64_t* edge_ids /* [n_positive] */, int64_t batch, int64_t n_positive, float* out_src, float* out_dst,
+                             void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * DyRep: MemoryModel.compute_src_dst_node_temporal_embeddings with model_name == 'DyRep' (models/MemoryModel.py:73-83, :125-132, :163-166,
+ * :225-227): TGN's modules with the RNN cell (dygnn_rnn_weights).  A call returns the UPDATED MEMORIES of its roots (the cell output for a
+ * node with a pending message, the stored memory otherwise); the temporal attention runs for the first n_positive pairs only, where the
+ * attention embedding of the other endpoint of pair i replaces its memory in the new raw message.  n_positive = 0 (a negative call) runs no
+ * attention at all.  n_positive, state, chronological order, workspace and argument checks as for dygnn_tgn_forward_step; out_dst must
+ * follow out_src (one [2, batch, F_n] block).  dygnn_dyrep_forward_levels: the levels are those of the first n_positive pairs
+ * (dygnn_tgn_forward_levels' layout with batch = n_positive; not read when n_positive = 0).  Inference only.
+ * ---------------------------------------------------------------------------------------- */
+size_t dygnn_dyrep_workspace_bytes(const dygnn_tgat_config* cfg_host, int64_t num_nodes, int64_t batch);
+int dygnn_dyrep_forward_step(const dygnn_tgat_config* cfg_host, const dygnn_tgat_weights* w_host, const dygnn_rnn_weights* rnn_host,
+                             const dygnn_csr* csr_host, const float* node_feat, const float* edge_feat, const dygnn_tgn_state* state_host,
+                             const int64_t* src, const int64_t* dst, const double* times, const int64_t* edge_ids /* [n_positive] */,
+                             int64_t batch, int64_t n_positive, float* out_src, float* out_dst,
+                             void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
+int dygnn_dyrep_forward_levels(const dygnn_tgat_config* cfg_host, const dygnn_tgat_weights* w_host, const dygnn_rnn_weights* rnn_host,
+                               const dygnn_tgat_levels* levels_host, const float* node_feat, const float* edge_feat,
+                               const dygnn_tgn_state* state_host, const int64_t* src, const int64_t* dst, const double* times,
+                               const int64_t* edge_ids /* [n_positive] */, int64_t batch, int64_t n_positive, float* out_src, float* out_dst,
+                               void* workspace, size_t workspace_bytes, dygnn_stream_t stream);
+
 /* ---- training: train_link_prediction.py:229-257 on the HIP path ------------------------------------
  * dygnn_dygformer_train_forward = models/DyGFormer.py:68-194 in TRAIN mode: dropout (probability dropout_p) on the attention
  * probabilities, the attention output and the FFN (models/DyGFormer.py:429-431, :456-460), masks drawn from a counter-based

@@ -1,0 +1,432 @@
+"""dyglib_amd.JODIE and dyglib_amd.DyRep (dygnn_jodie_forward_step, dygnn_dyrep_forward_step / _levels; dyglib_amd/csrc/memory_rnn.hip, tgat.hip)
+on an MI355X: against the reference's own outputs (tests/golden/jodie_<case>.npz, dyrep_<case>[_<tag>].npz, eval_jodie.npz, eval_dyrep.npz) and,
+for shapes the fixtures do not cover, against tests/memory_variant_oracle.py.  Tolerance: tests.parity.close, 1e-4 absolute, as for TGN over
+the same chronological runs."""
+import numpy as np
+import pytest
+import torch
+
+from dyglib_amd import synthetic as syn
+from tests import golden_cases as gc
+from tests import memory_variant_cases as mv
+from tests import memory_variant_oracle as mo
+from tests.parity import close
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _model(node_feat, edge_feat, params, shifts, time_feat_dim=mv.TIME_FEAT_DIM):
+    from dyglib_amd import JODIE
+    m = JODIE(node_feat, edge_feat, None, time_feat_dim=time_feat_dim, src_node_mean_time_shift=shifts[0], src_node_std_time_shift=shifts[1],
+              dst_node_mean_time_shift_dst=shifts[2], dst_node_std_time_shift=shifts[3], device=DEV)
+    sd = m.state_dict()
+    sd.update({k: torch.from_numpy(v) for k, v in params.items()})
+    m.load_state_dict(sd, strict=True)
+    m = m.to(DEV).eval()
+    m.memory_bank.__init_memory_bank__()
+    return m
+
+
+def _case_model(c):
+    return _model(c["node_feat"], c["edge_feat"], c["params"], c["shifts"])
+
+
+def _bank(m):
+    mb = m.memory_bank
+    return [x.clone() for x in (mb.node_memories.data, mb.node_last_updated_times.data, mb.msg, mb.msg_time, mb.has_msg)]
+
+
+def _two_calls(m, b):
+    ns, nd = m.compute_src_dst_node_temporal_embeddings(b["src"], b["neg"], b["t"], edge_ids=None, edges_are_positive=False)
+    ps, pd = m.compute_src_dst_node_temporal_embeddings(b["src"], b["dst"], b["t"], edge_ids=b["eid"], edges_are_positive=True)
+    return ps, pd, ns, nd
+
+
+@pytest.fixture(scope="module", params=list(mv.CASES))
+def case(request):
+    return request.param, mv.build_case(request.param), gc.load_golden(request.param)
+
+
+def test_hip_matches_golden_and_replays_from_a_backup(case):
+    name, c, g = case
+    m = _case_model(c)
+    backup = None
+    with torch.no_grad():
+        for i, b in enumerate(c["batches"]):
+            if i == 2:
+                backup = m.memory_bank.backup_memory_bank()
+            ps, pd, ns, nd = _two_calls(m, b)
+            for tag, v in (("neg_src", ns), ("neg_dst", nd), ("pos_src", ps), ("pos_dst", pd)):
+                close(v.cpu().numpy(), g[f"b{i}_{tag}"], f"{name} batch {i} {tag}")
+        close(m.memory_bank.node_memories.data.cpu().numpy(), g["final_memory"], name + " memory")
+        close(m.memory_bank.node_last_updated_times.data.cpu().numpy(), g["final_last_update"], name + " last update")
+        # reload the backup taken before batch 2 and replay from there: same rows, same final bank (MemoryModel.py:345-366)
+        end = _bank(m)
+        m.memory_bank.reload_memory_bank(backup)
+        for i, b in enumerate(c["batches"][2:], start=2):
+            ps, pd, ns, nd = _two_calls(m, b)
+            close(ps.cpu().numpy(), g[f"b{i}_pos_src"], f"{name} replay batch {i} pos_src")
+            close(nd.cpu().numpy(), g[f"b{i}_neg_dst"], f"{name} replay batch {i} neg_dst")
+        assert all(torch.equal(x, y) for x, y in zip(end, _bank(m)))
+        b = c["batches"][0]
+        with pytest.raises(AssertionError):
+            m.compute_src_dst_node_temporal_embeddings(b["src"], b["dst"], b["t"], edge_ids=None, edges_are_positive=True)
+        with pytest.raises(IndexError):
+            m.compute_src_dst_node_temporal_embeddings(b["src"], b["dst"] + m.num_nodes, b["t"], edge_ids=b["eid"], edges_are_positive=True)
+        with pytest.raises(IndexError):
+            m.compute_src_dst_node_temporal_embeddings(b["src"], b["dst"], b["t"], edge_ids=b["eid"] + c["edge_feat"].shape[0], edges_are_positive=True)
+
+
+def test_fused_and_joint_steps_equal_the_two_calls(case):
+    """compute_step_embeddings / compute_step_embeddings_joint ([positives ; negatives] in one library call, the first rows update the state) are
+    bit-identical, in their rows and in the whole bank they leave, to the negative call followed by the positive call"""
+    name, c, g = case
+    two, four, joint = _case_model(c), _case_model(c), _case_model(c)
+    with torch.no_grad():
+        for b in c["batches"]:
+            n = len(b["src"])
+            ref = _two_calls(two, b)
+            got = four.compute_step_embeddings(b["src"], b["dst"], b["src"], b["neg"], b["t"], b["eid"])
+            js, jd = joint.compute_step_embeddings_joint(np.concatenate([b["src"], b["src"]]), np.concatenate([b["dst"], b["neg"]]),
+                                                         np.concatenate([b["t"], b["t"]]), b["eid"], n)
+            for x, y in zip(ref, got):
+                assert torch.equal(x, y)
+            for x, y in zip(ref, (js[:n], jd[:n], js[n:], jd[n:])):
+                assert torch.equal(x, y)
+            for x, y, z in zip(_bank(two), _bank(four), _bank(joint)):
+                assert torch.equal(x, y) and torch.equal(x, z)
+
+
+def test_rows_and_state_do_not_depend_on_the_workgroup_shapes(monkeypatch):
+    """rows per workgroup (DYGNN_RNN_MT) and memory-dim slices (DYGNN_RNN_SLICES) of the RNN row kernel, the switches the GRU kernel has under
+    its own name: rows and the bank left behind are bit-identical for every choice"""
+    c = mv.build_case("jodie_hub")
+
+    def run(env):
+        for k_, v in env.items():
+            monkeypatch.setenv(k_, v)
+        m = _case_model(c)
+        outs = []
+        with torch.no_grad():
+            for b in c["batches"]:
+                outs.append(torch.cat(m.compute_step_embeddings(b["src"], b["dst"], b["src"], b["neg"], b["t"], b["eid"])))
+        for k_ in env:
+            monkeypatch.delenv(k_)
+        return [torch.cat(outs)] + _bank(m)
+
+    base = run({})
+    assert base[0].abs().max() > 0.5
+    for env in ({"DYGNN_RNN_MT": "2", "DYGNN_RNN_SLICES": "1"}, {"DYGNN_RNN_MT": "4", "DYGNN_RNN_SLICES": "3"}, {"DYGNN_RNN_MT": "1", "DYGNN_RNN_SLICES": "6"},
+                {"DYGNN_RNN_MT": "8", "DYGNN_RNN_SLICES": "5"}):
+        assert all(torch.equal(x, y) for x, y in zip(base, run(env))), env
+
+
+def _against_oracle(m, params, edge_feat, shifts, batches, what):
+    p, ef = {k: torch.from_numpy(v) for k, v in params.items()}, torch.from_numpy(edge_feat)
+    st = mo.MemoryState(m.num_nodes, m.memory_dim, m.message_dim)
+    pend = []
+    with torch.no_grad():
+        for i, b in enumerate(batches):
+            roots = np.concatenate([b["src"], b["neg"], b["src"], b["dst"]])
+            pend.append(int(st.has[roots].sum()))
+            got = m.compute_step_embeddings(b["src"], b["dst"], b["src"], b["neg"], b["t"], b["eid"])
+            ons, ond = mo.jodie_forward(p, ef, st, b["src"], b["neg"], b["t"], None, False, shifts)
+            ops, opd = mo.jodie_forward(p, ef, st, b["src"], b["dst"], b["t"], b["eid"], True, shifts)
+            for x, y, tag in zip(got, (ops, opd, ons, ond), ("pos src", "pos dst", "neg src", "neg dst")):
+                close(x.cpu().numpy(), y.numpy(), f"{what} batch {i} {tag}", label=f"{what} {tag}")
+    close(m.memory_bank.node_memories.data.cpu().numpy(), st.M.numpy(), what + " memory")
+    close(m.memory_bank.node_last_updated_times.data.cpu().numpy(), st.U.numpy(), what + " last update")
+    close(m.memory_bank.msg.cpu().numpy(), st.msg.numpy(), what + " pending messages")
+    assert np.array_equal(m.memory_bank.has_msg.cpu().numpy() != 0, st.has) and np.array_equal(m.memory_bank.msg_time.cpu().numpy()[st.has], st.msg_t[st.has])
+    return pend
+
+
+def test_hand_made_batches_against_oracle():
+    c = mv.build_case("jodie_hub")
+    src, dst, t, eid = c["src"], c["dst"], c["t"], c["eid"]
+    i64 = lambda *x: np.array(x, dtype=np.int64)
+
+    def batch(sl, neg):
+        return dict(src=src[sl].copy(), dst=dst[sl].copy(), t=t[sl].copy(), eid=eid[sl].copy(), neg=np.asarray(neg, dtype=np.int64))
+    # B = 1, twice (the second call finds both nodes pending)
+    b1 = [batch(slice(0, 1), [dst[5]]), batch(slice(1, 2), [dst[0]])]
+    _against_oracle(_case_model(c), c["params"], c["edge_feat"], c["shifts"], b1, "jodie B=1")
+    # B = 5 with src[i] == dst[i] in one row, then a batch whose negative destination is one of its positive roots
+    b5 = batch(slice(0, 5), dst[5:10])
+    b5["dst"][2] = b5["src"][2]
+    b5b = batch(slice(5, 10), dst[0:5])
+    b5b["neg"][1] = b5b["src"][3]
+    b5b["neg"][4] = b5b["dst"][0]
+    _against_oracle(_case_model(c), c["params"], c["edge_feat"], c["shifts"], [b5, b5b, batch(slice(10, 15), dst[0:5])], "jodie B=5")
+    # B = 7 on the hub graph, three batches: pending root rows 0, odd, and more than 4
+    # (the second batch's first negative is a node no earlier batch touched)
+    b7 = [batch(slice(0, 7), i64(*dst[20:27])), batch(slice(7, 14), i64(src[20], *dst[1:7])), batch(slice(14, 21), i64(*dst[7:14]))]
+    pend = _against_oracle(_case_model(c), c["params"], c["edge_feat"], c["shifts"], b7, "jodie B=7")
+    assert pend[0] == 0 and pend[1] % 2 == 1 and pend[2] > 4, pend
+
+
+def test_other_feature_dims_against_oracle():
+    """dims that are no multiples of the 16-wide tiles (memory 40 = 2.5 tiles over the slices, edge 24, time 20: message 124)"""
+    Fn, Fe, Ft, B = 40, 24, 20, 50
+    data, nf, ef = syn.make_bipartite_graph(120, 30, 2000, seed=47, edge_feat_dim=Fe, duplicate_time_every=9)
+    nf = np.ascontiguousarray(nf[:, :Fn])
+    params = syn.make_jodie_params(31, node_feat_dim=Fn, edge_feat_dim=Fe, time_feat_dim=Ft)
+    s, d, t, e = data.src_node_ids, data.dst_node_ids, data.node_interact_times, data.edge_ids
+    shifts = tuple(float(x) for x in mv.reference_time_shifts(s[:1400], d[:1400], t[:1400]))
+    rs, ud = np.random.RandomState(3), np.unique(d)
+    batches = [dict(src=s[i * B:(i + 1) * B], dst=d[i * B:(i + 1) * B], t=t[i * B:(i + 1) * B], eid=e[i * B:(i + 1) * B], neg=syn.random_negative_dst(rs, ud, B))
+               for i in range(5)]
+    _against_oracle(_model(nf, ef, params, shifts, time_feat_dim=Ft), params, ef, shifts, batches, "jodie other dims")
+
+
+def test_mid_size_batches_against_oracle():
+    """TGN's mid-size shape: 700 x 60 bipartite, B = 200, 8 chronological batches from interaction 0 with the memory carried across them: all
+    four blocks per batch and the bank left behind, against the oracle"""
+    B, NB = 200, 8
+    data, nf, ef = syn.make_bipartite_graph(700, 60, 40_000, seed=11, edge_feat_kind="sparse4", duplicate_time_every=13)
+    params = syn.make_jodie_params(5)
+    s, d, t, e = data.src_node_ids, data.dst_node_ids, data.node_interact_times, data.edge_ids
+    from dyglib_amd import compute_src_dst_node_time_shifts
+    shifts = tuple(float(x) for x in compute_src_dst_node_time_shifts(s[:28_000], d[:28_000], t[:28_000]))
+    rs, ud = np.random.RandomState(2), np.unique(d)
+    batches = [dict(src=s[i * B:(i + 1) * B], dst=d[i * B:(i + 1) * B], t=t[i * B:(i + 1) * B], eid=e[i * B:(i + 1) * B], neg=syn.random_negative_dst(rs, ud, B))
+               for i in range(NB)]
+    _against_oracle(_model(nf, ef, params, shifts), params, ef, shifts, batches, f"jodie mid-size (B=200, {NB} batches)")
+
+
+def test_evaluation_loop_matches_reference():
+    from dyglib_amd import Data, MergeLayer, NegativeEdgeSampler, evaluate_memory_model_link_prediction, get_idx_data_loader
+    r = mv.EVAL_CASE
+    c = mv.build_case(r["case"])
+    g = gc.load_golden("eval_jodie")
+    first, last = gc.eval_indices(len(c["src"]))
+    sl = slice(first, last)
+    eval_data = Data(c["src"][sl], c["dst"][sl], c["t"][sl], c["eid"][sl], c["labels"][sl])
+    neg = NegativeEdgeSampler(c["src"], c["dst"], seed=gc.EVAL_NEG_SEED)
+    draws = np.concatenate([neg.sample(size=min(r["batch"], last - first - i))[1] for i in range(0, last - first, r["batch"])])
+    assert np.array_equal(draws, g["neg_dst"])                                                  # the negative draws are the reference's, exactly
+    merge = MergeLayer(172, 172, 172, 1)
+    merge.load_state_dict({k: torch.from_numpy(v) for k, v in c["mparams"].items()})
+    model = torch.nn.Sequential(_case_model(c), merge).to(DEV)
+    idx = np.arange(last - first)
+    loaders = {"index tensors": get_idx_data_loader(list(idx), r["batch"], shuffle=False),
+               "device tensors": [torch.from_numpy(idx[i:i + r["batch"]]).to(DEV) for i in range(0, len(idx), r["batch"])],
+               "numpy": [idx[i:i + r["batch"]] for i in range(0, len(idx), r["batch"])]}
+    seen = []
+    for what, loader in loaders.items():
+        model[0].memory_bank.__init_memory_bank__()
+        losses, metrics = evaluate_memory_model_link_prediction("JODIE", model, None, loader, neg, eval_data, torch.nn.BCELoss())
+        assert len(losses) == len(metrics) == len(g["losses"]) and all(isinstance(x, float) for x in losses), what
+        assert np.abs(np.array(losses) - g["losses"]).max() <= 1e-5, what                      # the bounds tests/test_evaluate.py holds TGN to
+        assert np.abs(np.array([m["roc_auc"] for m in metrics]) - g["roc_auc"]).max() <= 2e-3, what
+        assert np.abs(np.array([m["average_precision"] for m in metrics]) - g["average_precision"]).max() <= 1e-2, what
+        seen.append((losses, metrics))
+    assert seen[0] == seen[1] == seen[2]
+
+
+# ---- DyRep ---------------------------------------------------------------------------------------------------------------------
+def _dyrep(c, tag=None, nf=None, ef=None, params=None):
+    from dyglib_amd import DyRep, get_neighbor_sampler
+    cfg = c["cfg"]
+    strategy, seed, tsf = gc.SAMPLING_STRATEGIES[tag] if tag else ("recent", 1, 0.0)
+    sampler = get_neighbor_sampler(c["data"], strategy, time_scaling_factor=tsf, seed=seed, device=DEV)
+    m = DyRep(c["node_feat"], c["edge_feat"], sampler, time_feat_dim=cfg["time_feat_dim"], num_layers=cfg["num_layers"], num_heads=cfg["num_heads"],
+              dropout=0.1, device=DEV)
+    sd = m.state_dict()
+    sd.update({k: torch.from_numpy(v) for k, v in c["params"].items()})
+    m.load_state_dict(sd, strict=True)
+    m = m.to(DEV).eval()
+    m.set_neighbor_sampler(sampler)              # resets a random sampler's RandomState (MemoryModel.py:253-263)
+    m.memory_bank.__init_memory_bank__()
+    return m, sampler
+
+
+def _dyrep_two_calls(m, b, k):
+    ns, nd = m.compute_src_dst_node_temporal_embeddings(b["src"], b["neg"], b["t"], edge_ids=None, edges_are_positive=False, num_neighbors=k)
+    ps, pd = m.compute_src_dst_node_temporal_embeddings(b["src"], b["dst"], b["t"], edge_ids=b["eid"], edges_are_positive=True, num_neighbors=k)
+    return ps, pd, ns, nd
+
+
+@pytest.fixture(scope="module", params=list(mv.DYREP_CASES))
+def dyrep_case(request):
+    return request.param, mv.build_dyrep_case(request.param)
+
+
+@pytest.mark.parametrize("tag", [None, *mv.DYREP_RANDOM_TAGS])
+def test_dyrep_matches_golden(dyrep_case, tag):
+    """`recent`, and the random strategies: the negative call's draws are replayed and thrown away, so the RandomState stream -- and with it
+    every later positive call's neighbours, messages and memories -- is the reference's"""
+    name, c = dyrep_case
+    g = gc.load_golden(name + ("_" + tag if tag else ""))
+    m, _ = _dyrep(c, tag)
+    k = c["cfg"]["num_neighbors"]
+    what = f"{name}/{tag or 'recent'}"
+    backup = None
+    with torch.no_grad():
+        for i, b in enumerate(c["batches"]):
+            if i == 2 and tag is None:
+                backup = m.memory_bank.backup_memory_bank()
+            if i % 2 == 0:
+                ps, pd, ns, nd = _dyrep_two_calls(m, b, k)
+            else:                                # the step entry point: the fused step under `recent`, the two calls in the reference's order otherwise
+                ps, pd, ns, nd = m.compute_step_embeddings(b["src"], b["dst"], b["src"], b["neg"], b["t"], b["eid"], num_neighbors=k)
+            for key, v in (("neg_src", ns), ("neg_dst", nd), ("pos_src", ps), ("pos_dst", pd)):
+                close(v.cpu().numpy(), g[f"b{i}_{key}"], f"{what} batch {i} {key}")
+        close(m.memory_bank.node_memories.data.cpu().numpy(), g["final_memory"], what + " memory")
+        close(m.memory_bank.node_last_updated_times.data.cpu().numpy(), g["final_last_update"], what + " last update")
+        if tag is None:                          # backup / reload / replay round trip
+            end = _bank(m)
+            m.memory_bank.reload_memory_bank(backup)
+            for i, b in enumerate(c["batches"][2:], start=2):
+                ps, pd, ns, nd = _dyrep_two_calls(m, b, k)
+                close(ps.cpu().numpy(), g[f"b{i}_pos_src"], f"{what} replay batch {i} pos_src")
+            assert all(torch.equal(x, y) for x, y in zip(end, _bank(m)))
+            with pytest.raises(AssertionError):
+                m.compute_src_dst_node_temporal_embeddings(b["src"], b["dst"], b["t"], edge_ids=None, edges_are_positive=True, num_neighbors=k)
+            with pytest.raises(IndexError):
+                m.compute_src_dst_node_temporal_embeddings(b["src"], b["dst"] + m.num_nodes, b["t"], edge_ids=b["eid"], edges_are_positive=True, num_neighbors=k)
+        else:
+            with pytest.raises(NotImplementedError):
+                m.compute_step_embeddings_joint(np.concatenate([b["src"], b["src"]]), np.concatenate([b["dst"], b["neg"]]), np.concatenate([b["t"], b["t"]]),
+                                                b["eid"], len(b["src"]), num_neighbors=k)
+
+
+def test_dyrep_fused_and_joint_steps_equal_the_two_calls(dyrep_case, monkeypatch):
+    name, c = dyrep_case
+    k = c["cfg"]["num_neighbors"]
+    (two, _), (four, _), (joint, _) = _dyrep(c), _dyrep(c), _dyrep(c)
+    rows = []
+    with torch.no_grad():
+        for b in c["batches"]:
+            n = len(b["src"])
+            ref = _dyrep_two_calls(two, b, k)
+            got = four.compute_step_embeddings(b["src"], b["dst"], b["src"], b["neg"], b["t"], b["eid"], num_neighbors=k)
+            js, jd = joint.compute_step_embeddings_joint(np.concatenate([b["src"], b["src"]]), np.concatenate([b["dst"], b["neg"]]),
+                                                         np.concatenate([b["t"], b["t"]]), b["eid"], n, num_neighbors=k)
+            for x, y in zip(ref, got):
+                assert torch.equal(x, y)
+            for x, y in zip(ref, (js[:n], jd[:n], js[n:], jd[n:])):
+                assert torch.equal(x, y)
+            for x, y, z in zip(_bank(two), _bank(four), _bank(joint)):
+                assert torch.equal(x, y) and torch.equal(x, z)
+            rows.append(torch.cat(got))
+    # rows and bank do not depend on rows per workgroup / slices of the two RNN kernels (nor on the chain kernels' rows per workgroup)
+    monkeypatch.setenv("DYGNN_RNN_MT", "2"); monkeypatch.setenv("DYGNN_RNN_SLICES", "3"); monkeypatch.setenv("DYGNN_CHAIN_MT", "2")
+    other, _ = _dyrep(c)
+    with torch.no_grad():
+        for b, want in zip(c["batches"], rows):
+            assert torch.equal(torch.cat(other.compute_step_embeddings(b["src"], b["dst"], b["src"], b["neg"], b["t"], b["eid"], num_neighbors=k)), want)
+    assert all(torch.equal(x, y) for x, y in zip(_bank(two), _bank(other)))
+
+
+def test_dyrep_mid_size_batches_against_oracle():
+    """TGN's mid-size shape (700 x 60 bipartite, B = 200, k = 10, 1 layer, 8 batches): four blocks per batch and the bank against the oracle"""
+    from dyglib_amd import DyRep, get_neighbor_sampler
+    from oracle import dygformer_oracle as orc
+    B, NB, K = 200, 8, 10
+    data, nf, ef = syn.make_bipartite_graph(700, 60, 40_000, seed=11, edge_feat_kind="sparse4", duplicate_time_every=13)
+    params = syn.make_dyrep_params(5, nf.shape[0], num_layers=1)
+    sampler = get_neighbor_sampler(data, "recent", seed=1, device=DEV)
+    m = DyRep(nf, ef, sampler, 100, num_layers=1, num_heads=2, dropout=0.1, device=DEV)
+    sd = m.state_dict(); sd.update({k: torch.from_numpy(v) for k, v in params.items()}); m.load_state_dict(sd, strict=True)
+    m = m.to(DEV).eval()
+    m.memory_bank.__init_memory_bank__()
+    adj = orc.OracleAdjacency(data.src_node_ids, data.dst_node_ids, data.edge_ids, data.node_interact_times)
+    p, nft, eft = {k: torch.from_numpy(v) for k, v in params.items()}, torch.from_numpy(nf), torch.from_numpy(ef)
+    st = mo.MemoryState(nf.shape[0], 172, m.message_dim)
+    rs, ud = np.random.RandomState(2), np.unique(data.dst_node_ids)
+    with torch.no_grad():
+        for i in range(NB):
+            sl = slice(i * B, (i + 1) * B)
+            s, d, t, e = data.src_node_ids[sl], data.dst_node_ids[sl], data.node_interact_times[sl], data.edge_ids[sl]
+            ng = syn.random_negative_dst(rs, ud, B)
+            got = m.compute_step_embeddings(s, d, s, ng, t, e, num_neighbors=K)
+            ons, ond = mo.dyrep_forward(p, nft, eft, adj, st, s, ng, t, None, False, 1, K)
+            ops, opd = mo.dyrep_forward(p, nft, eft, adj, st, s, d, t, e, True, 1, K)
+            for x, y, tag in zip(got, (ops, opd, ons, ond), ("pos src", "pos dst", "neg src", "neg dst")):
+                close(x.cpu().numpy(), y.numpy(), f"dyrep mid-size batch {i} {tag}", label=f"dyrep mid-size {tag}")
+    close(m.memory_bank.node_memories.data.cpu().numpy(), st.M.numpy(), "dyrep mid-size memory")
+    close(m.memory_bank.node_last_updated_times.data.cpu().numpy(), st.U.numpy(), "dyrep mid-size last update")
+    close(m.memory_bank.msg.cpu().numpy(), st.msg.numpy(), "dyrep mid-size pending messages")
+
+
+def test_dyrep_evaluation_loop_matches_reference():
+    from dyglib_amd import Data, MergeLayer, NegativeEdgeSampler, evaluate_memory_model_link_prediction, get_idx_data_loader
+    r = mv.DYREP_EVAL_CASE
+    c = mv.build_dyrep_case(r["case"])
+    g = gc.load_golden("eval_dyrep")
+    d = c["data"]
+    first, last = gc.eval_indices(d.num_interactions)
+    sl = slice(first, last)
+    eval_data = Data(d.src_node_ids[sl], d.dst_node_ids[sl], d.node_interact_times[sl], d.edge_ids[sl], d.labels[sl])
+    neg = NegativeEdgeSampler(d.src_node_ids, d.dst_node_ids, seed=gc.EVAL_NEG_SEED)
+    draws = np.concatenate([neg.sample(size=min(r["batch"], last - first - i))[1] for i in range(0, last - first, r["batch"])])
+    assert np.array_equal(draws, g["neg_dst"])
+    backbone, sampler = _dyrep(c)
+    merge = MergeLayer(172, 172, 172, 1)
+    merge.load_state_dict({k: torch.from_numpy(v) for k, v in c["mparams"].items()})
+    model = torch.nn.Sequential(backbone, merge).to(DEV)
+    idx = np.arange(last - first)
+    seen = []
+    for what, loader in (("index tensors", get_idx_data_loader(list(idx), r["batch"], shuffle=False)),
+                         ("device tensors", [torch.from_numpy(idx[i:i + r["batch"]]).to(DEV) for i in range(0, len(idx), r["batch"])]),
+                         ("numpy", [idx[i:i + r["batch"]] for i in range(0, len(idx), r["batch"])])):
+        model[0].memory_bank.__init_memory_bank__()
+        losses, metrics = evaluate_memory_model_link_prediction("DyRep", model, sampler, loader, neg, eval_data, torch.nn.BCELoss(),
+                                                                num_neighbors=c["cfg"]["num_neighbors"])
+        assert len(losses) == len(g["losses"]), what
+        assert np.abs(np.array(losses) - g["losses"]).max() <= 1e-5, what
+        assert np.abs(np.array([m["roc_auc"] for m in metrics]) - g["roc_auc"]).max() <= 2e-3, what
+        assert np.abs(np.array([m["average_precision"] for m in metrics]) - g["average_precision"]).max() <= 1e-2, what
+        seen.append((losses, metrics))
+    assert seen[0] == seen[1] == seen[2]
+
+
+def _dyrep_against_oracle(c, batches, what):
+    """the fused step per batch against mo.dyrep_forward: four blocks, then memory, last update, pending messages, their times and flags"""
+    from oracle import dygformer_oracle as orc
+    d, cfg = c["data"], c["cfg"]
+    m, _ = _dyrep(c)
+    p, nf, ef = {k: torch.from_numpy(v) for k, v in c["params"].items()}, torch.from_numpy(c["node_feat"]), torch.from_numpy(c["edge_feat"])
+    adj = orc.OracleAdjacency(d.src_node_ids, d.dst_node_ids, d.edge_ids, d.node_interact_times)
+    st = mo.MemoryState(m.num_nodes, m.memory_dim, m.message_dim)
+    L, k = cfg["num_layers"], cfg["num_neighbors"]
+    pend = []
+    with torch.no_grad():
+        for i, b in enumerate(batches):
+            pend.append(int(st.has[np.concatenate([b["src"], b["neg"], b["src"], b["dst"]])].sum()))
+            got = m.compute_step_embeddings(b["src"], b["dst"], b["src"], b["neg"], b["t"], b["eid"], num_neighbors=k)
+            ons, ond = mo.dyrep_forward(p, nf, ef, adj, st, b["src"], b["neg"], b["t"], None, False, L, k)
+            ops, opd = mo.dyrep_forward(p, nf, ef, adj, st, b["src"], b["dst"], b["t"], b["eid"], True, L, k)
+            for x, y, tag in zip(got, (ops, opd, ons, ond), ("pos src", "pos dst", "neg src", "neg dst")):
+                close(x.cpu().numpy(), y.numpy(), f"{what} batch {i} {tag}", label=f"{what} {tag}")
+    close(m.memory_bank.node_memories.data.cpu().numpy(), st.M.numpy(), what + " memory")
+    close(m.memory_bank.node_last_updated_times.data.cpu().numpy(), st.U.numpy(), what + " last update")
+    close(m.memory_bank.msg.cpu().numpy(), st.msg.numpy(), what + " pending messages")
+    assert np.array_equal(m.memory_bank.has_msg.cpu().numpy() != 0, st.has) and np.array_equal(m.memory_bank.msg_time.cpu().numpy()[st.has], st.msg_t[st.has])
+    return pend
+
+
+@pytest.mark.parametrize("name", ["dyrep_hub", "dyrep_gen"])          # one layer, k = 10 on the hub graph; two layers, k = 4 (de-duplicated level 1)
+def test_dyrep_hand_made_batches_against_oracle(name):
+    """the shapes where DyRep's own code differs from JODIE's: k_rnn_list, the owner / list pass and the levels with n_positive = 1, a pair with
+    src == dst (the commit takes the other endpoint from the pair's own attention rows), a negative destination that is a positive root (covered
+    by the per-root rows, not by the lists), and three B = 7 batches with 0, an odd number of, and more than 4 pending root rows"""
+    c = mv.build_dyrep_case(name)
+    d = c["data"]
+    src, dst, t, eid = d.src_node_ids, d.dst_node_ids, d.node_interact_times, d.edge_ids
+
+    def batch(sl, neg):
+        return dict(src=src[sl].copy(), dst=dst[sl].copy(), t=t[sl].copy(), eid=eid[sl].copy(), neg=np.asarray(neg, dtype=np.int64))
+    _dyrep_against_oracle(c, [batch(slice(0, 1), [dst[5]]), batch(slice(1, 2), [dst[0]]), batch(slice(2, 3), [src[0]])], f"{name} B=1")
+    b5 = batch(slice(0, 5), dst[5:10])
+    b5["dst"][2] = b5["src"][2]
+    b5b = batch(slice(5, 10), dst[0:5])
+    b5b["neg"][1] = b5b["src"][3]
+    b5b["neg"][4] = b5b["dst"][0]
+    _dyrep_against_oracle(c, [b5, b5b, batch(slice(10, 15), dst[0:5])], f"{name} B=5")
+    if name == "dyrep_hub":          # (the second batch's first two negatives are nodes no earlier batch touched)
+        b7 = [batch(slice(0, 7), dst[20:27]), batch(slice(7, 14), [src[20], src[19], *dst[2:7]]), batch(slice(14, 21), dst[7:14])]
+        pend = _dyrep_against_oracle(c, b7, f"{name} B=7")
+        assert pend[0] == 0 and pend[1] % 2 == 1 and pend[2] > 4, pend
