@@ -160,6 +160,21 @@ class DygformerTaps(C.Structure):
                 ("phase_cycles", C.c_void_p), ("ev_kernel_start", C.c_void_p), ("ev_kernel_stop", C.c_void_p)]
 
 
+class MmArgs(C.Structure):
+    """dygnn_mm_args: the parameters of the general GEMM (include/dygnn.h)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("A", "B", "C", "bias", "colsum_out", "m_dev", "a_rows")]
+                + [(n, C.c_int64) for n in ("sAb", "sAh", "sBb", "sBh", "sCb", "sCh")]
+                + [(n, C.c_int32) for n in ("lda", "ldb", "ldc", "M", "N", "K", "batch", "H")]
+                + [("alpha", C.c_float), ("beta", C.c_float)]
+                + [(n, C.c_int32) for n in ("tA", "tB", "relu", "c_is_zero", "a_kpad")])
+
+
+class DwPair(C.Structure):
+    """dygnn_dw_pair: one problem of the grouped weight-gradient product."""
+    _fields_ = [("A", C.c_void_p), ("lda", C.c_int32), ("M", C.c_int32), ("B", C.c_void_p), ("ldb", C.c_int32), ("N", C.c_int32),
+                ("C", C.c_void_p), ("ldc", C.c_int32), ("colsum", C.c_void_p)]
+
+
 # name -> (restype, argtypes).  Every symbol include/dygnn.h declares; tests check the export list.
 SIGNATURES = {
     "dygnn_last_error": (C.c_char_p, []),
@@ -299,6 +314,11 @@ SIGNATURES = {
                                        C.c_int64, C.c_void_p, C.c_void_p]),
     "dygnn_edgebank_evaluate": (C.c_int, [C.POINTER(EdgeBank), C.c_void_p, C.c_void_p, C.c_void_p, c_i64p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "dygnn_mm": (C.c_int, [C.POINTER(MmArgs), C.c_void_p]),
+    "dygnn_mm_path": (C.c_int32, [C.POINTER(MmArgs)]),
+    "dygnn_mm_plan": (C.c_int32, [C.POINTER(MmArgs), c_i32p, c_i32p]),
+    "dygnn_mm_gathers_rows": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "dygnn_dw_grouped": (C.c_int, [C.c_int32, C.POINTER(DwPair), C.c_int32, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

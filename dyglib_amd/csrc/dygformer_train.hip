@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void k_mm(const MM p) {
     }
 }
 
-// The large products: 128 x (32*WN) tile per workgroup, 4 waves as 2 x 2, each wave 4 x WN accumulator tiles; operands go
+// The large products: (32*WM) x (32*WN) tile per workgroup (instantiated as 64 x 64 only), 4 waves as 2 x 2, each wave WM x WN accumulator tiles; operands go
 // through LDS in k-major layout ([16 k][tile + 4]) with float4 global loads when pointers / leading dimensions allow
 // (vecA / vecB), so one k-step of 16 costs a wave 8 or 6 LDS reads per 16 or 8 MFMAs instead of k_mm's 5 per 4.
 template <int WN, int WM>
@@ -420,37 +420,31 @@ static void launch_mm_dma(hipStream_t s, const MM& p, bool tA, bool tB, int batc
 
 static int colsum(hipStream_t s, const float* A, int lda, int64_t M, int N, float* out, bool accumulate = false);
 
-bool mm_gathers_rows(const float* A, int lda, const float* B, int ldb, int M, int N, int K) {
-    const char* dma_env = getenv("DYGNN_MM_DMA");
-    return M >= 48 && N >= 48 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && lda % 4 == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0 && ldb % 4 == 0 &&
-           K % 4 == 0 && !(dma_env && dma_env[0] == '0');
-}
-
-int mm(hipStream_t s, const float* A, int lda, bool tA, const float* B, int ldb, bool tB, float* C, int ldc, int M, int N, int K, const float* bias, float alpha,
-       float beta, int batch, int H, int64_t sAb, int64_t sAh, int64_t sBb, int64_t sBh, int64_t sCb, int64_t sCh, bool relu, bool c_is_zero, float* colsum_out, const int32_t* m_dev, bool a_kpad,
-       const int32_t* a_rows) {
-    if (M <= 0 || N <= 0 || batch <= 0) return DYGNN_OK;
-    MM p{A, B, C, bias, M, N, K, lda, ldb, ldc, tA ? 1 : 0, tB ? 1 : 0, alpha, beta, H, sAb, sAh, sBb, sBh, sCb, sCh, relu ? 1 : 0, 1, K, nullptr, m_dev,
-         ((reinterpret_cast<uintptr_t>(C) & 15) == 0 && ldc % 4 == 0 && sCb % 4 == 0 && sCh % 4 == 0) ? 1 : 0, a_rows};
-    if (colsum_out) {                 // rides along inside the 64-row-tile kernel; anything else gets the stand-alone reduction
-        if (tA && batch == 1 && M >= 48 && N >= 48) p.colsum = colsum_out;
-        else if (int rc = colsum(s, A, lda, K, M, colsum_out)) return rc;
-    }
+// The whole dispatch of mm(), host only: which kernel, how many K parts, which epilogue, where the column sums are made -- or the refusal.
+// mm() launches what this returns and dygnn_mm_path reports it, so the two cannot disagree.
+int mm_plan(const float* A, int lda, bool tA, const float* B, int ldb, bool tB, const float* C, int ldc, int M, int N, int K, float beta, int batch, int64_t sAb,
+            int64_t sAh, int64_t sBb, int64_t sBh, int64_t sCb, int64_t sCh, bool relu, bool has_colsum, bool a_kpad, bool has_rows, MmPlan* out) {
+    MmPlan pl{};
+    pl.ksplit = 1;
+    pl.kchunk = K;
+    if (M <= 0 || N <= 0 || batch <= 0) { *out = pl; return DYGNN_OK; }
+    if (has_colsum && !tA) { set_error("mm: column sums need a transposed A (op(A)[m][k] = A[k * lda + m])"); return DYGNN_E_UNSUPPORTED; }
+    if (has_colsum && batch != 1) { set_error("mm: column sums need batch == 1"); return DYGNN_E_UNSUPPORTED; }
+    if (has_rows && tA) { set_error("mm: a row table needs a k-contiguous A (!tA)"); return DYGNN_E_UNSUPPORTED; }
     // weight gradients: small output, K = all rows of the call -> split K over workgroups, partial sums meet by atomicAdd
     if (batch == 1 && K >= 2048 && !relu) {
-        p.kchunk = 256;
-        p.ksplit = (K + p.kchunk - 1) / p.kchunk;
-        if (beta == 0.f && !c_is_zero) DYGNN_HIP(hipMemset2DAsync(C, (size_t)ldc * sizeof(float), 0, (size_t)N * sizeof(float), (size_t)M, s));
-        p.beta = 0.f;
+        if (beta != 0.f && beta != 1.f) { set_error("mm: a product split over K (K >= 2048) takes beta 0 or 1"); return DYGNN_E_UNSUPPORTED; }
+        pl.kchunk = 256;
+        pl.ksplit = (K + pl.kchunk - 1) / pl.kchunk;
     }
-    batch *= p.ksplit;
+    pl.vecC = ((reinterpret_cast<uintptr_t>(C) & 15) == 0 && ldc % 4 == 0 && sCb % 4 == 0 && sCh % 4 == 0) ? 1 : 0;
+    pl.vecA = ((reinterpret_cast<uintptr_t>(A) & 15) == 0 && lda % 4 == 0 && sAb % 4 == 0 && sAh % 4 == 0) ? 1 : 0;
+    pl.vecB = ((reinterpret_cast<uintptr_t>(B) & 15) == 0 && ldb % 4 == 0 && sBb % 4 == 0 && sBh % 4 == 0) ? 1 : 0;
     if (M >= 48 && N >= 48) {
-        const int vecA = ((reinterpret_cast<uintptr_t>(A) & 15) == 0 && lda % 4 == 0 && sAb % 4 == 0 && sAh % 4 == 0) ? 1 : 0;
-        const int vecB = ((reinterpret_cast<uintptr_t>(B) & 15) == 0 && ldb % 4 == 0 && sBb % 4 == 0 && sBh % 4 == 0) ? 1 : 0;
         // Tile choice, measured on the TGAT / TGN / training shapes (M = 50 .. 270,000, N = 136 .. 800, K = 136 .. 25,600 split):
         //  * 64-row tiles always: the k-loop is latency-bound (one global -> LDS hop per 16-wide k-step), so what pays is more resident
         //    workgroups per CU, not more MFMAs per LDS read; 128-row tiles were slower at every size (TGAT -7 %, training -5 %);
-        //  * 64-column tiles unless 128-column tiles pad clearly less (N = 272 pads to 320 instead of 384): TGN +38 %, TGAT +14 %.
+        //  * 64-column tiles always: ceil(N / 128) * 128 >= ceil(N / 64) * 64, so 128-column tiles never pad less.
         // both operands by LDS-DMA when no float4 can straddle a bound (see k_mm_dma)
         const char* dma_env = getenv("DYGNN_MM_DMA");
         // (Measured and not kept, round 2: the 32 x 208-per-wave register tile of k_dw_grouped applied to the tall activation x weight products
@@ -459,23 +453,46 @@ int mm(hipStream_t s, const float* A, int lda, bool tA, const float* B, int ldb,
         //  not the k-loop's MFMA density, set the pace.)
         // a_kpad: A is k-contiguous with rows padded to a multiple of 4 floats (zeros behind K): its last float4 stays inside the row
         const bool kok = K % 4 == 0 || (a_kpad && !tA && !tB && lda >= ((K + 3) & ~3));
-        if (vecA && vecB && kok && (!tA || M % 4 == 0) && (tB || N % 4 == 0) && !(dma_env && dma_env[0] == '0')) {
-            // measured: 64 x 64 tiles with a 4-stage ring; 3 stages tie, 6 / 8 stages and 128 x 128 tiles (3 stages) lose occupancy and are slower
-            launch_mm_dma<2, 2, 4>(s, p, tA, tB, batch);
-            DYGNN_LAUNCH_CHECK();
-            return DYGNN_OK;
+        if (pl.vecA && pl.vecB && kok && (!tA || M % 4 == 0) && (tB || N % 4 == 0) && !(dma_env && dma_env[0] == '0')) {
+            pl.kernel = kMmDma;
+            pl.f4_epilogue = (pl.vecC && pl.ksplit == 1 && beta == 0.f) ? 1 : 0;       // the condition k_mm_dma tests on the device
+        } else {
+            if (has_rows) { set_error("mm: a row table needs the LDS-DMA kernel (aligned k-contiguous operands, K %% 4 == 0)"); return DYGNN_E_UNSUPPORTED; }
+            pl.kernel = kMmBig;
         }
-        if (a_rows) { set_error("mm: a row table needs the LDS-DMA kernel (aligned k-contiguous operands, K %% 4 == 0)"); return DYGNN_E_UNSUPPORTED; }
-        const double w64 = (double)(ceil_div(N, 64) * 64) / N, w128 = (double)(ceil_div(N, 128) * 128) / N;
-        if (N <= 64 || w64 * 0.95 < w128)
-            hipLaunchKernelGGL((k_mm_big<2, 2>), dim3((unsigned)ceil_div(M, 64), (unsigned)ceil_div(N, 64), (unsigned)batch), dim3(256), 0, s, p, vecA, vecB);
-        else
-            hipLaunchKernelGGL((k_mm_big<4, 2>), dim3((unsigned)ceil_div(M, 64), (unsigned)ceil_div(N, 128), (unsigned)batch), dim3(256), 0, s, p, vecA, vecB);
-        DYGNN_LAUNCH_CHECK();
-        return DYGNN_OK;
+        pl.colsum_route = has_colsum ? 1 : 0;      // rides along inside the 64-row-tile kernels
+    } else {
+        if (has_rows) { set_error("mm: a row table needs at least 48 rows and columns"); return DYGNN_E_UNSUPPORTED; }
+        pl.kernel = kMmSmall;
+        pl.colsum_route = has_colsum ? 2 : 0;      // the stand-alone reduction
     }
-    if (a_rows) { set_error("mm: a row table needs at least 48 rows and columns"); return DYGNN_E_UNSUPPORTED; }
-    hipLaunchKernelGGL(k_mm, dim3((unsigned)ceil_div(M, 64), (unsigned)ceil_div(N, 64), (unsigned)batch), dim3(256), 0, s, p);
+    *out = pl;
+    return DYGNN_OK;
+}
+
+bool mm_gathers_rows(const float* A, int lda, const float* B, int ldb, int M, int N, int K) {
+    MmPlan pl;
+    return mm_plan(A, lda, false, B, ldb, true, nullptr, 0, M, N, K, 0.f, 1, 0, 0, 0, 0, 0, 0, false, false, false, false, &pl) == DYGNN_OK && pl.kernel == kMmDma;
+}
+
+int mm(hipStream_t s, const float* A, int lda, bool tA, const float* B, int ldb, bool tB, float* C, int ldc, int M, int N, int K, const float* bias, float alpha,
+       float beta, int batch, int H, int64_t sAb, int64_t sAh, int64_t sBb, int64_t sBh, int64_t sCb, int64_t sCh, bool relu, bool c_is_zero, float* colsum_out, const int32_t* m_dev, bool a_kpad,
+       const int32_t* a_rows) {
+    if (M <= 0 || N <= 0 || batch <= 0) return DYGNN_OK;
+    MmPlan pl;
+    if (int rc = mm_plan(A, lda, tA, B, ldb, tB, C, ldc, M, N, K, beta, batch, sAb, sAh, sBb, sBh, sCb, sCh, relu, colsum_out != nullptr, a_kpad, a_rows != nullptr, &pl)) return rc;
+    MM p{A, B, C, bias, M, N, K, lda, ldb, ldc, tA ? 1 : 0, tB ? 1 : 0, alpha, beta, H, sAb, sAh, sBb, sBh, sCb, sCh, relu ? 1 : 0, pl.ksplit, pl.kchunk, nullptr, m_dev,
+         pl.vecC, a_rows};
+    if (pl.colsum_route == 1) p.colsum = colsum_out;
+    else if (pl.colsum_route == 2) { if (int rc = colsum(s, A, lda, K, M, colsum_out)) return rc; }
+    // split: the parts add onto a zeroed C (beta = 0) or onto the old one (beta = 1); the kernels do not read p.beta when ksplit > 1
+    if (pl.ksplit > 1 && beta == 0.f && !c_is_zero) DYGNN_HIP(hipMemset2DAsync(C, (size_t)ldc * sizeof(float), 0, (size_t)N * sizeof(float), (size_t)M, s));
+    batch *= pl.ksplit;
+    const dim3 grid((unsigned)ceil_div(M, 64), (unsigned)ceil_div(N, 64), (unsigned)batch);
+    // measured: 64 x 64 tiles with a 4-stage ring; 3 stages tie, 6 / 8 stages and 128 x 128 tiles (3 stages) lose occupancy and are slower
+    if (pl.kernel == kMmDma) launch_mm_dma<2, 2, 4>(s, p, tA, tB, batch);
+    else if (pl.kernel == kMmBig) hipLaunchKernelGGL((k_mm_big<2, 2>), grid, dim3(256), 0, s, p, pl.vecA, pl.vecB);
+    else hipLaunchKernelGGL(k_mm, grid, dim3(256), 0, s, p);
     DYGNN_LAUNCH_CHECK();
     return DYGNN_OK;
 }

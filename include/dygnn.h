@@ -851,6 +851,73 @@ int dygnn_edgebank_evaluate(dygnn_edgebank* table_host, const int64_t* src, cons
                             int64_t n_batches, int64_t queries_per_batch, int32_t mode, int32_t window_mode, float* out,
                             dygnn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The general fp32 GEMM every backbone's products go through, and the grouped weight-gradient product of the fused trainers, as entry
+ * points of their own (what tests/test_gemm_gpu.py drives; the backbones call the same functions inside the library).
+ *
+ *   C = [relu] (alpha * op(A) . op(B) + bias[n] + beta * C)      per batch z = zb * H + zh, which adds zb * sXb + zh * sXh floats to A, B, C
+ *   op(A)[m][k] = tA ? A[k * lda + m] : A[m * lda + k],  op(B)[k][n] = tB ? B[n * ldb + k] : B[k * ldb + n]
+ *
+ * C is OVERWRITTEN (beta = 0: its old contents are not read, NaN included) or scaled and added to (beta != 0).  Exactly M x N elements per
+ * batch are written: nothing between N and ldc, nothing outside the batches.  bias (or NULL) is added once, before relu.
+ * Products with batch == 1, K >= 2048 and no relu are split over K and meet in float atomics: C is zeroed first (beta = 0; skipped when
+ * c_is_zero says the caller did it), or the parts add onto it (beta = 1).  A split product takes beta 0 or 1 only.
+ * colsum_out (or NULL; tA and batch == 1 only): colsum_out[m] += sum_k op(A)[m][k], ACCUMULATED onto what the buffer holds.
+ * m_dev (or NULL): device int32 count of live rows, 0 <= *m_dev <= M.  Rows below it are computed.  64-row tiles wholly at or beyond it are
+ *   not touched by the kernels, except that a split product with beta = 0 and !c_is_zero has zeroed all M rows.  Rows of the tile that holds
+ *   the count, at or beyond it, are unspecified (written from operand rows [count, M), which must be readable).
+ * a_kpad: !tA and !tB only; A's rows hold zeros from column K to the next multiple of 4 (lda at least that), which lets a K that is no multiple
+ *   of 4 take the LDS-DMA kernel.
+ * a_rows (or NULL; !tA only): device int32 table, row m of op(A) is A[a_rows[m]].  Only the LDS-DMA kernel gathers: a call that cannot take it
+ *   (see below) is refused.  With m_dev, entries at and beyond the count are not read.
+ * No alignment is required for a correct result; alignment picks the kernel (dygnn_mm_path):
+ *   0  M < 48 or N < 48: the 64 x 64 scalar-load kernel
+ *   2  the LDS-DMA kernel: A, B 16-byte aligned, lda, ldb and the A / B batch strides multiples of 4, K % 4 == 0 (or a_kpad), M % 4 == 0 with tA,
+ *      N % 4 == 0 with !tB, and the environment variable DYGNN_MM_DMA (read per call) not "0".  Its float4 epilogue needs C 16-byte aligned,
+ *      ldc and the C strides multiples of 4, beta = 0 and no split.
+ *   1  everything else.
+ * Refused with DYGNN_E_UNSUPPORTED before anything is launched or zeroed: a split product with beta outside {0, 1}; colsum_out with !tA or
+ * batch > 1; a_rows with tA; a_rows on a call that is not path 2.  NULL A, B or C, negative sizes, H < 1: DYGNN_E_INVALID.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct dygnn_mm_args {
+    const float*   A;
+    const float*   B;
+    float*         C;
+    const float*   bias;
+    float*         colsum_out;
+    const int32_t* m_dev;
+    const int32_t* a_rows;
+    int64_t sAb, sAh, sBb, sBh, sCb, sCh;
+    int32_t lda, ldb, ldc;
+    int32_t M, N, K;
+    int32_t batch, H;
+    float   alpha, beta;
+    int32_t tA, tB, relu, c_is_zero, a_kpad;
+} dygnn_mm_args;
+
+int dygnn_mm(const dygnn_mm_args* a, dygnn_stream_t stream);
+/* Which kernel dygnn_mm runs for these arguments: 0, 1 or 2 as above, or the (negative) code dygnn_mm would return.  Host only: nothing is
+ * launched and no pointer is followed (their alignment is what counts).  An empty product (M, N or batch 0) launches nothing and reports 0.
+ * dygnn_mm_plan also reports the number of K parts (1 = not split) and whether the float4 epilogue is taken (either may be NULL). */
+int32_t dygnn_mm_path(const dygnn_mm_args* a);
+int32_t dygnn_mm_plan(const dygnn_mm_args* a, int32_t* ksplit, int32_t* float4_epilogue);
+/* 1 when a !tA, tB product of these operands takes the LDS-DMA kernel, the only one that accepts a_rows (what the backbones ask before they
+ * choose between a row table and a staging copy); the same decision as dygnn_mm_path. */
+int32_t dygnn_mm_gathers_rows(const float* A, int32_t lda, const float* B, int32_t ldb, int32_t M, int32_t N, int32_t K);
+
+/* Weight-gradient-shaped products in one grouped split-K launch: C_p[m][n] += sum_k A_p[k][m] * B_p[k][n] for every problem p, all over the
+ * same K rows; colsum_p[m] += sum_k A_p[k][m] where colsum is not NULL.  C and colsum ACCUMULATE (float atomics): zero them first.
+ * Preconditions, else DYGNN_E_UNSUPPORTED with nothing launched: A and B 16-byte aligned; lda, ldb and N multiples of 4; M a multiple of 4 or
+ * lda >= M rounded up to one; at most 4 * DYGNN_MAX_LAYERS + 4 problems.  C, ldc and colsum need no alignment; only M x N elements are touched. */
+typedef struct dygnn_dw_pair {
+    const float* A; int32_t lda, M;
+    const float* B; int32_t ldb, N;
+    float* C; int32_t ldc;
+    float* colsum;
+} dygnn_dw_pair;
+
+int dygnn_dw_grouped(int32_t K, const dygnn_dw_pair* pairs, int32_t npairs, dygnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,8 @@ def test_struct_layouts_match_header():
     assert C.sizeof(_capi.EncoderLayerWeights) == 12 * 8
     assert C.sizeof(_capi.DygformerWeights) == (14 + 12 * _capi.DYGNN_MAX_LAYERS + 2) * 8
     assert C.sizeof(_capi.DygformerTaps) == (5 + _capi.DYGNN_MAX_LAYERS) * 8
+    assert C.sizeof(_capi.MmArgs) == 7 * 8 + 6 * 8 + 8 * 4 + 2 * 4 + 5 * 4 + 4           # 4 bytes of tail padding
+    assert C.sizeof(_capi.DwPair) == 8 + 2 * 4 + 8 + 2 * 4 + 8 + 4 + 4 + 8               # 4 bytes of padding behind ldc
 
 
 @pytest.mark.parametrize("name", ["bip_p2_l64", "gen_p1_l32"])
