@@ -523,7 +523,7 @@ static int wgrad(hipStream_t s, int K, const float* A, int lda, int M, const flo
         const train::DwPair pr{A, lda, M, B, ldb, N, C, ldc, nullptr};
         return train::dw_grouped(s, K, &pr, 1);
     }
-    return train::mm(s, A, lda, true, B, ldb, false, C, ldc, M, N, K, nullptr, 1.f, 1.f);
+    return train::mm(s, A, lda, true, B, ldb, false, C, ldc, M, N, K, train::MmOpt().beta(1.f));
 }
 
 // ---- workspace ------------------------------------------------------------------------------------------------------------------------------
@@ -654,7 +654,7 @@ extern "C" int dygnn_cawn_train_forward(const dygnn_cawn_config* cfg, const dygn
     DYGNN_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_cawnt_scale, dim3(blocks(d.Pd)), dim3(256), 0, s, w->pos_b1, d.Pd, 2.f, F32(p.b1x2));      // both rows carry the bias
     DYGNN_LAUNCH_CHECK();
-    if (int rc = train::mm(s, F32(p.hs), d.Pd, false, w->pos_w1, d.Pd, true, F32(p.pf), d.Pd, PR, d.Pd, d.Pd, F32(p.b1x2))) return rc;
+    if (int rc = train::mm(s, F32(p.hs), d.Pd, false, w->pos_w1, d.Pd, true, F32(p.pf), d.Pd, PR, d.Pd, d.Pd, train::MmOpt().bias(F32(p.b1x2)))) return rc;
     hipLaunchKernelGGL(k_cawnt_gather, dim3(blocks(p.NT * d.D)), dim3(256), 0, s, node_feat, edge_feat, I32(p.nid), I32(p.eidc), F32(p.dtv), valid, pidx,
                        F32(p.pf), w->time_w, w->time_b, L, d.Fn, d.Ft, d.Fe, d.Pd, F32(p.x));
     DYGNN_LAUNCH_CHECK();
@@ -664,7 +664,7 @@ extern "C" int dygnn_cawn_train_forward(const dygnn_cawn_config* cfg, const dygn
         const int H = e == 0 ? d.Hf : d.Hp, in = e == 0 ? d.D : d.Pd;
         const float* Xin = F32(p.x) + (e == 0 ? 0 : d.D - d.Pd);
         float *G = F32(p.enc[e].G), *GR = F32(p.enc[e].GR), *hb = F32(p.enc[e].h), *cb = F32(p.enc[e].c);
-        if (int rc = train::mm(s, Xin, d.D, false, m[0].w_ih, in, true, G, 4 * H, NT, 4 * H, in, m[0].b_ih)) return rc;
+        if (int rc = train::mm(s, Xin, d.D, false, m[0].w_ih, in, true, G, 4 * H, NT, 4 * H, in, train::MmOpt().bias(m[0].b_ih))) return rc;
         for (int lv = 0; lv <= d.W; ++lv) {
             const int64_t rows = p.I * L.n(lv);
             const float* HH = nullptr;
@@ -677,7 +677,7 @@ extern "C" int dygnn_cawn_train_forward(const dygnn_cawn_config* cfg, const dygn
                                d.k, H, hb, cb);
             DYGNN_LAUNCH_CHECK();
         }
-        if (int rc = train::mm(s, Xin, d.D, false, m[1].w_ih, in, true, GR, 4 * H, NT, 4 * H, in, m[1].b_ih)) return rc;
+        if (int rc = train::mm(s, Xin, d.D, false, m[1].w_ih, in, true, GR, 4 * H, NT, 4 * H, in, train::MmOpt().bias(m[1].b_ih))) return rc;
         hipLaunchKernelGGL(k_cawnt_cell, dim3(blocks(p.NT * H)), dim3(256), 0, s, GR, (const float*)nullptr, m[1].b_hh, valid, (int64_t)0, (int64_t)0, p.NT,
                            d.k, H, F32(p.enc[e].hr), (float*)nullptr);
         DYGNN_LAUNCH_CHECK();
@@ -688,7 +688,7 @@ extern "C" int dygnn_cawn_train_forward(const dygnn_cawn_config* cfg, const dygn
     // projection_layers[0], the transformer block over the M walks of a sequence (sites 0 .. 3, every row draws as itself)
     const train::Drop dr = train::make_drop(dropout_p, seed);
     const float scale = 1.0f / sqrtf((float)(A / d.heads));
-    if (int rc = train::mm(s, F32(p.eo), d.E, false, w->proj0_w, d.E, true, F32(p.x0), A, R, A, d.E, w->proj0_b)) return rc;
+    if (int rc = train::mm(s, F32(p.eo), d.E, false, w->proj0_w, d.E, true, F32(p.x0), A, R, A, d.E, train::MmOpt().bias(w->proj0_b))) return rc;
     const train::BlockBufs v = bufs(p, ws);
     auto attn = [&]() -> int {
         const size_t lds_fwd = (size_t)3 * d.M * kLdh * sizeof(float);
@@ -701,8 +701,8 @@ extern "C" int dygnn_cawn_train_forward(const dygnn_cawn_config* cfg, const dygn
     // mean over the walks, projection_layers[1]: sequence 2 p -> out_src[p], 2 p + 1 -> out_dst[p] (rows of stride 2 A)
     hipLaunchKernelGGL(k_cawnt_mean, dim3(blocks(p.I * A)), dim3(256), 0, s, F32(p.y), p.I, d.M, A, F32(p.ym));
     DYGNN_LAUNCH_CHECK();
-    if (int rc = train::mm(s, F32(p.ym), 2 * A, false, w->proj1_w, A, true, out_src, d.Fn, (int)batch, d.Fn, A, w->proj1_b)) return rc;
-    return train::mm(s, F32(p.ym) + A, 2 * A, false, w->proj1_w, A, true, out_dst, d.Fn, (int)batch, d.Fn, A, w->proj1_b);
+    if (int rc = train::mm(s, F32(p.ym), 2 * A, false, w->proj1_w, A, true, out_src, d.Fn, (int)batch, d.Fn, A, train::MmOpt().bias(w->proj1_b))) return rc;
+    return train::mm(s, F32(p.ym) + A, 2 * A, false, w->proj1_w, A, true, out_dst, d.Fn, (int)batch, d.Fn, A, train::MmOpt().bias(w->proj1_b));
 }
 
 extern "C" int dygnn_cawn_backward(const dygnn_cawn_config* cfg, const dygnn_cawn_weights* w, const dygnn_cawn_weights* grads, const float* grad_out_src,
@@ -737,8 +737,8 @@ extern "C" int dygnn_cawn_backward(const dygnn_cawn_config* cfg, const dygnn_caw
     float* dym = F32(p.dym);
     if (int rc = train::mm(s, grad_out_src, d.Fn, false, w->proj1_w, A, false, dym, 2 * A, B, A, d.Fn)) return rc;
     if (int rc = train::mm(s, grad_out_dst, d.Fn, false, w->proj1_w, A, false, dym + A, 2 * A, B, A, d.Fn)) return rc;
-    if (int rc = train::mm(s, grad_out_src, d.Fn, true, F32(p.ym), 2 * A, false, G(grads->proj1_w), A, d.Fn, A, B, nullptr, 1.f, 1.f)) return rc;
-    if (int rc = train::mm(s, grad_out_dst, d.Fn, true, F32(p.ym) + A, 2 * A, false, G(grads->proj1_w), A, d.Fn, A, B, nullptr, 1.f, 1.f)) return rc;
+    if (int rc = train::mm(s, grad_out_src, d.Fn, true, F32(p.ym), 2 * A, false, G(grads->proj1_w), A, d.Fn, A, B, train::MmOpt().beta(1.f))) return rc;
+    if (int rc = train::mm(s, grad_out_dst, d.Fn, true, F32(p.ym) + A, 2 * A, false, G(grads->proj1_w), A, d.Fn, A, B, train::MmOpt().beta(1.f))) return rc;
     if (int rc = colsum(s, grad_out_src, d.Fn, batch, d.Fn, part, G(grads->proj1_b))) return rc;
     if (int rc = colsum(s, grad_out_dst, d.Fn, batch, d.Fn, part, G(grads->proj1_b))) return rc;
     hipLaunchKernelGGL(k_cawnt_bcast, dim3(blocks(p.R * A)), dim3(256), 0, s, dym, p.R, d.M, A, gA);
@@ -796,8 +796,8 @@ extern "C" int dygnn_cawn_backward(const dygnn_cawn_config* cfg, const dygnn_caw
             if (int rc = colsum(s, dG, 4 * H, p.NT, 4 * H, part, G(g[dir].b_ih), G(g[dir].b_hh))) return rc;
             // dx: node and edge features are constants, only the time and the position columns are computed
             if (e == 0)
-                if (int rc = train::mm(s, dG, 4 * H, false, m[dir].w_ih + d.Fn, in, false, dxt, d.Ft, NT, d.Ft, 4 * H, nullptr, 1.f, dir == 0 ? 0.f : 1.f)) return rc;
-            if (int rc = train::mm(s, dG, 4 * H, false, m[dir].w_ih + pcol, in, false, dxp, d.Pd, NT, d.Pd, 4 * H, nullptr, 1.f, dxp_set ? 1.f : 0.f)) return rc;
+                if (int rc = train::mm(s, dG, 4 * H, false, m[dir].w_ih + d.Fn, in, false, dxt, d.Ft, NT, d.Ft, 4 * H, train::MmOpt().beta(dir == 0 ? 0.f : 1.f))) return rc;
+            if (int rc = train::mm(s, dG, 4 * H, false, m[dir].w_ih + pcol, in, false, dxp, d.Pd, NT, d.Pd, 4 * H, train::MmOpt().beta(dxp_set ? 1.f : 0.f))) return rc;
             dxp_set = true;
         }
     }
@@ -819,5 +819,5 @@ extern "C" int dygnn_cawn_backward(const dygnn_cawn_config* cfg, const dygnn_caw
     hipLaunchKernelGGL(k_cawnt_mlp_bwd, dim3(blocks((int64_t)PR * d.Pd)), dim3(256), 0, s, F32(p.ct), w->pos_w0, w->pos_b0, dhs, (int64_t)PR, d.Pd, W1, dp);
     DYGNN_LAUNCH_CHECK();
     if (int rc = colsum(s, dp, d.Pd, 2 * (int64_t)PR, d.Pd, part, G(grads->pos_b0))) return rc;
-    return train::mm(s, dp, d.Pd, true, F32(p.ct), 3, false, G(grads->pos_w0), W1, d.Pd, W1, 2 * PR, nullptr, 1.f, 1.f);
+    return train::mm(s, dp, d.Pd, true, F32(p.ct), 3, false, G(grads->pos_w0), W1, d.Pd, W1, 2 * PR, train::MmOpt().beta(1.f));
 }

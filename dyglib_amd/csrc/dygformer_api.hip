@@ -1,5 +1,4 @@
-// C-ABI entry points for the DyGFormer forward path + the fused link-predictor head + the general GEMM.
-#include <vector>
+// C-ABI entry points for the DyGFormer forward path + the fused link-predictor head (the general GEMM's are in gemm.hip).
 #include "dygformer_layout.h"
 #include "gemm.h"
 
@@ -536,50 +535,4 @@ extern "C" int dygnn_merge_layer_backward(const float* a, const float* b, int64_
     const train::DwPair pairs[2] = {{workspace, hidden, hidden, a, dim, dim, grad_fc1_w, 2 * dim, grad_fc1_b},
                                     {workspace, hidden, hidden, b, dim, dim, grad_fc1_w + dim, 2 * dim, nullptr}};
     return train::dw_grouped(as_stream(stream), (int)n, pairs, 2);
-}
-
-// ---- the general GEMM and the grouped weight-gradient product as entry points of their own (tests/test_gemm_gpu.py) ----------------------
-static_assert(sizeof(dygnn_mm_args) == 168 && sizeof(dygnn_dw_pair) == 56, "the ctypes structures of _capi.py assume these layouts");
-static int mm_args_check(const dygnn_mm_args* a) {
-    DYGNN_REQUIRE(a != nullptr, "mm: null arguments");
-    DYGNN_REQUIRE(a->M >= 0 && a->N >= 0 && a->K >= 0 && a->batch >= 0 && a->H >= 1, "mm: negative size");
-    DYGNN_REQUIRE(a->A && a->B && a->C, "mm: null pointer");
-    DYGNN_REQUIRE(a->lda >= (a->tA ? a->M : a->K) && a->ldb >= (a->tB ? a->K : a->N) && a->ldc >= a->N, "mm: a leading dimension is shorter than its row");
-    return DYGNN_OK;
-}
-
-extern "C" int32_t dygnn_mm_plan(const dygnn_mm_args* a, int32_t* ksplit, int32_t* float4_epilogue) {
-    if (int rc = mm_args_check(a)) return rc;
-    train::MmPlan pl;
-    if (int rc = train::mm_plan(a->A, a->lda, a->tA != 0, a->B, a->ldb, a->tB != 0, a->C, a->ldc, a->M, a->N, a->K, a->beta, a->batch, a->sAb, a->sAh, a->sBb, a->sBh,
-                                a->sCb, a->sCh, a->relu != 0, a->colsum_out != nullptr, a->a_kpad != 0, a->a_rows != nullptr, &pl))
-        return rc;
-    if (ksplit) *ksplit = pl.ksplit;
-    if (float4_epilogue) *float4_epilogue = pl.f4_epilogue;
-    return pl.kernel;
-}
-
-extern "C" int32_t dygnn_mm_path(const dygnn_mm_args* a) { return dygnn_mm_plan(a, nullptr, nullptr); }
-
-extern "C" int32_t dygnn_mm_gathers_rows(const float* A, int32_t lda, const float* B, int32_t ldb, int32_t M, int32_t N, int32_t K) {
-    return train::mm_gathers_rows(A, lda, B, ldb, M, N, K) ? 1 : 0;
-}
-
-extern "C" int dygnn_mm(const dygnn_mm_args* a, dygnn_stream_t stream) {
-    if (int rc = mm_args_check(a)) return rc;
-    return train::mm(as_stream(stream), a->A, a->lda, a->tA != 0, a->B, a->ldb, a->tB != 0, a->C, a->ldc, a->M, a->N, a->K, a->bias, a->alpha, a->beta, a->batch, a->H,
-                     a->sAb, a->sAh, a->sBb, a->sBh, a->sCb, a->sCh, a->relu != 0, a->c_is_zero != 0, a->colsum_out, a->m_dev, a->a_kpad != 0, a->a_rows);
-}
-
-extern "C" int dygnn_dw_grouped(int32_t K, const dygnn_dw_pair* pairs, int32_t npairs, dygnn_stream_t stream) {
-    DYGNN_REQUIRE(K >= 0 && npairs >= 0 && (npairs == 0 || pairs != nullptr), "dw_grouped: bad sizes");
-    for (int32_t i = 0; i < npairs; ++i) {
-        const dygnn_dw_pair& q = pairs[i];
-        DYGNN_REQUIRE(q.A && q.B && q.C, "dw_grouped: null pointer");
-        DYGNN_REQUIRE(q.M >= 0 && q.N >= 0 && q.lda >= q.M && q.ldb >= q.N && q.ldc >= q.N, "dw_grouped: negative size, or a leading dimension shorter than its row");
-    }
-    std::vector<train::DwPair> list;
-    list.reserve((size_t)npairs);
-    for (int32_t i = 0; i < npairs; ++i) list.push_back(train::DwPair{pairs[i].A, pairs[i].lda, pairs[i].M, pairs[i].B, pairs[i].ldb, pairs[i].N, pairs[i].C, pairs[i].ldc, pairs[i].colsum});
-    return train::dw_grouped(as_stream(stream), K, list.data(), npairs);
 }

@@ -16,7 +16,7 @@ namespace v3 {
 //     dhact^T = W2[:, step]^T . dF2^T,   dhpre = dhact o mask2 o gelu'(hpre),   dxn1^T += W1[step, :]^T . dhpre^T
 // with dF2 = dX o mask3; then LayerNorm-1 backward against the stored statistics, dX <- dX + LN1'(dxn1) in place, and the LN weight /
 // bias gradients (row sums by DPP, the eight waves meet in LDS, one atomic per channel and workgroup).  dF2 and dhpre are written as dense
-// rows for the grouped weight-gradient launch (k_dw_grouped, dygformer_train.hip), which also sums the bias gradients.
+// rows for the grouped weight-gradient launch (k_dw_grouped, gemm.hip), which also sums the bias gradients.
 struct FfnBwdArgs {
     const float* stream; int nstages;
     int64_t M;

@@ -30,18 +30,18 @@ static int encoder_block_forward(hipStream_t s, int d, int64_t R, const float* X
                                  uint32_t site, const RowMap& map, const BlockBufs& v, Attn attn) {
     const unsigned row_blocks = (unsigned)ceil_div(R, 4);
     const int Ri = (int)R;
-    if (int rc = mm(s, X, d, false, m.in_proj_w, d, true, v.qkv, 3 * d, Ri, 3 * d, d, m.in_proj_b)) return rc;
+    if (int rc = mm(s, X, d, false, m.in_proj_w, d, true, v.qkv, 3 * d, Ri, 3 * d, d, MmOpt().bias(m.in_proj_b))) return rc;
     if (int rc = attn()) return rc;
-    if (int rc = mm(s, v.O, d, false, m.out_proj_w, d, true, v.tmp, d, Ri, d, d, m.out_proj_b)) return rc;
+    if (int rc = mm(s, v.O, d, false, m.out_proj_w, d, true, v.tmp, d, Ri, d, d, MmOpt().bias(m.out_proj_b))) return rc;
     hipLaunchKernelGGL(k_res_ln<NV>, dim3(row_blocks), dim3(256), 0, s, v.tmp, X, m.norm0_w, m.norm0_b, R, d, map, dr, site + 1, v.pre0, v.mean0, v.rstd0,
                        v.y0);
     DYGNN_LAUNCH_CHECK();
-    if (int rc = mm(s, v.y0, d, false, m.fc0_w, d, true, v.hid, 4 * d, Ri, 4 * d, d, m.fc0_b, 1.f, 0.f, 1, 1, 0, 0, 0, 0, 0, 0, true)) return rc;
+    if (int rc = mm(s, v.y0, d, false, m.fc0_w, d, true, v.hid, 4 * d, Ri, 4 * d, d, MmOpt().bias(m.fc0_b).relu())) return rc;
     if (dropout_p > 0.f) {
         hipLaunchKernelGGL(k_row_drop, dim3((unsigned)ceil_div(R * 4 * d, 256)), dim3(256), 0, s, v.hid, R * 4 * d, 4 * d, map, dr, site + 2);
         DYGNN_LAUNCH_CHECK();
     }
-    if (int rc = mm(s, v.hid, 4 * d, false, m.fc1_w, 4 * d, true, v.tmp, d, Ri, d, 4 * d, m.fc1_b)) return rc;
+    if (int rc = mm(s, v.hid, 4 * d, false, m.fc1_w, 4 * d, true, v.tmp, d, Ri, d, 4 * d, MmOpt().bias(m.fc1_b))) return rc;
     hipLaunchKernelGGL(k_res_ln<NV>, dim3(row_blocks), dim3(256), 0, s, v.tmp, v.y0, m.norm1_w, m.norm1_b, R, d, map, dr, site + 3, v.pre1, v.mean1, v.rstd1,
                        v.out);
     DYGNN_LAUNCH_CHECK();
@@ -68,7 +68,7 @@ static int encoder_block_backward(hipStream_t s, int d, int64_t R, const float* 
     hipLaunchKernelGGL(k_hid_bwd, dim3((unsigned)ceil_div(R * 4 * d, 256)), dim3(256), 0, s, v.dhid, v.hid, R * 4 * d, dr.scale);
     DYGNN_LAUNCH_CHECK();
     if (int rc = cs(v.dhid, 4 * d, g.fc0_b)) return rc;
-    if (int rc = mm(s, v.dhid, 4 * d, false, m.fc0_w, d, false, v.gB, d, Ri, d, 4 * d, nullptr, 1.f, 1.f)) return rc;
+    if (int rc = mm(s, v.dhid, 4 * d, false, m.fc0_w, d, false, v.gB, d, Ri, d, 4 * d, MmOpt().beta(1.f))) return rc;
     // LayerNorm 0, attention block dropout: gB = d y0 -> gA = d X (residual part), gE = d (out_proj output)
     hipLaunchKernelGGL(k_res_ln_bwd<NV>, dim3(row_blocks), dim3(256), 0, s, v.gB, v.pre0, v.mean0, v.rstd0, m.norm0_w, R, d, map, dr, site + 1, v.gA, v.gE,
                        v.gD);
@@ -80,7 +80,7 @@ static int encoder_block_backward(hipStream_t s, int d, int64_t R, const float* 
     if (int rc = mm(s, v.gE, d, false, m.out_proj_w, d, false, v.gF, d, Ri, d, d)) return rc;
     if (int rc = attn_bwd()) return rc;
     if (int rc = cs(v.dqkv, 3 * d, g.in_proj_b)) return rc;
-    if (int rc = mm(s, v.dqkv, 3 * d, false, m.in_proj_w, d, false, v.gA, d, Ri, d, 3 * d, nullptr, 1.f, 1.f)) return rc;
+    if (int rc = mm(s, v.dqkv, 3 * d, false, m.in_proj_w, d, false, v.gA, d, Ri, d, 3 * d, MmOpt().beta(1.f))) return rc;
     // the block's weight gradients, grouped split-K over its R rows
     const DwPair pairs[4] = {{v.dqkv, 3 * d, 3 * d, X, d, d, W(g.in_proj_w), d, nullptr},
                              {v.gE, d, d, v.O, d, d, W(g.out_proj_w), d, nullptr},

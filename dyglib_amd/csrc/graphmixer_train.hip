@@ -462,16 +462,16 @@ extern "C" int dygnn_graphmixer_train_forward(const dygnn_graphmixer_config* cfg
         hipLaunchKernelGGL(k_gmt_ln_fwd, dim3((unsigned)ceil_div(p.R, 4)), dim3(256), 0, s, F32(v.x1), m.channel_norm_w, m.channel_norm_b, p.R, C, F32(v.y),
                            F32(v.mean), F32(v.rstd));
         DYGNN_LAUNCH_CHECK();
-        if (int rc = train::mm(s, F32(v.y), C, false, m.channel_fc0_w, C, true, F32(v.hpre), H, R, H, C, m.channel_fc0_b)) return rc;
+        if (int rc = train::mm(s, F32(v.y), C, false, m.channel_fc0_w, C, true, F32(v.hpre), H, R, H, C, train::MmOpt().bias(m.channel_fc0_b))) return rc;
         hipLaunchKernelGGL(k_gmt_gelu_drop, dim3(blocks(p.R * H)), dim3(256), 0, s, F32(v.hpre), F32(v.hact), p.R * H, dr, site + 2);
         DYGNN_LAUNCH_CHECK();
-        if (int rc = train::mm(s, F32(v.hact), H, false, m.channel_fc1_w, H, true, F32(p.tmp), C, R, C, H, m.channel_fc1_b)) return rc;
+        if (int rc = train::mm(s, F32(v.hact), H, false, m.channel_fc1_w, H, true, F32(p.tmp), C, R, C, H, train::MmOpt().bias(m.channel_fc1_b))) return rc;
         hipLaunchKernelGGL(k_gmt_res, dim3(blocks(p.R * C)), dim3(256), 0, s, F32(v.x1), F32(p.tmp), F32(p.x[l + 1]), p.R * C, dr, site + 3);
         DYGNN_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(k_gmt_cat, dim3(blocks(n * (C + Fn))), dim3(256), 0, s, F32(p.x[p.L]), F32(p.term), node_feat, nodes, n, node_rows, K, C, Fn, F32(p.z));
     DYGNN_LAUNCH_CHECK();
-    return train::mm(s, F32(p.z), C + Fn, false, w->output_w, C + Fn, true, out, Fn, (int)n, Fn, C + Fn, w->output_b);
+    return train::mm(s, F32(p.z), C + Fn, false, w->output_w, C + Fn, true, out, Fn, (int)n, Fn, C + Fn, train::MmOpt().bias(w->output_b));
 }
 
 extern "C" int dygnn_graphmixer_backward(const dygnn_graphmixer_config* cfg, const dygnn_graphmixer_weights* w, const dygnn_graphmixer_weights* grads,

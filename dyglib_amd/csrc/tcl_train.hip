@@ -425,8 +425,8 @@ extern "C" int dygnn_tcl_train_forward(const dygnn_tcl_config* cfg, const dygnn_
         X = v.out;
     }
     // output_layer on position 0 of every sequence: rows of stride S d
-    if (int rc = train::mm(s, X, S * d, false, w->output_w, d, true, out_src, d, (int)B, d, d, w->output_b)) return rc;
-    return train::mm(s, X + (size_t)B * S * d, S * d, false, w->output_w, d, true, out_dst, d, (int)B, d, d, w->output_b);
+    if (int rc = train::mm(s, X, S * d, false, w->output_w, d, true, out_src, d, (int)B, d, d, train::MmOpt().bias(w->output_b))) return rc;
+    return train::mm(s, X + (size_t)B * S * d, S * d, false, w->output_w, d, true, out_dst, d, (int)B, d, d, train::MmOpt().bias(w->output_b));
 }
 
 extern "C" int dygnn_tcl_backward(const dygnn_tcl_config* cfg, const dygnn_tcl_weights* w, const dygnn_tcl_weights* grads, const float* grad_out_src,

@@ -610,7 +610,7 @@ int expand_levels(hipStream_t s, const dygnn_csr* csr, const TgatRoots& r, int L
 template <bool RELU>
 static int gemm_nt(const float* A, const float* W, const float* bias, float* C, int64_t M, int N, int K, int ldc, hipStream_t s, const int32_t* m_dev = nullptr) {
     if (M == 0) return DYGNN_OK;
-    if (M >= 48 || m_dev) return train::mm(s, A, K, false, W, K, true, C, ldc, (int)M, N, K, bias, 1.f, 0.f, 1, 1, 0, 0, 0, 0, 0, 0, RELU, false, nullptr, m_dev);      // the LDS-tiled general GEMM
+    if (M >= 48 || m_dev) return train::mm(s, A, K, false, W, K, true, C, ldc, (int)M, N, K, train::MmOpt().bias(bias).relu(RELU).live_rows(m_dev));      // the LDS-tiled general GEMM
     hipLaunchKernelGGL((k_gemm_nt<RELU>), dim3((unsigned)ceil_div(M, 256), (unsigned)ceil_div(N, 64)), dim3(256), 0, s, A, W, bias, C, M, N, K, ldc);
     DYGNN_LAUNCH_CHECK();
     return DYGNN_OK;
@@ -757,8 +757,8 @@ static int tgat_layers(const TgatStages& c, const dygnn_tgat_weights* w, const f
         DYGNN_LAUNCH_CHECK();
         const float* qa = h_lower ? h_lower : node_feat;
         if (n >= 48 && train::mm_gathers_rows(qa, p.Fn, Lw.query_w, p.Dq, (int)n, p.Dq, p.Fn)) {
-            if (int rc = train::mm(s, qa, p.Fn, false, Lw.query_w, p.Dq, true, F32(p.q), p.Dq, (int)n, p.Dq, p.Fn, cq, 1.f, 0.f, 1, 1, 0, 0, 0, 0,
-                                   0, 0, false, false, nullptr, nl, false, h_lower ? lmap : I32(p.ids[l - 1]))) return rc;
+            if (int rc = train::mm(s, qa, p.Fn, false, Lw.query_w, p.Dq, true, F32(p.q), p.Dq, (int)n, p.Dq, p.Fn,
+                                   train::MmOpt().bias(cq).live_rows(nl).rows(h_lower ? lmap : I32(p.ids[l - 1])))) return rc;
         } else {      // a handful of rows, or a product the row-gathering kernel cannot take (Dq < 48, DYGNN_MM_DMA=0, unaligned feature table): the
                       // feature rows are staged ([n][Fn], Ft = 0: no time columns), then the small-M kernel
             hipLaunchKernelGGL(k_tgat_qrows, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, s, h_lower, node_feat, I32(p.ids[l - 1]), w->time_w, w->time_b, n, p.Fn, 0,
@@ -769,8 +769,8 @@ static int tgat_layers(const TgatStages& c, const dygnn_tgat_weights* w, const f
             DYGNN_LAUNCH_CHECK();
         }
         // qk[i][h] = W_k,h^T q_ih : per head [n][hd] x [hd][Dkv] (rows h*hd .. of key_w), one batched launch over the heads
-        if (int rc = train::mm(s, F32(p.q), p.Dq, false, Lw.key_w, p.Dkv, false, F32(p.qk), p.H * p.Dkv, (int)n, p.Dkv, p.hd, nullptr, 1.f, 0.f, p.H, p.H, 0, p.hd,
-                               0, (int64_t)p.hd * p.Dkv, 0, p.Dkv, false, false, nullptr, nl)) return rc;
+        if (int rc = train::mm(s, F32(p.q), p.Dq, false, Lw.key_w, p.Dkv, false, F32(p.qk), p.H * p.Dkv, (int)n, p.Dkv, p.hd,
+                               train::MmOpt().batched(p.H, p.H).strideA(0, p.hd).strideB(0, (int64_t)p.hd * p.Dkv).strideC(0, p.Dkv).live_rows(nl))) return rc;
         }
         const bool attn_in_post = chain && chain::post_fuses_attention(n, p.Fn, p.Ft, p.Dkv, p.H, p.k);      // the chain's last kernel runs it on its own rows
         if (attn_in_post) {
@@ -804,8 +804,8 @@ static int tgat_layers(const TgatStages& c, const dygnn_tgat_weights* w, const f
             continue;
         }
         // att[i][h*hd ..] = W_v,h z_ih : per head [n][Dkv] x [Dkv][hd]
-        if (int rc = train::mm(s, F32(p.z), p.H * p.Dkv, false, Lw.value_w, p.Dkv, true, F32(p.att), p.Dq, (int)n, p.hd, p.Dkv, nullptr, 1.f, 0.f, p.H, p.H, 0, p.Dkv,
-                               0, (int64_t)p.hd * p.Dkv, 0, p.hd, false, false, nullptr, nl)) return rc;
+        if (int rc = train::mm(s, F32(p.z), p.H * p.Dkv, false, Lw.value_w, p.Dkv, true, F32(p.att), p.Dq, (int)n, p.hd, p.Dkv,
+                               train::MmOpt().batched(p.H, p.H).strideA(0, p.Dkv).strideB(0, (int64_t)p.hd * p.Dkv).strideC(0, p.hd).live_rows(nl))) return rc;
         if (int rc = gemm_nt<false>(F32(p.att), Lw.res_w, Lw.res_b, F32(p.fc), n, p.Dq, p.Dq, p.Dq, s, nl)) return rc;
         hipLaunchKernelGGL(k_tgat_post, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, s, F32(p.fc), h_lower, lmap, ct, Lw.ln_w, Lw.ln_b, node_feat, I32(p.ids[l - 1]),
                            n, p.Dq, p.Fn, F32(p.merge_in), nl);

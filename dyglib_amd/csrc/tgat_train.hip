@@ -431,21 +431,21 @@ int train_forward(hipStream_t s, const dygnn_tgat_config& cfg, const dygnn_tgat_
         DYGNN_LAUNCH_CHECK();
         if (int rc = train::mm(s, F32(v.qin), p.Dq, false, Lw.query_w, p.Dq, true, F32(v.q), p.Dq, (int)n, p.Dq, p.Dq)) return rc;
         // qk[i][h] = W_k,h^T q_ih, per head [n][hd] x [hd][Dkv]
-        if (int rc = train::mm(s, F32(v.q), p.Dq, false, Lw.key_w, p.Dkv, false, F32(v.qk), p.H * p.Dkv, (int)n, p.Dkv, p.hd, nullptr, 1.f, 0.f, p.H, p.H, 0,
-                               p.hd, 0, (int64_t)p.hd * p.Dkv, 0, p.Dkv)) return rc;
+        if (int rc = train::mm(s, F32(v.q), p.Dq, false, Lw.key_w, p.Dkv, false, F32(v.qk), p.H * p.Dkv, (int)n, p.Dkv, p.hd,
+                               train::MmOpt().batched(p.H, p.H).strideA(0, p.hd).strideB(0, (int64_t)p.hd * p.Dkv).strideC(0, p.Dkv))) return rc;
         const XRows X{h_lower, node_feat, edge_feat, ids_lower, I32(p.eid[l]), F32(p.dt[l]), w->time_w, w->time_b, n, p.k, p.Fn, p.Fe, p.Ft, p.Dkv};
         hipLaunchKernelGGL(k_tt_attn_fwd, dim3((unsigned)n), dim3(64), attn_lds, s, X, F32(v.qk), p.H, scale, dr, (uint32_t)(2 * (l - 1)), F32(v.P), F32(v.z));
         DYGNN_LAUNCH_CHECK();
         // att[i][h*hd ..] = W_v,h z_ih
-        if (int rc = train::mm(s, F32(v.z), p.H * p.Dkv, false, Lw.value_w, p.Dkv, true, F32(v.att), p.Dq, (int)n, p.hd, p.Dkv, nullptr, 1.f, 0.f, p.H, p.H, 0,
-                               p.Dkv, 0, (int64_t)p.hd * p.Dkv, 0, p.hd)) return rc;
-        if (int rc = train::mm(s, F32(v.att), p.Dq, false, Lw.res_w, p.Dq, true, F32(p.fc), p.Dq, (int)n, p.Dq, p.Dq, Lw.res_b)) return rc;
+        if (int rc = train::mm(s, F32(v.z), p.H * p.Dkv, false, Lw.value_w, p.Dkv, true, F32(v.att), p.Dq, (int)n, p.hd, p.Dkv,
+                               train::MmOpt().batched(p.H, p.H).strideA(0, p.Dkv).strideB(0, (int64_t)p.hd * p.Dkv).strideC(0, p.hd))) return rc;
+        if (int rc = train::mm(s, F32(v.att), p.Dq, false, Lw.res_w, p.Dq, true, F32(p.fc), p.Dq, (int)n, p.Dq, p.Dq, train::MmOpt().bias(Lw.res_b))) return rc;
         hipLaunchKernelGGL(k_tt_post, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, s, F32(p.fc), F32(v.qin), Lw.ln_w, Lw.ln_b, node_feat, ids_lower, n, p.Dq, p.Fn,
                            dr, (uint32_t)(2 * (l - 1) + 1), F32(v.pre), F32(v.mean), F32(v.rstd), F32(v.merge));
         DYGNN_LAUNCH_CHECK();
-        if (int rc = train::mm(s, F32(v.merge), p.Dq + p.Fn, false, Lw.fc1_w, p.Dq + p.Fn, true, F32(v.hid), p.Fn, (int)n, p.Fn, p.Dq + p.Fn, Lw.fc1_b, 1.f, 0.f,
-                               1, 1, 0, 0, 0, 0, 0, 0, true)) return rc;
-        if (int rc = train::mm(s, F32(v.hid), p.Fn, false, Lw.fc2_w, p.Fn, true, F32(v.h), p.Fn, (int)n, p.Fn, p.Fn, Lw.fc2_b)) return rc;
+        if (int rc = train::mm(s, F32(v.merge), p.Dq + p.Fn, false, Lw.fc1_w, p.Dq + p.Fn, true, F32(v.hid), p.Fn, (int)n, p.Fn, p.Dq + p.Fn,
+                               train::MmOpt().bias(Lw.fc1_b).relu())) return rc;
+        if (int rc = train::mm(s, F32(v.hid), p.Fn, false, Lw.fc2_w, p.Fn, true, F32(v.h), p.Fn, (int)n, p.Fn, p.Fn, train::MmOpt().bias(Lw.fc2_b))) return rc;
     }
     const size_t half = (size_t)batch * p.Fn * sizeof(float);
     DYGNN_HIP(hipMemcpyAsync(out_src, F32(p.lv[p.L].h), half, hipMemcpyDeviceToDevice, s));
@@ -500,17 +500,17 @@ int train_backward(hipStream_t s, const dygnn_tgat_config& cfg, const dygnn_tgat
         if (int rc = colsum(s, F32(p.dy), Dq, n, Dq, F32(p.part), W(G.ln_b))) return rc;
         // 3. residual_fc, then W_v per head: dz_ih = W_v,h^T datt_ih
         if (int rc = train::mm(s, F32(p.dfc), Dq, false, Lw.res_w, Dq, false, F32(p.datt), Dq, ni, Dq, Dq)) return rc;
-        if (int rc = train::mm(s, F32(p.datt), Dq, false, Lw.value_w, Dkv, false, F32(p.dz), H * Dkv, ni, Dkv, hd, nullptr, 1.f, 0.f, H, H, 0, hd, 0,
-                               (int64_t)hd * Dkv, 0, Dkv)) return rc;
+        if (int rc = train::mm(s, F32(p.datt), Dq, false, Lw.value_w, Dkv, false, F32(p.dz), H * Dkv, ni, Dkv, hd,
+                               train::MmOpt().batched(H, H).strideA(0, hd).strideB(0, (int64_t)hd * Dkv).strideC(0, Dkv))) return rc;
         // 4. attention
         const XRows X{h_lower, nullptr, nullptr, ids_lower, I32(p.eid[l]), F32(p.dt[l]), w->time_w, w->time_b, n, p.k, Fn, p.Fe, Ft, Dkv};
         hipLaunchKernelGGL(k_tt_attn_bwd, dim3((unsigned)n), dim3(64), attn_lds, s, X, reinterpret_cast<const float* const*>(ws + p.tabs), F32(v.qk), F32(v.P),
                            F32(p.dz), H, scale, dr, site_p, F32(p.dqk), dlow, F32(p.tdw), F32(p.tdb), fg);
         DYGNN_LAUNCH_CHECK();
         // 5. W_k, W_q: dq_ih = W_k,h d(W_k,h^T q_ih); dqin += dq W_q
-        if (int rc = train::mm(s, F32(p.dqk), H * Dkv, false, Lw.key_w, Dkv, true, F32(p.dq), Dq, ni, hd, Dkv, nullptr, 1.f, 0.f, H, H, 0, Dkv, 0,
-                               (int64_t)hd * Dkv, 0, hd)) return rc;
-        if (int rc = train::mm(s, F32(p.dq), Dq, false, Lw.query_w, Dq, false, F32(p.dqin), Dq, ni, Dq, Dq, nullptr, 1.f, 1.f)) return rc;
+        if (int rc = train::mm(s, F32(p.dqk), H * Dkv, false, Lw.key_w, Dkv, true, F32(p.dq), Dq, ni, hd, Dkv,
+                               train::MmOpt().batched(H, H).strideA(0, Dkv).strideB(0, (int64_t)hd * Dkv).strideC(0, hd))) return rc;
+        if (int rc = train::mm(s, F32(p.dq), Dq, false, Lw.query_w, Dq, false, F32(p.dqin), Dq, ni, Dq, Dq, train::MmOpt().beta(1.f))) return rc;
         hipLaunchKernelGGL(k_tt_qin_bwd, dim3((unsigned)ceil_div(n * Dq, 256)), dim3(256), 0, s, F32(p.dqin), n, Fn, Ft, w->time_w, w->time_b, dlow, F32(p.tdb), ids_lower, fg);
         DYGNN_LAUNCH_CHECK();
         // 7. time encoder (shared by all layers and the query's cos(b)): per-row partials -> fixed-order column sums

@@ -208,10 +208,10 @@ extern "C" int dygnn_tgn_backward(const dygnn_tgat_config* cfg, const dygnn_tgat
     if (int rc = tgt::train_backward(s, *cfg, w, grads, grad_out_src, grad_out_dst, batch, dropout_p, seed, ws + p.tgat, &fg)) return rc;
     // 2. GRU cell: gate pre-activations of the listed rows again (the saved message / memory rows, the current weights), their derivatives,
     //    then the four parameter gradients.  d(updated memory) = d feat0 (feat0 = memory + raw).
-    if (int rc = train::mm(s, F32(p.msgs), Dm, false, gru->weight_ih, Dm, true, F32(p.gi), 3 * F, rows, 3 * F, Dm, gru->bias_ih, 1.f, 0.f, 1, 1, 0, 0, 0, 0, 0, 0,
-                           false, false, nullptr, meta + tgn::kCount)) return rc;
-    if (int rc = train::mm(s, F32(p.hold), F, false, gru->weight_hh, F, true, F32(p.gh), 3 * F, rows, 3 * F, F, gru->bias_hh, 1.f, 0.f, 1, 1, 0, 0, 0, 0, 0, 0,
-                           false, false, nullptr, meta + tgn::kCount)) return rc;
+    if (int rc = train::mm(s, F32(p.msgs), Dm, false, gru->weight_ih, Dm, true, F32(p.gi), 3 * F, rows, 3 * F, Dm,
+                           train::MmOpt().bias(gru->bias_ih).live_rows(meta + tgn::kCount))) return rc;
+    if (int rc = train::mm(s, F32(p.hold), F, false, gru->weight_hh, F, true, F32(p.gh), 3 * F, rows, 3 * F, F,
+                           train::MmOpt().bias(gru->bias_hh).live_rows(meta + tgn::kCount))) return rc;
     hipLaunchKernelGGL(tgn::k_tgn_gru_bwd, dim3((unsigned)ceil_div(p.rows * F, 256)), dim3(256), 0, s, meta, F32(p.dfeat), F32(p.hold), F, p.rows, F32(p.gi), F32(p.gh));
     DYGNN_LAUNCH_CHECK();
     const train::DwPair pairs[2] = {{F32(p.gi), 3 * F, 3 * F, F32(p.msgs), Dm, Dm, gg->weight_ih, Dm, gg->bias_ih},

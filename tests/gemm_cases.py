@@ -168,6 +168,21 @@ def _mm_cases():
     out.append(heads("heads-dma-all-strides", DMA, 50, 8, 52, True))
     out.append(heads("heads-big-all-strides", BIG, 65, 6, 50, True))
     out.append(heads("heads-small-n20", SMALL, 20, 8, 48, True))
+    # ---- batched with all six strides in play, one case per kernel: batch = 4, H = 2, every stride non-zero and different from the other five
+    # (a call that swaps two of them reads NaN or misses C); a guard block between the four products of each operand.  The smallest shapes that
+    # select each kernel; k_mm_dma keeps its strides multiples of 4, the other two get odd ones
+    def strided(name, kernel, M, N, K, tA, tB, step, **kw):
+        c = mk(name, kernel, M, N, K, tA, tB, batch=4, H=2, bias=True, group="batched", **kw)
+        st = {}
+        for i, (X, rows, ld) in enumerate((("A", K if tA else M, c["lda"]), ("B", N if tB else K, c["ldb"]), ("C", M, c["ldc"]))):
+            st[f"s{X}h"] = rows * ld + r4(4 * ld + 16) + step * i
+            st[f"s{X}b"] = 2 * st[f"s{X}h"] + r4(4 * ld + 16) + step * (i + 1)
+        assert all(st.values()) and len(set(st.values())) == 6
+        c["strides"] = st
+        return c
+    out.append(strided("strides-small-TN", SMALL, 5, 7, 6, True, False, 1, alpha=-2.0))
+    out.append(strided("strides-dma-NN", DMA, 64, 48, 8, False, False, 4, alpha=0.5))
+    out.append(strided("strides-big-NT", BIG, 50, 49, 7, False, True, 1, offA=1, beta=1.0))
     # ---- column sums (tA), onto a pre-filled colsum_out: riding along in k_mm_dma and k_mm_big, stand-alone next to k_mm, and split at K = 2304
     for tB in (False, True):
         o = ON[(True, tB)]
@@ -187,7 +202,7 @@ def _mm_cases():
 MM_CASES = _mm_cases()
 MM_RUN = [c for c in MM_CASES if c["kernel"] >= 0]
 MM_REFUSED = [c for c in MM_CASES if c["kernel"] < 0]
-SPOT_CASES = ["dma-TN-m48n48k4", "heads-big-all-strides", "epi-NT-n51-relu-beta1"]
+SPOT_CASES = ["dma-TN-m48n48k4", "heads-big-all-strides", "epi-NT-n51-relu-beta1", "strides-small-TN", "strides-dma-NN", "strides-big-NT"]
 
 
 # ---- buffers ----------------------------------------------------------------------------------------------------------------------------------

@@ -59,6 +59,14 @@ def test_the_table_reaches_every_kernel_orientation_epilogue_split_and_colsum_ro
         assert {c["m_dev"] for c in run if c["kernel"] == kernel and c["M"] == 132} >= {0, 1, 64, 65, 132}
         assert any(c["relu"] and c["bias"] for c in run if c["kernel"] == kernel)
         assert any(c["batch"] == 6 and c["H"] == 3 for c in run if c["kernel"] == kernel)
+        # all six strides at once, non-zero and pairwise different: two of them swapped in a call cannot go unseen
+        assert any(c["batch"] == 4 and c["H"] == 2 and all(c["strides"].values()) and len(set(c["strides"].values())) == 6
+                   for c in run if c["kernel"] == kernel)
+    # every option of a call leaves its default in some case that runs
+    for differs in (lambda c: c["bias"], lambda c: c["alpha"] != 1.0, lambda c: c["beta"] != 0.0, lambda c: c["relu"], lambda c: c["batch"] != 1,
+                    lambda c: c["H"] != 1, lambda c: c["c_is_zero"], lambda c: c["colsum"], lambda c: c["m_dev"] is not None, lambda c: c["a_kpad"],
+                    lambda c: c["a_rows"], *(lambda c, k=k: c["strides"][k] != 0 for k in ("sAb", "sAh", "sBb", "sBh", "sCb", "sCh"))):
+        assert any(differs(c) for c in run)
     dma = [c for c in run if c["kernel"] == gc.DMA]
     for relu in (False, True):
         assert {c["f4"] for c in dma if c["relu"] == relu and c["bias"]} == {True, False}
