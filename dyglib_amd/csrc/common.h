@@ -17,6 +17,12 @@ constexpr int kWave = 64;   // CDNA4 wavefront
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Carving a workspace into consecutive blocks: take(bytes) = the byte offset of the next block, every block 256-byte aligned; o = the total
+struct Carve {
+    size_t o = 0;
+    size_t take(size_t bytes) { const size_t r = o; o += (bytes + 255) & ~size_t(255); return r; }
+};
+
 // First index p in [lo, hi) with ts[p] >= t, or hi (np.searchsorted side='left' on an ascending CSR row).  A 64-ary search: every step the
 // wave probes 64 evenly spaced timestamps and one ballot+popcount picks the sub-range.  All 64 lanes must call (uniform lo/hi/t).
 __device__ __forceinline__ int64_t wave_lower_bound(const double* __restrict__ ts, int64_t lo, int64_t hi, double t, int lane) {

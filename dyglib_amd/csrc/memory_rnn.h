@@ -1,7 +1,7 @@
 // nn.RNNCell memory update of the JODIE / DyRep arms of the reference MemoryModel (memory_rnn.hip): the one-gate siblings of the GRU
 // row-block kernel (tgat_chain.h), in two forms -- one row per ROOT of a call (JODIE's rows; DyRep's returned rows) and one row per
-// LISTED node with the row count read on the device (DyRep's updated memories under the attention, TGN's list pass) -- and the commit of
-// the positive pairs from the per-root scratch.
+// LISTED node with the row count read on the device (DyRep's updated memories under the attention, TGN's list pass: the cell of
+// tgn::memory_update, tgn.h) -- and the commit of the positive pairs from the per-root scratch.  DyRep's entry points: tgn.hip.
 #pragma once
 #include "tgat_chain.h"
 

@@ -9,12 +9,13 @@
 //                          per-row scratch of the commit
 //   3. k_jodie_commit      positive pairs only: persists the updated memories / last-update times and stores the new raw messages, from
 //                          the per-row scratch alone
-// DyRep (tgat.hip: dyrep_forward_impl) uses the same row kernel without the projection for the rows it returns, k_rnn_list (the cell over
+// DyRep (tgn.hip: dyrep_forward_impl) uses the same row kernel without the projection for the rows it returns, k_rnn_list (the cell over
 // TGN's node lists, row count on the device) under its attention, and the same commit with the attention rows as the other endpoint's part.
 // The reference updates all num_nodes memories on every call (MemoryModel.py:108-109) and reads the roots' rows; here a root row is
 // computed where it is read, once per occurrence: a row's value is a fixed sequence of operations on its own message and memory (the
 // chain kernels' property), so duplicates carry the same bits and nothing of size [num_nodes] is allocated or touched.
 #include "memory_rnn.h"
+#include "tgn.h"
 #include "chain_stream.h"
 
 namespace dygnn {
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(kThreads) void k_rnn_rows(const RnnRowArgs a) {
     }
 }
 
-// End of a positive call, one launch, the form of k_tgn_commit (tgat.hip): entry e = role * n_pos + i (role 0 = source); messages are stored
+// End of a positive call, one launch, the form of k_tgn_commit (tgn.hip): entry e = role * n_pos + i (role 0 = source); messages are stored
 // source role first, then destination role, and only a node's LAST stored message is ever read (MemoryModel.py:284-291), so the last entry
 // of a node does the work for that node and the others exit.  Everything read here is the row kernel's per-row scratch (rows i and B + i
 // of the pair) and the call's inputs: no workgroup reads a state row that another one writes.
@@ -311,13 +312,12 @@ int memory_commit(hipStream_t s, const int64_t* src, const int64_t* dst, const d
 struct JodiePlan { size_t pack, upd, lu, pend, total; };
 static JodiePlan make_jodie_plan(int Fn, int Dm, int64_t B) {
     JodiePlan p{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~size_t(255); return r; };
-    p.pack = take(pack_bytes(plan_pack_rnn(Fn, Dm)));
-    p.upd = take((size_t)2 * B * Fn * sizeof(float));
-    p.lu = take((size_t)2 * B * sizeof(float));
-    p.pend = take((size_t)2 * B * sizeof(int32_t));
-    p.total = o;
+    Carve ws;
+    p.pack = ws.take(pack_bytes(plan_pack_rnn(Fn, Dm)));
+    p.upd = ws.take((size_t)2 * B * Fn * sizeof(float));
+    p.lu = ws.take((size_t)2 * B * sizeof(float));
+    p.pend = ws.take((size_t)2 * B * sizeof(int32_t));
+    p.total = ws.o;
     return p;
 }
 
@@ -358,8 +358,8 @@ extern "C" int dygnn_jodie_forward_step(const dygnn_tgat_config* cfg, const floa
     if (int rc = chain::check_jodie(cfg)) return rc;
     DYGNN_REQUIRE(n_pos >= 0 && n_pos <= batch, "jodie: n_positive must be in [0, batch]");
     DYGNN_REQUIRE(time_w && time_b && proj_w && proj_b, "jodie: null weights");
-    DYGNN_REQUIRE(rnn && rnn->weight_ih && rnn->weight_hh && rnn->bias_ih && rnn->bias_hh, "jodie: null RNN weights");
-    DYGNN_REQUIRE(st && st->memory && st->last_update && st->msg && st->msg_time && st->has_msg && st->num_nodes >= 1, "jodie: bad state");
+    if (int rc = check_cell(rnn, "jodie", "RNN weights")) return rc;
+    if (int rc = check_state(st, "jodie")) return rc;
     DYGNN_REQUIRE(batch >= 0 && edge_feat && workspace, "jodie: bad arguments");
     DYGNN_REQUIRE(batch == 0 || (src && dst && times && out_src && out_dst), "jodie: null pointer");
     DYGNN_REQUIRE(n_pos == 0 || edge_ids != nullptr, "jodie: edge_ids required for positive edges");   // MemoryModel.py:140

@@ -13,8 +13,8 @@
 #include "gemm.h"
 #include "tgat_chain.h"
 #include "tgat_attn.h"
-#include "tgat_levels.h"
-#include "memory_rnn.h"
+#include "tgat_stages.h"
+#include "tgn.h"
 
 namespace dygnn {
 
@@ -27,7 +27,7 @@ __device__ __forceinline__ f4 tmfma(float a, float b, f4 c) { return __builtin_a
 // TGN (MemoryModel.py:108-109, :609): the level-0 set of a call is what it reads.  Every level-0 slot (entry q, position j) stores
 // owner[id] = slot -- plain stores, some slot of a node wins; chain::pack's list blocks (tgat_chain.h: ListArgs) let the winner list its
 // node.  (Flags claimed with returning atomics cost 25 us per step here: 8,800 device-scope atomics on a 28-KB array.)
-// (struct TgnTouch: tgat_levels.h)
+// (struct TgnTouch: tgn.h)
 // `src` given: this is the top level [src ; dst] read straight from the caller's int64 / float64 arrays (B pairs)
 __global__ __launch_bounds__(256) void k_tgat_expand(const int64_t* __restrict__ indptr, const int32_t* __restrict__ cnbr,
                                                        const int32_t* __restrict__ ceid, const double* __restrict__ cts, int64_t num_nodes,
@@ -64,18 +64,6 @@ __global__ __launch_bounds__(256) void k_tgat_expand(const int64_t* __restrict__
         nbr_dt[q * k + j] = (float)(t - (double)tn);                    // models/TGAT.py:116-119: f64 - f32 -> f64 -> .float()
         if (tt.owner && nb >= 0 && nb < tt.N) tt.owner[nb] = (int32_t)(q * (k + 1) + j);
     }
-}
-
-// TGN on PRE-SAMPLED levels (random sampling strategies): what k_tgat_expand's `tt` does while it writes level 0 — every level-0 slot names
-// itself owner of its node (slot code: level-1 entry q, neighbour column j, or k for the entry itself), the two list counters are zeroed
-__global__ void k_tgn_touch_levels(const int32_t* __restrict__ ids0, int64_t n1, int k, TgnTouch tt) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < 2) tt.counts[i] = 0;
-    if (i >= n1 * (k + 1)) return;
-    const int32_t node = ids0[i];
-    if (node < 0 || node >= tt.N) return;
-    if (i < n1) tt.owner[node] = (int32_t)(i * (k + 1) + k);
-    else { const int64_t q = (i - n1) / k; tt.owner[node] = (int32_t)(q * (k + 1) + (i - n1 - q * k)); }
 }
 
 // the query-input rows alone, [n][Fn+Ft] = [h(self) | cos(b)]: one wave per row, four rows per workgroup, float4 copies (its predecessor, one
@@ -498,39 +486,38 @@ static TgatPlan make_tgat_plan(const dygnn_tgat_config& c, int64_t B) {
     p.Dq = p.Fn + p.Ft; p.Dkv = p.Fn + p.Fe + p.Ft; p.hd = p.H > 0 ? p.Dq / p.H : 0;
     p.n[p.L] = 2 * B;
     for (int l = p.L; l >= 1; --l) p.n[l - 1] = p.n[l] * (1 + p.k);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~size_t(255); return r; };
+    Carve ws;
     for (int l = 0; l <= p.L; ++l) {
-        p.ids[l] = take(p.n[l] * sizeof(int32_t));
-        p.times[l] = take(p.n[l] * sizeof(double));
-        p.h[l] = l >= 1 ? take((size_t)p.n[l] * p.Fn * sizeof(float)) : 0;
-        p.eid[l] = l >= 1 ? take((size_t)p.n[l] * p.k * sizeof(int32_t)) : 0;
-        p.dt[l] = l >= 1 ? take((size_t)p.n[l] * p.k * sizeof(float)) : 0;
+        p.ids[l] = ws.take(p.n[l] * sizeof(int32_t));
+        p.times[l] = ws.take(p.n[l] * sizeof(double));
+        p.h[l] = l >= 1 ? ws.take((size_t)p.n[l] * p.Fn * sizeof(float)) : 0;
+        p.eid[l] = l >= 1 ? ws.take((size_t)p.n[l] * p.k * sizeof(int32_t)) : 0;
+        p.dt[l] = l >= 1 ? ws.take((size_t)p.n[l] * p.k * sizeof(float)) : 0;
     }
     const int64_t nmax = p.L >= 1 ? p.n[1] : 0;                        // the largest computed level
-    p.q_in = take((size_t)nmax * p.Dq * sizeof(float));
-    p.qk = take((size_t)nmax * p.H * p.Dkv * sizeof(float));
-    p.z = take((size_t)nmax * p.H * p.Dkv * sizeof(float));
-    p.q = take((size_t)nmax * p.Dq * sizeof(float));
-    p.att = take((size_t)nmax * p.Dq * sizeof(float));
-    p.fc = take((size_t)nmax * p.Dq * sizeof(float));
-    p.merge_in = take((size_t)nmax * (p.Dq + p.Fn) * sizeof(float));
-    p.hid = take((size_t)nmax * p.Fn * sizeof(float));
-    p.cq = take((size_t)(p.L > 0 ? p.L : 1) * (p.Dq + p.Ft) * sizeof(float));      // per layer: the query's constant term [Dq] | cos(b) [Ft]
+    p.q_in = ws.take((size_t)nmax * p.Dq * sizeof(float));
+    p.qk = ws.take((size_t)nmax * p.H * p.Dkv * sizeof(float));
+    p.z = ws.take((size_t)nmax * p.H * p.Dkv * sizeof(float));
+    p.q = ws.take((size_t)nmax * p.Dq * sizeof(float));
+    p.att = ws.take((size_t)nmax * p.Dq * sizeof(float));
+    p.fc = ws.take((size_t)nmax * p.Dq * sizeof(float));
+    p.merge_in = ws.take((size_t)nmax * (p.Dq + p.Fn) * sizeof(float));
+    p.hid = ws.take((size_t)nmax * p.Fn * sizeof(float));
+    p.cq = ws.take((size_t)(p.L > 0 ? p.L : 1) * (p.Dq + p.Ft) * sizeof(float));      // per layer: the query's constant term [Dq] | cos(b) [Ft]
     if (p.L == 2) {
         p.dd_cap = 1024;
         while ((int64_t)p.dd_cap < 2 * p.n[1]) p.dd_cap <<= 1;
-        p.dd_slots = take((size_t)p.dd_cap * sizeof(int32_t));
-        p.dd_canon = take((size_t)p.n[1] * sizeof(int32_t));
-        p.dd_cidx = take((size_t)p.n[1] * sizeof(int32_t));
-        p.dd_map = take((size_t)p.n[1] * sizeof(int32_t));
-        p.dd_count = take(sizeof(int32_t));
-        p.dd_ids = take((size_t)p.n[1] * sizeof(int32_t));
-        p.dd_times = take((size_t)p.n[1] * sizeof(double));
+        p.dd_slots = ws.take((size_t)p.dd_cap * sizeof(int32_t));
+        p.dd_canon = ws.take((size_t)p.n[1] * sizeof(int32_t));
+        p.dd_cidx = ws.take((size_t)p.n[1] * sizeof(int32_t));
+        p.dd_map = ws.take((size_t)p.n[1] * sizeof(int32_t));
+        p.dd_count = ws.take(sizeof(int32_t));
+        p.dd_ids = ws.take((size_t)p.n[1] * sizeof(int32_t));
+        p.dd_times = ws.take((size_t)p.n[1] * sizeof(double));
     }
     // packed weight fragments of the row-block chains (tgat_chain.h), with room for the GRU of a TGN call
-    p.pack = take(chain::pack_bytes(chain::plan_pack(p.L, p.Fn, p.Ft, p.Dkv, p.H > 0 ? p.H : 1, 2 * p.Fn + p.Ft + p.Fe)));
-    p.total = o;
+    p.pack = ws.take(chain::pack_bytes(chain::plan_pack(p.L, p.Fn, p.Ft, p.Dkv, p.H > 0 ? p.H : 1, 2 * p.Fn + p.Ft + p.Fe)));
+    p.total = ws.o;
     return p;
 }
 
@@ -626,19 +613,23 @@ extern "C" size_t dygnn_tgat_workspace_bytes(const dygnn_tgat_config* cfg, int64
 }
 
 namespace dygnn {
+size_t tgat_plan_bytes(const dygnn_tgat_config& cfg, int64_t batch) { return make_tgat_plan(cfg, batch).total; }
+
 // Distinct entries of level 1 are computed once (see k_dedup_insert): only when the library samples itself (`recent` is a function of
 // (node, time); pre-sampled random levels draw independently per entry) and the pair attention kernel, which knows the row map, applies.
 // Decided once per library call, by its entry point.
-static bool tgat_dedup_active(const TgatPlan& p, bool presampled) {
+static bool tgat_dedup_active(const dygnn_tgat_config& c, bool presampled) {
     const char* dd_env = getenv("DYGNN_TGAT_DEDUP");                 // "0" switches it off (read per call: the A/B switch of tests/test_tgat.py)
     const bool dedup_on = !(dd_env && dd_env[0] == '0');
-    return dedup_on && !presampled && p.L == 2 && p.k <= 20 && p.H <= 2 && p.Dkv <= 512;
+    return dedup_on && !presampled && c.num_layers == 2 && c.num_neighbors <= 20 && c.num_heads <= 2 &&
+           c.node_feat_dim + c.edge_feat_dim + c.time_feat_dim <= 512;
 }
-// The argument checks of a TGAT / TGN inference call.  `levels` given: the caller's pre-sampled levels (copy_levels checks them), csr and the
-// roots are not read.
-static int check_tgat_args(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_csr* csr, const dygnn_tgat_levels* levels,
-                           const float* node_feat, const float* edge_feat, const TgatRoots& r, const float* out_src, const float* out_dst,
-                           const void* workspace, size_t workspace_bytes) {
+TgatStages tgat_stages(const dygnn_tgat_config& cfg, int64_t batch, void* workspace, hipStream_t s, bool presampled) {
+    return TgatStages{cfg, batch, static_cast<char*>(workspace), s, tgat_dedup_active(cfg, presampled)};
+}
+
+int check_tgat_args(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_csr* csr, const dygnn_tgat_levels* levels, const float* node_feat,
+                    const float* edge_feat, const TgatRoots& r, const float* out_src, const float* out_dst, const void* workspace, size_t workspace_bytes) {
     if (int rc = check_tgat(cfg)) return rc;
     DYGNN_REQUIRE(w && w->time_w && w->time_b, "tgat: null weights");
     DYGNN_REQUIRE(levels || (csr && csr->indptr && csr->num_nodes >= 1), "tgat: bad csr");
@@ -653,18 +644,14 @@ static int check_tgat_args(const dygnn_tgat_config* cfg, const dygnn_tgat_weight
     return check_layer_weights(w, cfg->num_layers, "tgat: null layer weights");
 }
 
-// What the level stage and the layer stage of one call share
-struct TgatStages {
-    const TgatPlan& p;
-    char* ws;             // the call's TgatPlan workspace
-    hipStream_t s;
-    bool dedup;           // tgat_dedup_active
-};
+TgatLevel0 tgat_level0(const TgatStages& c) {
+    const TgatPlan p = make_tgat_plan(c.cfg, c.B);
+    return TgatLevel0{reinterpret_cast<const int32_t*>(c.ws + p.ids[0]), c.dedup ? reinterpret_cast<const int32_t*>(c.ws + p.dd_count) : nullptr, p.n[0], p.n[1],
+                      reinterpret_cast<float*>(c.ws + p.pack)};
+}
 
-// Level stage: the level arrays of the call in its workspace, sampled from the graph (`recent`) or copied from the caller's `levels`.
-// touch (TGN): every level-0 slot names itself owner of its node.
-static int tgat_levels(const TgatStages& c, const dygnn_csr* csr, const TgatRoots& roots, const dygnn_tgat_levels* levels, const TgnTouch* touch) {
-    const TgatPlan& p = c.p;
+int tgat_levels(const TgatStages& c, const dygnn_csr* csr, const TgatRoots& roots, const dygnn_tgat_levels* levels, const TgnTouch* touch) {
+    const TgatPlan p = make_tgat_plan(c.cfg, c.B);
     auto I32 = [&](size_t off) { return reinterpret_cast<int32_t*>(c.ws + off); };
     auto F64 = [&](size_t off) { return reinterpret_cast<double*>(c.ws + off); };
     auto F32 = [&](size_t off) { return reinterpret_cast<float*>(c.ws + off); };
@@ -708,11 +695,8 @@ static int launch_attn_lin(hipStream_t s, const TgatPlan& p, const float* qk, co
     return launch_attn_lin_t<0, 2>(s, p, lds, qk, h_lower, node_feat, edge_feat, ids, eid, dt, tw, tb, n, scale, z);
 }
 
-// Layer stage: layers 1..L, bottom-up, on the levels in the workspace, into out_src / out_dst.  packed (TGN): the caller has packed the layer
-// weights into the workspace's row-block fragments, and the layers run as chains.
-static int tgat_layers(const TgatStages& c, const dygnn_tgat_weights* w, const float* node_feat, const float* edge_feat, float* out_src, float* out_dst,
-                       bool packed) {
-    const TgatPlan& p = c.p;
+int tgat_layers(const TgatStages& c, const dygnn_tgat_weights* w, const float* node_feat, const float* edge_feat, float* out_src, float* out_dst, bool packed) {
+    const TgatPlan p = make_tgat_plan(c.cfg, c.B);
     const hipStream_t s = c.s;
     const bool dedup = c.dedup;
     const int64_t B = p.n[p.L] / 2;
@@ -825,106 +809,11 @@ static int tgat_forward(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* 
                         size_t workspace_bytes, dygnn_stream_t stream) {
     if (int rc = check_tgat_args(cfg, w, csr, levels, node_feat, edge_feat, roots, out_src, out_dst, workspace, workspace_bytes)) return rc;
     if (roots.B == 0) return DYGNN_OK;
-    const TgatPlan p = make_tgat_plan(*cfg, roots.B);
-    const TgatStages c{p, static_cast<char*>(workspace), as_stream(stream), tgat_dedup_active(p, levels != nullptr)};
+    const TgatStages c = tgat_stages(*cfg, roots.B, workspace, as_stream(stream), levels != nullptr);
     if (int rc = tgat_levels(c, csr, roots, levels, nullptr)) return rc;
     return tgat_layers(c, w, node_feat, edge_feat, out_src, out_dst, false);
 }
 
-// ================================================================================================
-// TGN (BASELINE config 5; reference models/MemoryModel.py): memory bank + last-message aggregation + GRU update +
-// the same temporal graph attention over (memory + raw) node features.
-// State (owned by the caller, one per model): memory M [N][Fn], last-update time U [N] (float32), and ONE pending raw
-// message per node (msg [N][2Fn+Ft+Fe], its float64 time, a flag): the reference keeps a Python list per node
-// (MemoryModel.py:389-407) but its aggregator only ever reads the last element (:284-291), and lists are cleared
-// whole (:400-407), so the last message is the entire observable state.
-// ================================================================================================
-// End of a positive call, one launch: for every batch node (a) persist the updated memory if it had a pending message and (b) store its
-// new raw message (MemoryModel.py:142-161, :223-241, :425-459).  Messages are stored source role first, then destination role, and only a
-// node's LAST stored message is ever read (:284-291): entry e = role * B + i (role 0 = source); the last entry of a node does the work
-// for that node, the others exit.  "Had a pending message" is read from the call's pendf (written by the list pass), not from
-// has_msg, which this kernel rewrites; the other endpoint's updated memory is Mnew when it was pending, M when not (nobody writes it then),
-// so no workgroup reads what another one writes.
-__global__ __launch_bounds__(256) void k_tgn_commit(const int64_t* __restrict__ src, const int64_t* __restrict__ dst, const double* __restrict__ times,
-                                                      const int64_t* __restrict__ eids, int64_t B, const float* __restrict__ Mnew, const int32_t* __restrict__ pendf,
-                                                      float* __restrict__ M, float* __restrict__ U, const float* __restrict__ edge_feat,
-                                                      const float* __restrict__ tw, const float* __restrict__ tb, int Fn, int Fe, int Ft, float* __restrict__ msg,
-                                                      double* __restrict__ msg_t, int32_t* __restrict__ has_msg, int64_t N) {
-    const int64_t e = blockIdx.x;
-    const bool role = e >= B;
-    const int64_t i = role ? e - B : e;
-    const int64_t node = role ? dst[i] : src[i];
-    const int64_t o = role ? src[i] : dst[i];
-    if (node < 0 || node >= N || o < 0 || o >= N) return;      // never index the state tables out of range (the host API raises IndexError for such ids)
-    int later = 0;
-    for (int64_t e2 = e + 1 + threadIdx.x; e2 < 2 * B; e2 += blockDim.x) {
-        const int64_t i2 = e2 >= B ? e2 - B : e2;
-        const int64_t n2 = e2 >= B ? dst[i2] : src[i2], o2 = e2 >= B ? src[i2] : dst[i2];
-        later |= (n2 == node && o2 >= 0 && o2 < N) ? 1 : 0;
-    }
-    if (__syncthreads_or(later)) return;
-    const bool pend = pendf[node] != 0, pend_o = pendf[o] != 0;
-    const float* mn = pend ? Mnew + node * Fn : M + node * Fn;      // the node's updated memory (MemoryModel.py:142-145 persists exactly this)
-    const float* mo = pend_o ? Mnew + o * Fn : M + o * Fn;
-    const float u = pend ? (float)msg_t[node] : U[node];            // last-update time after the persist (:447-459)
-    const int D = 2 * Fn + Ft + Fe;
-    const float dt = (float)times[i] - u;                           // float32 - float32 (MemoryModel.py:232-233)
-    float* m = msg + node * D;
-    for (int f = threadIdx.x; f < D; f += blockDim.x) {
-        float v;
-        if (f < Fn) v = mn[f];
-        else if (f < 2 * Fn) v = mo[f - Fn];
-        else if (f < 2 * Fn + Ft) v = cosf(fmaf(dt, tw[f - 2 * Fn], tb[f - 2 * Fn]));
-        else v = edge_feat[(size_t)eids[i] * Fe + (f - 2 * Fn - Ft)];
-        m[f] = v;
-        if (pend && f < Fn) M[node * Fn + f] = v;                   // persist
-    }
-    __syncthreads();                                                // msg_t[node] was read above by every thread
-    if (threadIdx.x == 0) {
-        if (pend) U[node] = u;
-        msg_t[node] = times[i];
-        has_msg[node] = 1;
-    }
-}
-
-// ---- the nodes a call reads (TGN) --------------------------------------------------------------------------------------------
-// The reference updates the memory of every node with a pending message on every call (get_updated_memories over range(num_nodes),
-// MemoryModel.py:108-109) although a call only reads the rows of its level-0 set (roots and sampled neighbours).  Here the GRU runs
-// over exactly those: every level-0 slot names itself owner of its node (k_tgat_expand); the winning slot lists the node (the list blocks
-// of chain::pack's launch): with a pending message for the GRU row-block kernel (tgat_chain.hip: gathers the listed rows, runs both gate
-// products and scatters the new memory and feat0 = memory + raw), without one for the plain feat0 = memory + raw rows of the same launch.
-// Rows of a product do not depend on which other rows are in it, so every row read later is bit-identical to the all-nodes update.
-struct TgnPlan { size_t Mnew, feat0, tgat, owner, pendf, list, count, list2, count2, total; };
-static TgnPlan make_tgn_plan(const dygnn_tgat_config& c, int64_t N, int64_t B) {
-    TgnPlan p{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~size_t(255); return r; };
-    p.Mnew = take((size_t)N * c.node_feat_dim * sizeof(float));
-    p.feat0 = take((size_t)N * c.node_feat_dim * sizeof(float));
-    p.owner = take((size_t)N * sizeof(int32_t));             // the level-0 slot that speaks for a node / whether the node had a pending message
-    p.pendf = take((size_t)N * sizeof(int32_t));
-    p.count = take(2 * sizeof(int32_t));                     // the two list lengths
-    p.count2 = p.count + sizeof(int32_t);
-    p.list = take((size_t)N * sizeof(int32_t));
-    p.list2 = take((size_t)N * sizeof(int32_t));
-    p.tgat = take(make_tgat_plan(c, B).total);
-    p.total = o;
-    return p;
-}
-
-int tgn_touch_levels(hipStream_t s, const int32_t* ids0, int64_t n1, int k, const TgnTouch& touch) {
-    hipLaunchKernelGGL(k_tgn_touch_levels, dim3((unsigned)ceil_div(n1 * (k + 1), 256)), dim3(256), 0, s, ids0, n1, k, touch);
-    DYGNN_LAUNCH_CHECK();
-    return DYGNN_OK;
-}
-
-int tgn_commit(hipStream_t s, const int64_t* src, const int64_t* dst, const double* times, const int64_t* edge_ids, int64_t n_pos, const float* Mnew,
-               const int32_t* pendf, const dygnn_tgn_state* st, const float* edge_feat, const float* tw, const float* tb, int Fn, int Fe, int Ft) {
-    hipLaunchKernelGGL(k_tgn_commit, dim3((unsigned)(2 * n_pos)), dim3(256), 0, s, src, dst, times, edge_ids, n_pos, Mnew, pendf, st->memory, st->last_update, edge_feat,
-                       tw, tb, Fn, Fe, Ft, st->msg, st->msg_time, st->has_msg, st->num_nodes);
-    DYGNN_LAUNCH_CHECK();
-    return DYGNN_OK;
-}
 }  // namespace dygnn
 
 extern "C" int dygnn_tgat_forward_levels(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_tgat_levels* levels, const float* node_feat,
@@ -970,215 +859,4 @@ extern "C" int dygnn_tgat_forward_roots(const dygnn_tgat_config* cfg, const dygn
     const int64_t b = n_roots / 2;
     return tgat_forward(cfg, w, csr, nullptr, node_feat, edge_feat, TgatRoots{ids, ids + b, times, b, true}, out, out + (size_t)b * (cfg ? cfg->node_feat_dim : 0),
                         workspace, workspace_bytes, stream);
-}
-
-extern "C" size_t dygnn_tgn_workspace_bytes(const dygnn_tgat_config* cfg, int64_t num_nodes, int64_t batch) {
-    if (check_tgat(cfg) != DYGNN_OK || batch < 0 || num_nodes < 1) return 0;
-    return make_tgn_plan(*cfg, num_nodes, batch).total;
-}
-
-// The first n_pos pairs of the batch are positive edges (they update the state), the rest only read it.
-static int tgn_forward_impl(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_gru_weights* gru, const dygnn_csr* csr,
-                            const float* node_feat, const float* edge_feat, const dygnn_tgn_state* st, const int64_t* src, const int64_t* dst,
-                            const double* times, const int64_t* edge_ids, int64_t batch, int64_t n_pos, float* out_src,
-                            float* out_dst, void* workspace, size_t workspace_bytes, dygnn_stream_t stream, const dygnn_tgat_levels* levels = nullptr) {
-    const bool edges_are_positive = n_pos > 0;
-    if (int rc = check_tgat(cfg)) return rc;
-    DYGNN_REQUIRE(n_pos >= 0 && n_pos <= batch, "tgn: n_positive must be in [0, batch]");
-    DYGNN_REQUIRE(gru && gru->weight_ih && gru->weight_hh && gru->bias_ih && gru->bias_hh, "tgn: null GRU weights");
-    DYGNN_REQUIRE(st && st->memory && st->last_update && st->msg && st->msg_time && st->has_msg && st->num_nodes >= 1, "tgn: bad state");
-    DYGNN_REQUIRE(batch >= 0 && node_feat && edge_feat && workspace, "tgn: bad arguments");
-    DYGNN_REQUIRE(!edges_are_positive || edge_ids != nullptr, "tgn: edge_ids required for positive edges");   // MemoryModel.py:140
-    if (batch == 0) return DYGNN_OK;
-    const int64_t N = st->num_nodes;
-    const int Fn = cfg->node_feat_dim, Fe = cfg->edge_feat_dim, Ft = cfg->time_feat_dim, Dm = 2 * Fn + Ft + Fe;
-    const TgnPlan p = make_tgn_plan(*cfg, N, batch);
-    if (workspace_bytes < p.total) { set_error("tgn: workspace too small (%zu < %zu bytes)", workspace_bytes, p.total); return DYGNN_E_WORKSPACE; }
-    hipStream_t s = as_stream(stream);
-    char* ws = static_cast<char*>(workspace);
-    float* Mnew = reinterpret_cast<float*>(ws + p.Mnew);
-    float* feat0 = reinterpret_cast<float*>(ws + p.feat0);
-    int32_t* owner = reinterpret_cast<int32_t*>(ws + p.owner);
-    int32_t* pendf = reinterpret_cast<int32_t*>(ws + p.pendf);
-    int32_t* list = reinterpret_cast<int32_t*>(ws + p.list);
-    int32_t* count = reinterpret_cast<int32_t*>(ws + p.count);
-    int32_t* list2 = reinterpret_cast<int32_t*>(ws + p.list2);
-    int32_t* count2 = reinterpret_cast<int32_t*>(ws + p.count2);
-    char* wt = ws + p.tgat;
-    const TgatRoots roots{src, dst, times, batch, false};
-    if (int rc = check_tgat_args(cfg, w, csr, levels, feat0, edge_feat, roots, out_src, out_dst, wt, p.total - p.tgat)) return rc;
-    const TgatPlan tp = make_tgat_plan(*cfg, batch);
-    DYGNN_REQUIRE(chain::fits(tp.Fn, tp.Ft, tp.Dkv, tp.H), "tgn: feature dims do not fit the row-block kernels");
-    const TgatStages c{tp, wt, s, tgat_dedup_active(tp, levels != nullptr)};
-    // 0. the levels of this call (they depend on the graph only).  Their level-0 set is what the call reads: every slot of it names itself
-    //    owner of its node.  Pre-sampled levels: `uniform` / `time_interval_aware`, the caller replayed the sampler's RandomState
-    //    (MemoryModel.py:626-629)
-    const TgnTouch touch{owner, count, N};
-    if (int rc = tgat_levels(c, csr, roots, levels, &touch)) return rc;
-    // 1. one launch: the owners list their nodes -- pending message: GRU rows; none: feat0 = memory + raw (MemoryModel.py:609) -- and the weights
-    //    of the GRU and of the layers are packed into operand fragments (tgat_chain.h); then the updated memories of the listed nodes (the
-    //    reference updates all nodes, MemoryModel.py:108-109): one launch, row count on the device
-    const chain::PackPlan pp = chain::plan_pack(tp.L, tp.Fn, tp.Ft, tp.Dkv, tp.H, Dm);
-    float* pk = reinterpret_cast<float*>(wt + tp.pack);
-    const int32_t* live = c.dedup ? reinterpret_cast<const int32_t*>(wt + tp.dd_count) : nullptr;
-    const chain::ListArgs la{reinterpret_cast<const int32_t*>(wt + tp.ids[0]), live, owner, st->has_msg, pendf, count, list, count2, list2, tp.n[1], N, tp.k};
-    if (int rc = chain::pack(s, pp, tp.L, tp.Fn, tp.Ft, tp.Dkv, tp.H, w, gru, Dm, pk, &la)) return rc;
-    const int64_t ub = N < tp.n[0] ? N : tp.n[0];              // the list cannot be longer than the level-0 set
-    const chain::GruArgs ga{list, count, list2, count2, st->msg, st->memory, node_feat, pk, pp.ih, pp.hh, gru->bias_ih, gru->bias_hh, Mnew, feat0, ub, Dm, Fn};
-    if (int rc = chain::launch_gru(s, ga)) return rc;
-    // 2. temporal graph attention over (memory + raw) features (GraphAttentionEmbedding, MemoryModel.py:548-664) on the levels built above
-    if (int rc = tgat_layers(c, w, feat0, edge_feat, out_src, out_dst, true)) return rc;
-    if (!edges_are_positive) return DYGNN_OK;
-    // 3. persist the updated memories of the batch nodes and store their new raw messages (MemoryModel.py:142-161)
-    return tgn_commit(s, src, dst, times, edge_ids, n_pos, Mnew, pendf, st, edge_feat, w->time_w, w->time_b, Fn, Fe, Ft);
-}
-
-extern "C" int dygnn_tgn_forward(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_gru_weights* gru, const dygnn_csr* csr,
-                                 const float* node_feat, const float* edge_feat, const dygnn_tgn_state* st, const int64_t* src, const int64_t* dst,
-                                 const double* times, const int64_t* edge_ids, int64_t batch, int32_t edges_are_positive, float* out_src,
-                                 float* out_dst, void* workspace, size_t workspace_bytes, dygnn_stream_t stream) {
-    return tgn_forward_impl(cfg, w, gru, csr, node_feat, edge_feat, st, src, dst, times, edge_ids, batch, edges_are_positive ? batch : 0, out_src, out_dst,
-                            workspace, workspace_bytes, stream);
-}
-
-// dygnn_tgn_forward_step on PRE-SAMPLED levels: the reference accepts any sampling strategy for TGN (MemoryModel.py:626-629); `uniform` and
-// `time_interval_aware` draw from the sampler's numpy RandomState, which the host mirror replays in the reference's order (one call on
-// [src ; dst], MemoryModel.py:104-131) and hands over as level arrays in dygnn_tgat_forward_levels' layout.  src / dst / times are still read:
-// by the commit of a positive call (messages, last-update times).
-extern "C" int dygnn_tgn_forward_levels(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_gru_weights* gru,
-                                        const dygnn_tgat_levels* levels, const float* node_feat, const float* edge_feat, const dygnn_tgn_state* st,
-                                        const int64_t* src, const int64_t* dst, const double* times, const int64_t* edge_ids, int64_t batch,
-                                        int64_t n_positive, float* out_src, float* out_dst, void* workspace, size_t workspace_bytes, dygnn_stream_t stream) {
-    DYGNN_REQUIRE(levels != nullptr, "tgn_forward_levels: levels is NULL");
-    DYGNN_REQUIRE(n_positive == 0 || (src && dst && times), "tgn_forward_levels: a positive call needs src / dst / times");
-    return tgn_forward_impl(cfg, w, gru, nullptr, node_feat, edge_feat, st, src, dst, times, edge_ids, batch, n_positive, out_src, out_dst, workspace,
-                            workspace_bytes, stream, levels);
-}
-
-extern "C" int dygnn_tgn_forward_step(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_gru_weights* gru, const dygnn_csr* csr,
-                                      const float* node_feat, const float* edge_feat, const dygnn_tgn_state* st, const int64_t* src, const int64_t* dst,
-                                      const double* times, const int64_t* edge_ids, int64_t batch, int64_t n_positive, float* out_src,
-                                      float* out_dst, void* workspace, size_t workspace_bytes, dygnn_stream_t stream) {
-    return tgn_forward_impl(cfg, w, gru, csr, node_feat, edge_feat, st, src, dst, times, edge_ids, batch, n_positive, out_src, out_dst, workspace,
-                            workspace_bytes, stream);
-}
-
-// ================================================================================================
-// DyRep (reference models/MemoryModel.py with model_name == 'DyRep'): TGN's modules with nn.RNNCell in place of nn.GRUCell, and two twists
-// on the data flow (:163-166, :225-227): a call RETURNS the updated memories of its roots, and in a positive call the attention embedding
-// of the other endpoint of a pair takes the place of its memory in the new raw message.  So only the positive pairs need the attention:
-//   1. chain::pack_rnn + k_rnn_rows (memory_rnn.hip) over all roots [src ; dst] of the batch, without the time projection: the returned
-//      rows -- gathered from updated memory BEFORE the commit, which runs last -- and the per-root scratch of the commit.  A negative call
-//      (n_positive = 0) ends here: its attention would be thrown away (the reference still computes it).
-//   2. TGN's pipeline on the first n_positive pairs: levels (sampled here, or the caller's), owner slots, list pass + layer packing,
-//      k_rnn_list (the cell over the listed level-0 nodes, row count on the device) -> feat0 = updated memory + raw, the layers as chains
-//      -> attention rows [2 n_positive][Fn] in the workspace.
-//   3. chain::memory_commit with those rows as the "other endpoint" part of the messages.
-// ================================================================================================
-namespace dygnn {
-struct DyrepPlan { size_t tgn, rpk, upd, lu, pend, att, total; };
-static DyrepPlan make_dyrep_plan(const dygnn_tgat_config& c, int64_t N, int64_t B) {
-    DyrepPlan p{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~size_t(255); return r; };
-    const int Fn = c.node_feat_dim, Dm = 2 * Fn + c.time_feat_dim + c.edge_feat_dim;
-    p.tgn = take(make_tgn_plan(c, N, B).total);                  // room for every n_positive <= B
-    p.rpk = take(chain::pack_bytes(chain::plan_pack_rnn(Fn, Dm)));
-    p.upd = take((size_t)2 * B * Fn * sizeof(float));
-    p.lu = take((size_t)2 * B * sizeof(float));
-    p.pend = take((size_t)2 * B * sizeof(int32_t));
-    p.att = take((size_t)2 * B * Fn * sizeof(float));
-    p.total = o;
-    return p;
-}
-
-static int dyrep_forward_impl(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_rnn_weights* rnn, const dygnn_csr* csr,
-                              const dygnn_tgat_levels* levels, const float* node_feat, const float* edge_feat, const dygnn_tgn_state* st,
-                              const int64_t* src, const int64_t* dst, const double* times, const int64_t* edge_ids, int64_t batch, int64_t n_pos,
-                              float* out_src, float* out_dst, void* workspace, size_t workspace_bytes, dygnn_stream_t stream) {
-    if (int rc = check_tgat(cfg)) return rc;
-    if (int rc = chain::check_rnn_dims("dyrep", cfg->node_feat_dim, cfg->edge_feat_dim, cfg->time_feat_dim)) return rc;
-    DYGNN_REQUIRE(n_pos >= 0 && n_pos <= batch, "dyrep: n_positive must be in [0, batch]");
-    DYGNN_REQUIRE(rnn && rnn->weight_ih && rnn->weight_hh && rnn->bias_ih && rnn->bias_hh, "dyrep: null RNN weights");
-    DYGNN_REQUIRE(st && st->memory && st->last_update && st->msg && st->msg_time && st->has_msg && st->num_nodes >= 1, "dyrep: bad state");
-    DYGNN_REQUIRE(batch >= 0 && node_feat && edge_feat && workspace && w && w->time_w && w->time_b, "dyrep: bad arguments");
-    DYGNN_REQUIRE(batch == 0 || (src && dst && times && out_src && out_dst), "dyrep: null pointer");
-    DYGNN_REQUIRE(n_pos == 0 || edge_ids != nullptr, "dyrep: edge_ids required for positive edges");   // MemoryModel.py:140
-    DYGNN_REQUIRE(batch == 0 || out_dst == out_src + (size_t)batch * cfg->node_feat_dim, "dyrep: out_dst must follow out_src (one [2, batch, dim] block)");
-    if (batch == 0) return DYGNN_OK;
-    const int64_t N = st->num_nodes;
-    const int Fn = cfg->node_feat_dim, Fe = cfg->edge_feat_dim, Ft = cfg->time_feat_dim, Dm = 2 * Fn + Ft + Fe;
-    const DyrepPlan p = make_dyrep_plan(*cfg, N, batch);
-    if (workspace_bytes < p.total) { set_error("dyrep: workspace too small (%zu < %zu bytes)", workspace_bytes, p.total); return DYGNN_E_WORKSPACE; }
-    hipStream_t s = as_stream(stream);
-    char* ws = static_cast<char*>(workspace);
-    float* rpk = reinterpret_cast<float*>(ws + p.rpk);
-    float* upd = reinterpret_cast<float*>(ws + p.upd);
-    float* lu = reinterpret_cast<float*>(ws + p.lu);
-    int32_t* pend = reinterpret_cast<int32_t*>(ws + p.pend);
-    float* att_src = reinterpret_cast<float*>(ws + p.att);
-    float* att_dst = att_src + (size_t)n_pos * Fn;
-    // 1. the returned rows: the updated memories of the roots, before anything is committed
-    const chain::RnnPackPlan rp = chain::plan_pack_rnn(Fn, Dm);
-    if (int rc = chain::pack_rnn(s, rp, Fn, Dm, rnn, rpk)) return rc;
-    chain::RnnRowArgs ra{src, dst, times, batch, N, st->msg, st->memory, st->last_update, st->msg_time, st->has_msg, rpk, rp.ih, rp.hh,
-                         rnn->bias_ih, rnn->bias_hh, nullptr, nullptr, {0.f, 0.f}, {1.f, 1.f}, out_src, upd, lu, pend, Dm, Fn};
-    if (int rc = chain::launch_rnn_rows(s, ra)) return rc;
-    if (n_pos == 0) return DYGNN_OK;
-    // 2. the attention embeddings of the positive pairs, over updated memory + raw features (TGN's pipeline with the RNN cell)
-    const TgnPlan tn = make_tgn_plan(*cfg, N, n_pos);
-    char* wn = ws + p.tgn;
-    float* Mnew = reinterpret_cast<float*>(wn + tn.Mnew);
-    float* feat0 = reinterpret_cast<float*>(wn + tn.feat0);
-    int32_t* owner = reinterpret_cast<int32_t*>(wn + tn.owner);
-    int32_t* pendf = reinterpret_cast<int32_t*>(wn + tn.pendf);
-    int32_t* list = reinterpret_cast<int32_t*>(wn + tn.list);
-    int32_t* count = reinterpret_cast<int32_t*>(wn + tn.count);
-    int32_t* list2 = reinterpret_cast<int32_t*>(wn + tn.list2);
-    int32_t* count2 = reinterpret_cast<int32_t*>(wn + tn.count2);
-    char* wt = wn + tn.tgat;
-    const TgatRoots roots{src, dst, times, n_pos, false};
-    if (int rc = check_tgat_args(cfg, w, csr, levels, feat0, edge_feat, roots, att_src, att_dst, wt, tn.total - tn.tgat)) return rc;
-    const TgatPlan tp = make_tgat_plan(*cfg, n_pos);
-    DYGNN_REQUIRE(chain::fits(tp.Fn, tp.Ft, tp.Dkv, tp.H), "dyrep: feature dims do not fit the row-block kernels");
-    const TgatStages c{tp, wt, s, tgat_dedup_active(tp, levels != nullptr)};
-    const TgnTouch touch{owner, count, N};
-    if (int rc = tgat_levels(c, csr, roots, levels, &touch)) return rc;
-    const chain::PackPlan pp = chain::plan_pack(tp.L, tp.Fn, tp.Ft, tp.Dkv, tp.H, 0);
-    float* pk = reinterpret_cast<float*>(wt + tp.pack);
-    const int32_t* live = c.dedup ? reinterpret_cast<const int32_t*>(wt + tp.dd_count) : nullptr;
-    const chain::ListArgs la{reinterpret_cast<const int32_t*>(wt + tp.ids[0]), live, owner, st->has_msg, pendf, count, list, count2, list2, tp.n[1], N, tp.k};
-    if (int rc = chain::pack(s, pp, tp.L, tp.Fn, tp.Ft, tp.Dkv, tp.H, w, nullptr, 0, pk, &la)) return rc;
-    const int64_t ub = N < tp.n[0] ? N : tp.n[0];
-    const chain::GruArgs ga{list, count, list2, count2, st->msg, st->memory, node_feat, rpk, rp.ih, rp.hh, rnn->bias_ih, rnn->bias_hh, Mnew, feat0, ub, Dm, Fn};
-    if (int rc = chain::launch_rnn_list(s, ga)) return rc;
-    if (int rc = tgat_layers(c, w, feat0, edge_feat, att_src, att_dst, true)) return rc;
-    // 3. persist and store: the other endpoint's part of a message is its attention row (MemoryModel.py:225-227)
-    return chain::memory_commit(s, src, dst, times, edge_ids, n_pos, batch, upd, lu, pend, att_src, att_dst, st, edge_feat, w->time_w, w->time_b, Fn, Fe, Ft);
-}
-}  // namespace dygnn
-
-extern "C" size_t dygnn_dyrep_workspace_bytes(const dygnn_tgat_config* cfg, int64_t num_nodes, int64_t batch) {
-    if (check_tgat(cfg) != DYGNN_OK || batch < 0 || num_nodes < 1) return 0;
-    if (chain::check_rnn_dims("dyrep", cfg->node_feat_dim, cfg->edge_feat_dim, cfg->time_feat_dim) != DYGNN_OK) return 0;
-    return make_dyrep_plan(*cfg, num_nodes, batch).total;
-}
-
-extern "C" int dygnn_dyrep_forward_step(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_rnn_weights* rnn, const dygnn_csr* csr,
-                                        const float* node_feat, const float* edge_feat, const dygnn_tgn_state* st, const int64_t* src, const int64_t* dst,
-                                        const double* times, const int64_t* edge_ids, int64_t batch, int64_t n_positive, float* out_src,
-                                        float* out_dst, void* workspace, size_t workspace_bytes, dygnn_stream_t stream) {
-    return dyrep_forward_impl(cfg, w, rnn, csr, nullptr, node_feat, edge_feat, st, src, dst, times, edge_ids, batch, n_positive, out_src, out_dst, workspace,
-                              workspace_bytes, stream);
-}
-
-// dygnn_dyrep_forward_step on PRE-SAMPLED levels of the first n_positive pairs (dygnn_tgn_forward_levels' layout with batch = n_positive;
-// not read when n_positive = 0)
-extern "C" int dygnn_dyrep_forward_levels(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_rnn_weights* rnn,
-                                          const dygnn_tgat_levels* levels, const float* node_feat, const float* edge_feat, const dygnn_tgn_state* st,
-                                          const int64_t* src, const int64_t* dst, const double* times, const int64_t* edge_ids, int64_t batch,
-                                          int64_t n_positive, float* out_src, float* out_dst, void* workspace, size_t workspace_bytes, dygnn_stream_t stream) {
-    DYGNN_REQUIRE(n_positive <= 0 || levels != nullptr, "dyrep_forward_levels: levels is NULL");
-    return dyrep_forward_impl(cfg, w, rnn, nullptr, levels, node_feat, edge_feat, st, src, dst, times, edge_ids, batch, n_positive, out_src, out_dst, workspace,
-                              workspace_bytes, stream);
 }

@@ -1,4 +1,5 @@
 // Host glue shared by the TGAT inference (tgat.hip) and training (tgat_train.hip) paths: argument checks and the level sets of a call.
+// (The inference stages built on it: tgat_stages.h; what TGN adds to a level-0 set: tgn.h.)
 // Level L = the 2B roots [src ; dst]; level l-1 = [level l ; its k neighbours (row-major n[l] x k)]; for l >= 1 the neighbours' edge ids and
 // time deltas (eid / dt [n[l]][k]) belong to level l.
 #pragma once
@@ -24,12 +25,7 @@ struct TgatRoots {
 };
 
 struct DedupBufs;      // tgat.hip: de-duplication of level 1 (inference)
-// TGN's owner slots of level 0 (tgat.hip: k_tgat_expand, k_tgn_touch_levels)
-struct TgnTouch {
-    int32_t* owner;                // [N]; entries of nodes outside this call's level-0 set are stale and never read
-    int32_t* counts;               // the two list lengths, zeroed here for the list pass of the next launch
-    int64_t N;
-};
+struct TgnTouch;       // tgn.h: TGN's owner slots of level 0
 
 int check_tgat(const dygnn_tgat_config* c);
 // every pointer of w->layers[0..L-1]; the message is "<what> (layer l)"
@@ -41,13 +37,5 @@ int copy_levels(hipStream_t s, const dygnn_tgat_levels* lv, int L, int k, const 
 // as they are (it reads the roots instead).  dd: level 1 is expanded from its distinct entries; touch: TGN's owner slots of level 0.
 int expand_levels(hipStream_t s, const dygnn_csr* csr, const TgatRoots& roots, int L, int k, const LevelBufs& to, const DedupBufs* dd = nullptr,
                   const TgnTouch* touch = nullptr);
-
-// TGN on levels that are already in place (ids0 = [n1 entries | n1 * k neighbours]): every level-0 slot names itself owner of its node and the
-// two list counters are zeroed, as expand_levels' `touch` does while it samples (the inference path on pre-sampled levels; the training path)
-int tgn_touch_levels(hipStream_t s, const int32_t* ids0, int64_t n1, int k, const TgnTouch& touch);
-// End of a positive TGN call (k_tgn_commit): persist the updated memories Mnew of the first n_pos pairs' nodes where pendf says they had a
-// pending message, and store their new raw messages.  ONE implementation for inference and training: the state a call leaves is the same bits.
-int tgn_commit(hipStream_t s, const int64_t* src, const int64_t* dst, const double* times, const int64_t* edge_ids, int64_t n_pos, const float* Mnew,
-               const int32_t* pendf, const dygnn_tgn_state* st, const float* edge_feat, const float* tw, const float* tb, int Fn, int Fe, int Ft);
 
 }  // namespace dygnn

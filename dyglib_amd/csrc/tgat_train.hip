@@ -1,7 +1,7 @@
 // TGAT training (SURVEY.md §8f-1 for BASELINE config 3): the forward of tgat.hip in TRAIN mode and its hand-written backward pass, so that
 // train_link_prediction.py:170-185, :242-257 (two calls, MergeLayer + BCE, loss.backward(), Adam) runs on the HIP path.
 //
-// Differences from the inference forward (tgat.hip: its level and layer stages, tgat_levels / tgat_layers):
+// Differences from the inference forward (tgat.hip: its level and layer stages, tgat_levels / tgat_layers, tgat_stages.h):
 //   * no de-duplication of level 1 and no row-block chains: every level entry is its own row, as in the reference recursion
 //     (models/TGAT.py:92-110), so each occurrence draws its own dropout mask and each level-(l-1) row has exactly ONE consumer
 //     (level l-1 = [level-l self rows ; their neighbour rows]).  The backward pass therefore WRITES the lower level's row gradients:

@@ -18,8 +18,8 @@
 #include "common.h"
 #include "gemm.h"
 #include "tgat_chain.h"
-#include "tgat_levels.h"
 #include "tgat_train.h"
+#include "tgn.h"
 
 namespace dygnn {
 namespace tgn {
@@ -77,13 +77,13 @@ __global__ __launch_bounds__(256) void k_tgn_gru_bwd(const int32_t* __restrict__
 }
 
 // The layers' block, the meta words, the saved rows and the GRU backward's buffers (`rows` = min(N, the level-0 set's size) bounds the pending
-// list) and pos [N]; then what only the forward call uses.
+// list) and pos [N]; then what only the forward call uses: the per-node scratch (its two counters are the meta words) and the GRU's fragments.
 struct Plan {
     int Fn, Dm;
     int64_t rows;
     size_t tgat, meta, msgs, hold, dfeat, gi, gh, pos;
-    size_t Mnew, feat0, owner, pendf, list, list2, pack, total;
-    chain::PackPlan pp;
+    ScratchPlan mem;
+    size_t pack, total;
 };
 
 static Plan make_plan(const dygnn_tgat_config& c, int64_t N, int64_t B) {
@@ -93,25 +93,19 @@ static Plan make_plan(const dygnn_tgat_config& c, int64_t N, int64_t B) {
     int64_t n0 = 2 * B;
     for (int l = 0; l < c.num_layers; ++l) n0 *= 1 + c.num_neighbors;
     p.rows = N < n0 ? N : n0;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~size_t(255); return r; };
-    p.tgat = take(tgt::train_plan_bytes(c, B));
-    p.meta = take(4 * sizeof(int32_t));
-    p.msgs = take((size_t)p.rows * p.Dm * sizeof(float));
-    p.hold = take((size_t)p.rows * p.Fn * sizeof(float));
-    p.dfeat = take((size_t)p.rows * p.Fn * sizeof(float));
-    p.gi = take((size_t)p.rows * 3 * p.Fn * sizeof(float));
-    p.gh = take((size_t)p.rows * 3 * p.Fn * sizeof(float));
-    p.pos = take((size_t)N * sizeof(int32_t));
-    p.Mnew = take((size_t)N * p.Fn * sizeof(float));
-    p.feat0 = take((size_t)N * p.Fn * sizeof(float));
-    p.owner = take((size_t)N * sizeof(int32_t));
-    p.pendf = take((size_t)N * sizeof(int32_t));
-    p.list = take((size_t)N * sizeof(int32_t));
-    p.list2 = take((size_t)N * sizeof(int32_t));
-    p.pp = chain::plan_pack(0, c.node_feat_dim, c.time_feat_dim, c.node_feat_dim + c.edge_feat_dim + c.time_feat_dim, c.num_heads, p.Dm);
-    p.pack = take(chain::pack_bytes(p.pp));
-    p.total = o;
+    Carve ws;
+    p.tgat = ws.take(tgt::train_plan_bytes(c, B));
+    p.meta = ws.take(4 * sizeof(int32_t));
+    p.msgs = ws.take((size_t)p.rows * p.Dm * sizeof(float));
+    p.hold = ws.take((size_t)p.rows * p.Fn * sizeof(float));
+    p.dfeat = ws.take((size_t)p.rows * p.Fn * sizeof(float));
+    p.gi = ws.take((size_t)p.rows * 3 * p.Fn * sizeof(float));
+    p.gh = ws.take((size_t)p.rows * 3 * p.Fn * sizeof(float));
+    p.pos = ws.take((size_t)N * sizeof(int32_t));
+    p.mem = carve_scratch(ws, N, p.Fn, false);
+    p.mem.count = p.meta + kCount * sizeof(int32_t);
+    p.pack = ws.take(chain::pack_bytes(chain::plan_pack(0, c.node_feat_dim, c.time_feat_dim, c.node_feat_dim + c.edge_feat_dim + c.time_feat_dim, c.num_heads, p.Dm)));
+    p.total = ws.o;
     return p;
 }
 
@@ -144,9 +138,8 @@ extern "C" int dygnn_tgn_train_forward(const dygnn_tgat_config* cfg, const dygnn
     DYGNN_REQUIRE(w && w->time_w && w->time_b && node_feat && edge_feat, "tgn_train_forward: null pointer");
     DYGNN_REQUIRE(batch > 0 && out_src && out_dst && workspace, "tgn_train_forward: bad arguments");
     DYGNN_REQUIRE(n_pos >= 0 && n_pos <= batch, "tgn_train_forward: n_positive must be in [0, batch]");
-    DYGNN_REQUIRE(gru && gru->weight_ih && gru->weight_hh && gru->bias_ih && gru->bias_hh, "tgn_train_forward: null GRU weights");
-    DYGNN_REQUIRE(st && st->memory && st->last_update && st->msg && st->msg_time && st->has_msg && st->num_nodes >= 1 && st->num_nodes <= INT32_MAX,
-                  "tgn_train_forward: bad state");
+    if (int rc = check_cell(gru, "tgn_train_forward", "GRU weights")) return rc;
+    if (int rc = check_state(st, "tgn_train_forward", INT32_MAX)) return rc;
     DYGNN_REQUIRE(n_pos == 0 || edge_ids != nullptr, "tgn_train_forward: edge_ids required for positive edges");      // MemoryModel.py:140
     DYGNN_REQUIRE(levels ? (n_pos == 0 || (src && dst && times)) : (csr && csr->indptr && csr->num_nodes >= 1 && src && dst && times),
                   "tgn_train_forward: need csr + src / dst / times (with levels: for a positive call)");
@@ -159,28 +152,26 @@ extern "C" int dygnn_tgn_train_forward(const dygnn_tgat_config* cfg, const dygnn
     char* ws = static_cast<char*>(workspace);
     auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     auto I32 = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
-    const int Fn = cfg->node_feat_dim, Fe = cfg->edge_feat_dim, Ft = cfg->time_feat_dim, k = cfg->num_neighbors;
+    const int Fn = cfg->node_feat_dim, Fe = cfg->edge_feat_dim, Ft = cfg->time_feat_dim;
     int32_t* meta = I32(p.meta);
+    const tgn::Scratch m = tgn::scratch_at(ws, p.mem);
     // 0. the levels of this call; every slot of their level-0 set names itself owner of its node
     if (int rc = tgt::train_levels(s, *cfg, csr, levels, src, dst, times, batch, ws + p.tgat, "tgn_train_forward")) return rc;
     const tgt::TrainLevel0 l0 = tgt::train_level0(*cfg, batch, ws + p.tgat);
-    if (int rc = tgn_touch_levels(s, l0.ids0, l0.n1, k, TgnTouch{I32(p.owner), meta, N})) return rc;
-    // 1. the inference path's list pass and GRU: Mnew (what a positive call commits) and feat0 = updated memory + raw for the call's nodes
-    const chain::ListArgs la{l0.ids0, nullptr, I32(p.owner), st->has_msg, I32(p.pendf), meta + tgn::kCount, I32(p.list), meta + tgn::kCount2, I32(p.list2),
-                             l0.n1, N, k};
-    if (int rc = chain::pack(s, p.pp, 0, Fn, Ft, Fn + Fe + Ft, cfg->num_heads, w, gru, p.Dm, F32(p.pack), &la)) return rc;
-    const chain::GruArgs ga{I32(p.list), meta + tgn::kCount, I32(p.list2), meta + tgn::kCount2, st->msg, st->memory, node_feat, F32(p.pack), p.pp.ih, p.pp.hh,
-                            gru->bias_ih, gru->bias_hh, F32(p.Mnew), F32(p.feat0), p.rows, p.Dm, Fn};
-    if (int rc = chain::launch_gru(s, ga)) return rc;
+    if (int rc = tgn_touch_levels(s, l0.ids0, l0.n1, cfg->num_neighbors, TgnTouch{m.owner, meta, N})) return rc;
+    // 1. the inference path's memory-update step, no layers packed (the training levels are not de-duplicated: no live count): Mnew (what a
+    //    positive call commits) and feat0 = updated memory + raw for the call's nodes
+    const tgn::Cell cell{gru, nullptr, 0, 0, gru->bias_ih, gru->bias_hh, chain::launch_gru};
+    if (int rc = tgn::memory_update(s, *cfg, 0, w, cell, TgatLevel0{l0.ids0, nullptr, l0.n0, l0.n1, F32(p.pack)}, m, st, node_feat)) return rc;
     // 2. what the GRU backward needs of the state, before the commit below (or a later call's) overwrites it
-    hipLaunchKernelGGL(tgn::k_tgn_save, dim3((unsigned)p.rows), dim3(256), 0, s, I32(p.list), I32(p.list2), meta, st->msg, st->memory, p.Dm, Fn, (int32_t)N, p.rows,
+    hipLaunchKernelGGL(tgn::k_tgn_save, dim3((unsigned)p.rows), dim3(256), 0, s, m.list, m.list2, meta, st->msg, st->memory, p.Dm, Fn, (int32_t)N, p.rows,
                        I32(p.pos), F32(p.msgs), F32(p.hold));
     DYGNN_LAUNCH_CHECK();
     // 3. the train-mode layers over feat0 (GraphAttentionEmbedding, MemoryModel.py:548-664)
-    if (int rc = tgt::train_forward(s, *cfg, w, F32(p.feat0), edge_feat, batch, dropout_p, seed, out_src, out_dst, ws + p.tgat)) return rc;
+    if (int rc = tgt::train_forward(s, *cfg, w, m.feat0, edge_feat, batch, dropout_p, seed, out_src, out_dst, ws + p.tgat)) return rc;
     if (n_pos == 0) return DYGNN_OK;
     // 4. persist the updated memories of the positive pairs' nodes and store their new raw messages (MemoryModel.py:142-161)
-    return tgn_commit(s, src, dst, times, edge_ids, n_pos, F32(p.Mnew), I32(p.pendf), st, edge_feat, w->time_w, w->time_b, Fn, Fe, Ft);
+    return tgn_commit(s, src, dst, times, edge_ids, n_pos, m.Mnew, m.pendf, st, edge_feat, w->time_w, w->time_b, Fn, Fe, Ft);
 }
 
 extern "C" int dygnn_tgn_backward(const dygnn_tgat_config* cfg, const dygnn_tgat_weights* w, const dygnn_gru_weights* gru, const dygnn_tgat_weights* grads,
@@ -189,8 +180,8 @@ extern "C" int dygnn_tgn_backward(const dygnn_tgat_config* cfg, const dygnn_tgat
     if (int rc = tgn::check_cfg(cfg)) return rc;
     DYGNN_REQUIRE(w && w->time_w && w->time_b && grads && grads->time_w && grads->time_b && grad_out_src && grad_out_dst && workspace && batch > 0,
                   "tgn_backward: bad arguments");
-    DYGNN_REQUIRE(gru && gru->weight_ih && gru->weight_hh && gru->bias_ih && gru->bias_hh, "tgn_backward: null GRU weights");
-    DYGNN_REQUIRE(gg && gg->weight_ih && gg->weight_hh && gg->bias_ih && gg->bias_hh, "tgn_backward: null GRU gradient buffer");
+    if (int rc = check_cell(gru, "tgn_backward", "GRU weights")) return rc;
+    if (int rc = check_cell(gg, "tgn_backward", "GRU gradient buffer")) return rc;
     DYGNN_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "tgn_backward: dropout must be in [0, 1)");
     DYGNN_REQUIRE(num_nodes >= 1 && num_nodes <= INT32_MAX, "tgn_backward: bad num_nodes");
     const tgn::Plan p = tgn::make_plan(*cfg, num_nodes, batch);

@@ -1,4 +1,4 @@
-"""dyglib_amd.JODIE and dyglib_amd.DyRep (dygnn_jodie_forward_step, dygnn_dyrep_forward_step / _levels; dyglib_amd/csrc/memory_rnn.hip, tgat.hip)
+"""dyglib_amd.JODIE and dyglib_amd.DyRep (dygnn_jodie_forward_step, dygnn_dyrep_forward_step / _levels; dyglib_amd/csrc/memory_rnn.hip, tgn.hip)
 on an MI355X: against the reference's own outputs (tests/golden/jodie_<case>.npz, dyrep_<case>[_<tag>].npz, eval_jodie.npz, eval_dyrep.npz) and,
 for shapes the fixtures do not cover, against tests/memory_variant_oracle.py.  Tolerance: tests.parity.close, 1e-4 absolute, as for TGN over
 the same chronological runs."""
