@@ -23,10 +23,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _capi
+from . import _capi, _glue
 from .modules import TimeEncoder, TransformerEncoder, fill_encoder_layer_weights
 from .neighbor_sampler import NeighborSampler
-from .tgat import _to_dev, _workspace
 
 
 class _CawnTrainFunction(torch.autograd.Function):
@@ -58,7 +57,7 @@ class _CawnTrainFunction(torch.autograd.Function):
                                                  roots.data_ptr(), tms.data_ptr(), C.byref(h), B, float(dropout_p), int(seed), out[0].data_ptr(),
                                                  out[1].data_ptr(), ws.data_ptr(), nbytes, _capi.current_stream_ptr()))
         ctx.cfg, ctx.w, ctx.ws, ctx.dropout_p, ctx.seed = cfg, w, ws, float(dropout_p), int(seed)
-        ctx.param_versions = [(p.data_ptr(), p._version) for p in params]
+        ctx.param_versions = _glue.param_versions(params)
         return out
 
     @staticmethod
@@ -68,17 +67,10 @@ class _CawnTrainFunction(torch.autograd.Function):
         if ctx.B == 0:
             return (None,) * (6 + len(params))
         dev = ctx.ws.device
-        g_src = (g_src if g_src is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
-        g_dst = (g_dst if g_dst is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
-        # the backward pass re-reads the CURRENT parameter values: they must be the ones the forward used
-        if [(p.data_ptr(), p._version) for p in params] != ctx.param_versions:
-            raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
-                               "a CAWN parameter changed between this call's forward and its backward")
-        sizes = [p.numel() for p in params]
-        # one fill for all gradient buffers; every buffer starts at a multiple of 4 floats (the library's products read float4)
-        starts = np.cumsum([0] + [(n + 3) // 4 * 4 for n in sizes])
-        flat = torch.zeros(int(starts[-1]), dtype=torch.float32, device=dev)
-        grads = [flat[int(a):int(a) + n].view_as(p) for a, n, p in zip(starts, sizes, params)]
+        g_src = _glue.grad_or_zeros(g_src, (ctx.B, model.node_feat_dim), dev)
+        g_dst = _glue.grad_or_zeros(g_dst, (ctx.B, model.node_feat_dim), dev)
+        _glue.check_param_versions(params, ctx.param_versions, "CAWN")
+        grads = _glue.zero_grads(params, dev, align_floats=4)                  # the library's products read the buffers as float4
         gstruct = model._weights({id(p): g for p, g in zip(params, grads)})
         _capi.check(model._lib.dygnn_cawn_backward(C.byref(ctx.cfg), C.byref(ctx.w), C.byref(gstruct), g_src.data_ptr(), g_dst.data_ptr(), ctx.B,
                                                    ctx.dropout_p, ctx.seed, ctx.ws.data_ptr(), ctx.ws.numel(), _capi.current_stream_ptr()))
@@ -162,10 +154,7 @@ class CAWN(nn.Module):
 
     def set_neighbor_sampler(self, neighbor_sampler: NeighborSampler):
         """models/CAWN.py:166-175."""
-        self.neighbor_sampler = neighbor_sampler
-        if self.neighbor_sampler.sample_neighbor_strategy in ["uniform", "time_interval_aware"]:
-            assert self.neighbor_sampler.seed is not None
-            self.neighbor_sampler.reset_random_state()
+        _glue.reset_sampler(self, neighbor_sampler)
 
     # ---- the reference's entry point ---------------------------------------------------------------------------------------------------
     def compute_src_dst_node_temporal_embeddings(self, src_node_ids, dst_node_ids, node_interact_times, num_neighbors: int = 20,
@@ -182,10 +171,7 @@ class CAWN(nn.Module):
         B = src.numel()
         sides = self._sample([src, dst], tms, num_neighbors)
         if train:
-            seed = getattr(self, "_fixed_dropout_seed", None)             # tests pin the masks; normally torch.manual_seed governs them
-            if seed is None:
-                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-            return _CawnTrainFunction.apply(self, sides, B, int(num_neighbors), float(self.dropout), seed, *self.parameters())
+            return _CawnTrainFunction.apply(self, sides, B, int(num_neighbors), float(self.dropout), _glue.dropout_seed(self), *self.parameters())
         idx = np.arange(B, dtype=np.int32)
         return self._forward(sides, idx, idx + B, num_neighbors, taps)
 
@@ -213,31 +199,23 @@ class CAWN(nn.Module):
         like the reference (IndexError; a target id of 0 is an AssertionError: the reference fails on it in pack_padded_sequence, its walks
         having length 0), and move ids (int64) and times (float64) to the model's device.  `trainable`: the caller has a differentiable path
         for train mode."""
-        if (torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters()))
-                and not (trainable and self.training and self._training_enabled)):
-            raise NotImplementedError("this dyglib_amd.CAWN call is inference-only on the HIP path: call it under torch.no_grad().  Gradients flow "
-                                      "through compute_src_dst_node_temporal_embeddings in train mode after enable_training() only (eval mode, "
-                                      "compute_step_embeddings and taps have no backward pass)")
+        _glue.refuse_untrainable(self, trainable and self._training_enabled,
+                                 "this dyglib_amd.CAWN call is inference-only on the HIP path: call it under torch.no_grad().  Gradients flow "
+                                 "through compute_src_dst_node_temporal_embeddings in train mode after enable_training() only (eval mode, "
+                                 "compute_step_embeddings and taps have no backward pass)")
         self.neighbor_sampler._check_strategy()
         assert num_neighbors > 0, "Number of sampled neighbors for each node should be greater than 0!"          # utils/utils.py:157
         assert self.walk_length > 0, "Number of sampled hops should be greater than 0!"                          # utils/utils.py:228
         _capi.check(self._lib.dygnn_cawn_check(C.byref(self._config(num_neighbors))))      # NotImplementedError with the library's message
         dev = self.walk_encoder.projection_layers[1].weight.device
-        csr = self.neighbor_sampler.csr
-        if getattr(self, "_validated_csr", None) is not csr:
-            csr.check_tables(self.node_raw_features.shape[0], self.edge_raw_features.shape[0])
-            self._validated_csr = csr
+        n_nodes = self.node_raw_features.shape[0]
+        _glue.validate_ids(self, self.neighbor_sampler.csr, id_arrays, n_nodes, n_nodes, self.edge_raw_features.shape[0])
         for ids in id_arrays:
-            csr.check_query_ids(ids, limit=self.node_raw_features.shape[0])
             if not isinstance(ids, torch.Tensor) and np.asarray(ids).size:
                 assert int(np.asarray(ids).min()) > 0, "cawn: node id 0 is the padding node: as a target its walks have length 0"
-        if dev.type != "cuda":
-            raise _capi.DygnnError("dyglib_amd.CAWN runs on an MI355X only; there is no CPU fallback")
-        if self.node_raw_features.device != dev:
-            self.node_raw_features = self.node_raw_features.to(dev)
-            self.edge_raw_features = self.edge_raw_features.to(dev)
-        parts = [_to_dev(ids, torch.int64, dev).reshape(-1) for ids in id_arrays]
-        tms = _to_dev(node_interact_times, torch.float64, dev).reshape(-1)
+        _glue.require_cuda_tables(self, dev)
+        parts = [_glue.to_dev(ids, torch.int64, dev).reshape(-1) for ids in id_arrays]
+        tms = _glue.to_dev(node_interact_times, torch.float64, dev).reshape(-1)
         assert all(p.numel() == tms.numel() for p in parts)
         return parts, tms
 
@@ -268,9 +246,7 @@ class CAWN(nn.Module):
     def _weights(self, replace: Optional[dict] = None) -> "_capi.CawnWeights":
         """ctypes view of the parameters; `replace` maps id(parameter) to another tensor of the same shape (the gradient buffers of the
         backward pass)."""
-        for p in self.parameters():
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise _capi.DygnnError("parameters must be contiguous float32")
+        _glue.require_f32_params(self.parameters())
         w = _capi.CawnWeights()
         p = (lambda t: t.data_ptr()) if replace is None else (lambda t: replace[id(t)].data_ptr())
         w.time_w, w.time_b = p(self.time_encoder.w.weight), p(self.time_encoder.w.bias)
@@ -294,7 +270,7 @@ class CAWN(nn.Module):
         nbytes = self._lib.dygnn_cawn_workspace_bytes(C.byref(cfg), n_sides, P)
         if nbytes == 0:                                  # AssertionError (bad argument) or NotImplementedError (unsupported) with the library's message
             _capi.check(self._lib.dygnn_cawn_check(C.byref(cfg)))
-        ws = _workspace(self._workspace, nbytes, (n_sides, P), num_neighbors, dev)
+        ws = _glue.workspace(self._workspace, nbytes, (n_sides, P), num_neighbors, dev)
         d, W1, M = self.node_feat_dim, self.walk_length + 1, int(num_neighbors) ** self.walk_length
         out_a = torch.empty((P, d), dtype=torch.float32, device=dev)
         out_b = torch.empty((P, d), dtype=torch.float32, device=dev)

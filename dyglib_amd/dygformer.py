@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 from torch.nn import MultiheadAttention
 
-from . import _capi
+from . import _capi, _glue
 from .modules import TimeEncoder
 from .neighbor_sampler import NeighborSampler
 
@@ -80,26 +80,18 @@ class _TrainFunction(torch.autograd.Function):
         _capi.check(rc)
         ctx.model, ctx.ws, ctx.seq, ctx.B, ctx.dropout_p, ctx.seed = model, ws, seq, B, float(dropout_p), int(seed)
         ctx.packed, ctx.weights = packed, weights
-        ctx.param_versions = [(p.data_ptr(), p._version) for p in model._param_list()]
+        ctx.param_versions = _glue.param_versions(model._param_list())
         return out_src, out_dst
 
     @staticmethod
     def backward(ctx, g_src, g_dst):
         model = ctx.model
         dev = ctx.ws.device
-        g_src = (g_src if g_src is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
-        g_dst = (g_dst if g_dst is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
+        g_src = _glue.grad_or_zeros(g_src, (ctx.B, model.node_feat_dim), dev)
+        g_dst = _glue.grad_or_zeros(g_dst, (ctx.B, model.node_feat_dim), dev)
         params = model._param_list()
-        # the backward pass re-reads the CURRENT parameter values: they must be the ones the forward used (PyTorch raises the same
-        # way when a tensor saved for backward was modified in place, e.g. by an optimizer step between forward and backward)
-        if [(p.data_ptr(), p._version) for p in params] != ctx.param_versions:
-            raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
-                               "a DyGFormer parameter changed between this call's forward and its backward")
-        sizes = model.__dict__.get("_psizes")
-        if sizes is None:
-            sizes = model.__dict__["_psizes"] = [p.numel() for p in params]
-        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)       # one fill for all gradient buffers
-        grads = [g.view_as(p) for g, p in zip(flat.split(sizes), params)]
+        _glue.check_param_versions(params, ctx.param_versions, "DyGFormer")
+        grads = _glue.zero_grads(params, dev)
         gstruct = model._weights_struct(grads)
         weights = ctx.weights
         rc = model._lib.dygnn_dygformer_backward(C.byref(model._cfg), C.byref(weights), C.byref(gstruct), g_src.data_ptr(), g_dst.data_ptr(), ctx.B,
@@ -247,10 +239,7 @@ class DyGFormer(nn.Module):
     # ---- reference API -------------------------------------------------------------------------
     def set_neighbor_sampler(self, neighbor_sampler: NeighborSampler):
         """models/DyGFormer.py:308-317."""
-        self.neighbor_sampler = neighbor_sampler
-        if self.neighbor_sampler.sample_neighbor_strategy in ["uniform", "time_interval_aware"]:
-            assert self.neighbor_sampler.seed is not None
-            self.neighbor_sampler.reset_random_state()
+        _glue.reset_sampler(self, neighbor_sampler)
 
     def compute_src_dst_node_temporal_embeddings(self, src_node_ids, dst_node_ids, node_interact_times,
                                                  _taps: Optional[dict] = None, _group_size: int = 0, _pair_stride: int = 0
@@ -340,13 +329,8 @@ class DyGFormer(nn.Module):
         return a.reshape(N, B, -1), b.reshape(N, B, -1)
 
     def _dropout_and_seed(self):
-        for p in self._param_list():
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise _capi.DygnnError("parameters must be contiguous float32")
-        seed = getattr(self, "_fixed_dropout_seed", None)             # tests pin the masks; normally torch.manual_seed governs them
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        return (float(self.dropout) if self.training else 0.0), seed
+        _glue.require_f32_params(self._param_list())
+        return (float(self.dropout) if self.training else 0.0), _glue.dropout_seed(self)
 
     def _seq_lens_groups(self, src_in, dst_in, t_in, src: torch.Tensor, dst: torch.Tensor, tms: torch.Tensor, dev):
         """(S_src, S_dst) of each of the N calls in [N, B] inputs, on the side stream (one synchronisation of IT, not of the main stream:
@@ -419,12 +403,8 @@ class DyGFormer(nn.Module):
     def _validate_ids(self, *id_arrays) -> None:
         """The reference trusts ids and fails with IndexError (list / tensor indexing); here host inputs are range-checked per call
         (two min/max over B ids) and the graph against the feature tables once per sampler, so no kernel can index outside a table."""
-        csr = self.neighbor_sampler.csr
-        if getattr(self, "_validated_csr", None) is not csr:
-            csr.check_tables(self.node_raw_features.shape[0], self.edge_raw_features.shape[0])
-            self._validated_csr = csr
-        for ids in id_arrays:
-            csr.check_query_ids(ids, limit=self.node_raw_features.shape[0])
+        n_nodes = self.node_raw_features.shape[0]
+        _glue.validate_ids(self, self.neighbor_sampler.csr, id_arrays, n_nodes, n_nodes, self.edge_raw_features.shape[0])
 
     def invalidate_packed(self) -> None:
         """Drop the kernel-ready weight copy.  It is re-packed automatically when a parameter's version counter or address changes
@@ -458,9 +438,7 @@ class DyGFormer(nn.Module):
 
     @staticmethod
     def _to_dev(x, dtype, dev) -> torch.Tensor:
-        if isinstance(x, torch.Tensor):
-            return x.to(device=dev, dtype=dtype).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(x, dtype={torch.int64: np.int64, torch.float64: np.float64}[dtype])).to(dev, non_blocking=True)
+        return _glue.to_dev(x, dtype, dev, non_blocking=True)
 
     def _weights_struct(self, replace: Optional[dict] = None) -> "_capi.DygformerWeights":
         """ctypes view of the parameters; `replace` maps parameter names to other tensors of the same shapes (the gradient
@@ -513,9 +491,7 @@ class DyGFormer(nn.Module):
                                                          _capi.current_stream_ptr()))
             self.__dict__["_packed_complete"] = True
         if self._packed is None or self._packed_key != key:
-            for p in plist:
-                if p.dtype != torch.float32 or not p.is_contiguous():
-                    raise _capi.DygnnError("parameters must be contiguous float32")
+            _glue.require_f32_params(plist)
             weights = self._weights_cached = self._weights_struct()
             nbytes = self._lib.dygnn_dygformer_packed_bytes(C.byref(self._cfg))
             if nbytes == 0:

@@ -22,10 +22,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _capi
+from . import _capi, _glue
 from .modules import TimeEncoder
 from .neighbor_sampler import NeighborSampler
-from .tgat import _to_dev, _workspace
 
 
 class _GraphMixerTrainFunction(torch.autograd.Function):
@@ -53,7 +52,7 @@ class _GraphMixerTrainFunction(torch.autograd.Function):
                                                        tms.data_ptr(), n, float(dropout_p), int(seed), out.data_ptr(), ws.data_ptr(), nbytes,
                                                        _capi.current_stream_ptr()))
         ctx.cfg, ctx.w, ctx.ws, ctx.dropout_p, ctx.seed = cfg, w, ws, float(dropout_p), int(seed)
-        ctx.param_versions = [(p.data_ptr(), p._version) for p in params]
+        ctx.param_versions = _glue.param_versions(params)
         return out
 
     @staticmethod
@@ -63,15 +62,10 @@ class _GraphMixerTrainFunction(torch.autograd.Function):
         if ctx.n == 0:
             return (None,) * (7 + len(params))
         dev = ctx.ws.device
-        g_out = (g_out if g_out is not None else torch.zeros((ctx.n, model.node_feat_dim), device=dev)).contiguous().float()
-        # the backward pass re-reads the CURRENT parameter values: they must be the ones the forward used
-        if [(p.data_ptr(), p._version) for p in params] != ctx.param_versions:
-            raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
-                               "a GraphMixer parameter changed between this call's forward and its backward")
+        g_out = _glue.grad_or_zeros(g_out, (ctx.n, model.node_feat_dim), dev)
+        _glue.check_param_versions(params, ctx.param_versions, "GraphMixer")
         trainable = [p for p in params if p.requires_grad]                    # the time encoder is frozen: no buffer, None below
-        sizes = [p.numel() for p in trainable]
-        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)       # one fill for all gradient buffers
-        grads = {id(p): g.view_as(p) for g, p in zip(flat.split(sizes), trainable)}
+        grads = {id(p): g for p, g in zip(trainable, _glue.zero_grads(trainable, dev))}
         gstruct = model._weights(grads)
         _capi.check(model._lib.dygnn_graphmixer_backward(C.byref(ctx.cfg), C.byref(ctx.w), C.byref(gstruct), g_out.data_ptr(), ctx.n, ctx.dropout_p,
                                                          ctx.seed, ctx.ws.data_ptr(), ctx.ws.numel(), _capi.current_stream_ptr()))
@@ -130,10 +124,7 @@ class GraphMixer(nn.Module):
 
     def set_neighbor_sampler(self, neighbor_sampler: NeighborSampler):
         """models/GraphMixer.py:152-160."""
-        self.neighbor_sampler = neighbor_sampler
-        if self.neighbor_sampler.sample_neighbor_strategy in ["uniform", "time_interval_aware"]:
-            assert self.neighbor_sampler.seed is not None
-            self.neighbor_sampler.reset_random_state()
+        _glue.reset_sampler(self, neighbor_sampler)
 
     # ---- the reference's entry points ------------------------------------------------------------------------------------------
     def compute_src_dst_node_temporal_embeddings(self, src_node_ids, dst_node_ids, node_interact_times, num_neighbors: int = 20,
@@ -174,28 +165,19 @@ class GraphMixer(nn.Module):
         """Refuse what is not built (autograd recording outside the training calls, random sampling, a CPU model), validate host ids like the
         reference (IndexError), and move ids (int64) and times (float64) to the model's device.  `trainable`: the caller has a differentiable
         path for train mode."""
-        if torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters())) and not (trainable and self.training):
-            raise NotImplementedError("this GraphMixer call is inference-only on the HIP path: call it under torch.no_grad().  Gradients flow "
-                                      "through compute_src_dst_node_temporal_embeddings and compute_node_temporal_embeddings (without taps) in "
-                                      "train mode only (eval mode and compute_step_embeddings have no backward pass)")
+        _glue.refuse_untrainable(self, trainable, "this GraphMixer call is inference-only on the HIP path: call it under torch.no_grad().  Gradients "
+                                 "flow through compute_src_dst_node_temporal_embeddings and compute_node_temporal_embeddings (without taps) in "
+                                 "train mode only (eval mode and compute_step_embeddings have no backward pass)")
         self.neighbor_sampler._check_strategy()
         if self.neighbor_sampler.sample_neighbor_strategy != "recent":
             raise NotImplementedError(f"GraphMixer on the HIP path samples on the device and supports sample_neighbor_strategy 'recent' only, not "
                                       f"'{self.neighbor_sampler.sample_neighbor_strategy}'")
         dev = self.output_layer.weight.device
-        if dev.type != "cuda":
-            raise _capi.DygnnError("dyglib_amd.GraphMixer runs on an MI355X only; there is no CPU fallback")
-        if self.node_raw_features.device != dev:
-            self.node_raw_features = self.node_raw_features.to(dev)
-            self.edge_raw_features = self.edge_raw_features.to(dev)
-        csr = self.neighbor_sampler.csr
-        if getattr(self, "_validated_csr", None) is not csr:
-            csr.check_tables(self.node_raw_features.shape[0], self.edge_raw_features.shape[0])
-            self._validated_csr = csr
-        for ids in id_arrays:
-            csr.check_query_ids(ids, limit=self.node_raw_features.shape[0])
-        parts = [_to_dev(ids, torch.int64, dev).reshape(-1) for ids in id_arrays]
-        tms = _to_dev(node_interact_times, torch.float64, dev).reshape(-1)
+        _glue.require_cuda_tables(self, dev)
+        n_nodes = self.node_raw_features.shape[0]
+        _glue.validate_ids(self, self.neighbor_sampler.csr, id_arrays, n_nodes, n_nodes, self.edge_raw_features.shape[0])
+        parts = [_glue.to_dev(ids, torch.int64, dev).reshape(-1) for ids in id_arrays]
+        tms = _glue.to_dev(node_interact_times, torch.float64, dev).reshape(-1)
         assert all(p.numel() == tms.numel() for p in parts)
         return parts, tms
 
@@ -208,9 +190,7 @@ class GraphMixer(nn.Module):
     def _weights(self, replace: Optional[dict] = None) -> "_capi.GraphmixerWeights":
         """ctypes view of the parameters; `replace` maps id(parameter) to another tensor of the same shape (the gradient buffers of the
         backward pass; a parameter it does not name, the frozen time encoder, becomes NULL)."""
-        for p in self.parameters():
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise _capi.DygnnError("parameters must be contiguous float32")
+        _glue.require_f32_params(self.parameters())
         w = _capi.GraphmixerWeights()
         p = (lambda t: t.data_ptr()) if replace is None else (lambda t: replace[id(t)].data_ptr() if id(t) in replace else None)
         w.time_w, w.time_b = p(self.time_encoder.w.weight), p(self.time_encoder.w.bias)
@@ -227,10 +207,8 @@ class GraphMixer(nn.Module):
     def _train_forward(self, nodes: torch.Tensor, tms: torch.Tensor, num_neighbors: int, time_gap: int) -> torch.Tensor:
         if self.num_layers > _capi.DYGNN_MAX_LAYERS or len(self.mlp_mixers) != self.num_layers:
             raise NotImplementedError(f"graphmixer: num_layers {self.num_layers} not supported (1..{_capi.DYGNN_MAX_LAYERS})")
-        seed = getattr(self, "_fixed_dropout_seed", None)                 # tests pin the masks; normally torch.manual_seed governs them
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        return _GraphMixerTrainFunction.apply(self, nodes, tms, int(num_neighbors), int(time_gap), float(self.dropout), seed, *self.parameters())
+        return _GraphMixerTrainFunction.apply(self, nodes, tms, int(num_neighbors), int(time_gap), float(self.dropout), _glue.dropout_seed(self),
+                                              *self.parameters())
 
     def _forward(self, nodes: torch.Tensor, tms: torch.Tensor, num_neighbors: int, time_gap: int, taps: Optional[int] = None):
         dev = nodes.device
@@ -241,7 +219,7 @@ class GraphMixer(nn.Module):
         nbytes = self._lib.dygnn_graphmixer_workspace_bytes(C.byref(cfg), n)
         if nbytes == 0:                                  # AssertionError (bad argument) or NotImplementedError (unsupported) with the library's message
             _capi.check(self._lib.dygnn_graphmixer_check(C.byref(cfg)))
-        ws = _workspace(self._workspace, nbytes, n, num_neighbors, dev)
+        ws = _glue.workspace(self._workspace, nbytes, n, num_neighbors, dev)
         out = torch.empty((n, self.node_feat_dim), dtype=torch.float32, device=dev)
         tap_struct, tap_out = None, None
         if taps is not None:

@@ -14,10 +14,10 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _capi
+from . import _capi, _glue
 from .modules import MergeLayer, TimeEncoder
 from .neighbor_sampler import NeighborSampler
-from .tgat import MultiHeadAttention, _tgat_levels, _tgat_weights, _to_dev, _workspace
+from .tgat import MultiHeadAttention, _tgat_levels, _tgat_weights
 
 
 class MemoryBank(nn.Module):
@@ -99,23 +99,18 @@ class _TgnTrainFunction(torch.autograd.Function):
             torch.cuda.current_stream(dev).synchronize()          # the level tensors may be freed afterwards
         ctx.model, ctx.cfg, ctx.w, ctx.gru, ctx.ws, ctx.B, ctx.dropout_p, ctx.seed = model, cfg, w, gru, ws, B, float(dropout_p), int(seed)
         ctx.feats = model.edge_raw_features                                   # read again by the backward pass
-        ctx.param_versions = [(p.data_ptr(), p._version) for p in params]
+        ctx.param_versions = _glue.param_versions(params)
         return out[0], out[1]
 
     @staticmethod
     def backward(ctx, g_src, g_dst):
         model = ctx.model
         dev = ctx.ws.device
-        g_src = (g_src if g_src is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
-        g_dst = (g_dst if g_dst is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
+        g_src = _glue.grad_or_zeros(g_src, (ctx.B, model.node_feat_dim), dev)
+        g_dst = _glue.grad_or_zeros(g_dst, (ctx.B, model.node_feat_dim), dev)
         params = model._param_list()
-        # the backward pass re-reads the CURRENT parameter values: they must be the ones the forward used
-        if [(p.data_ptr(), p._version) for p in params] != ctx.param_versions:
-            raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
-                               "a TGN parameter changed between this call's forward and its backward")
-        sizes = [p.numel() for p in params]
-        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)       # one fill for all gradient buffers
-        grads = [g.view_as(p) for g, p in zip(flat.split(sizes), params)]
+        _glue.check_param_versions(params, ctx.param_versions, "TGN")
+        grads = _glue.zero_grads(params, dev)
         by_id = {id(p): g for p, g in zip(params, grads)}
         em, cell = model.embedding_module, model.memory_updater.memory_updater
         gstruct = _tgat_weights(model.time_encoder, em.temporal_conv_layers, em.merge_layers, model.num_layers, by_id)
@@ -174,17 +169,11 @@ def _memory_call_inputs(model, src_node_ids, dst_node_ids, node_interact_times, 
     memory_bank indexing, MemoryModel.py:336; `csr`: the sampler's graph, checked against the tables once, or None for a model without
     neighbours), the inputs as device tensors and the number of positive pairs.  -> (dev, src, dst, tms, eids, B, n_pos)"""
     dev = model.memory_bank.node_memories.device
-    if dev.type != "cuda":
-        raise _capi.DygnnError(f"dyglib_amd.{type(model).__name__} runs on an MI355X only; there is no CPU fallback")
-    if model.node_raw_features.device != dev:
-        model.node_raw_features, model.edge_raw_features = model.node_raw_features.to(dev), model.edge_raw_features.to(dev)
+    _glue.require_cuda_tables(model, dev)
     model.memory_bank._alloc()
-    if csr is not None:
-        if getattr(model, "_validated_csr", None) is not csr:          # once per sampler: graph ids inside the tables and the memory bank
-            csr.check_tables(min(model.node_raw_features.shape[0], model.num_nodes), model.edge_raw_features.shape[0])
-            model._validated_csr = csr
-        csr.check_query_ids(src_node_ids, limit=model.num_nodes)
-        csr.check_query_ids(dst_node_ids, limit=model.num_nodes)
+    if csr is not None:                                                # once per sampler: graph ids inside the tables and the memory bank
+        _glue.validate_ids(model, csr, (src_node_ids, dst_node_ids), model.num_nodes, min(model.node_raw_features.shape[0], model.num_nodes),
+                           model.edge_raw_features.shape[0])
     else:
         for ids in (src_node_ids, dst_node_ids):
             if not isinstance(ids, torch.Tensor) and len(ids):
@@ -195,12 +184,13 @@ def _memory_call_inputs(model, src_node_ids, dst_node_ids, node_interact_times, 
         e = np.asarray(edge_ids)
         if int(e.min()) < 0 or int(e.max()) >= model.edge_raw_features.shape[0]:
             raise IndexError(f"edge id out of bounds for edge_raw_features with {model.edge_raw_features.shape[0]} rows")
-    src, dst, tms = _to_dev(src_node_ids, torch.int64, dev), _to_dev(dst_node_ids, torch.int64, dev), _to_dev(node_interact_times, torch.float64, dev)
+    src, dst = _glue.to_dev(src_node_ids, torch.int64, dev), _glue.to_dev(dst_node_ids, torch.int64, dev)
+    tms = _glue.to_dev(node_interact_times, torch.float64, dev)
     B = src.numel()
     assert dst.numel() == B and tms.numel() == B
     if edges_are_positive:
         assert edge_ids is not None                                                        # MemoryModel.py:140
-    eids = _to_dev(edge_ids, torch.int64, dev) if edge_ids is not None else None
+    eids = _glue.to_dev(edge_ids, torch.int64, dev) if edge_ids is not None else None
     n_pos = (B if edges_are_positive else 0) if _n_positive is None else int(_n_positive)
     if eids is not None and eids.numel() < n_pos:
         raise AssertionError("edge_ids must cover the positive edges")
@@ -224,10 +214,7 @@ class MemoryModel(nn.Module):
 
     def set_neighbor_sampler(self, neighbor_sampler: NeighborSampler):
         """MemoryModel.py:253-263."""
-        self.embedding_module.neighbor_sampler = neighbor_sampler
-        if neighbor_sampler.sample_neighbor_strategy in ["uniform", "time_interval_aware"]:
-            assert neighbor_sampler.seed is not None
-            neighbor_sampler.reset_random_state()
+        _glue.reset_sampler(self.embedding_module, neighbor_sampler)
 
     def compute_step_embeddings(self, src_node_ids, dst_node_ids, neg_src_node_ids, neg_dst_node_ids, node_interact_times, edge_ids,
                                 num_neighbors: int = 20):
@@ -291,7 +278,7 @@ class MemoryModel(nn.Module):
             return out_src, out_dst
         cfg, w, gru = self._config_and_weights(num_neighbors)
         st = self._state()
-        ws = _workspace(self._workspace, self._lib.dygnn_tgn_workspace_bytes(C.byref(cfg), self.num_nodes, B), B, num_neighbors, dev)
+        ws = _glue.workspace(self._workspace, self._lib.dygnn_tgn_workspace_bytes(C.byref(cfg), self.num_nodes, B), B, num_neighbors, dev)
         if random_strategy:
             # MemoryModel.py:626-629 with `uniform` / `time_interval_aware`: the draws are replayed on the host in the reference's order and the
             # library runs on the pre-sampled levels (dygnn_tgn_forward_levels)
@@ -330,13 +317,8 @@ class MemoryModel(nn.Module):
         return [p for p in self.parameters() if id(p) not in bank]
 
     def _dropout_and_seed(self):
-        for p in self._param_list():
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise _capi.DygnnError("parameters must be contiguous float32")
-        seed = getattr(self, "_fixed_dropout_seed", None)             # tests pin the masks; normally torch.manual_seed governs them
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        return (float(self.dropout) if self.training else 0.0), seed
+        _glue.require_f32_params(self._param_list())
+        return (float(self.dropout) if self.training else 0.0), _glue.dropout_seed(self)
 
     # ---- random sampling strategies: the draws are replayed on the host in the reference's recursion order -------------------------------
     def _sample_levels_host(self, src: np.ndarray, dst: np.ndarray, t: np.ndarray, k: int, dev):

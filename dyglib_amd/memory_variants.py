@@ -14,9 +14,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _capi
+from . import _capi, _glue
 from .memory_model import GraphAttentionEmbedding, MemoryBank, MemoryModel, _init_memory_model, _memory_call_inputs
-from .tgat import _tgat_weights, _workspace
+from .tgat import _tgat_weights
 
 
 def compute_src_dst_node_time_shifts(src_node_ids: np.ndarray, dst_node_ids: np.ndarray, node_interact_times: np.ndarray):
@@ -113,14 +113,12 @@ class JODIE(nn.Module):
         out = torch.empty((2, B, self.node_feat_dim), dtype=torch.float32, device=dev)      # one block: the library writes it in place
         if B == 0:
             return out[0], out[1]
-        for p in self.parameters():
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise _capi.DygnnError("parameters must be contiguous float32")
+        _glue.require_f32_params(self.parameters())
         cfg = _capi.TgatConfig(self.node_feat_dim, self.edge_feat_dim, self.time_feat_dim, self.num_layers, self.num_heads, int(num_neighbors))
         nbytes = self._lib.dygnn_jodie_workspace_bytes(C.byref(cfg), self.num_nodes, B)
         if nbytes == 0:
             _capi.check(-3)                      # NotImplementedError with the library's message: it names the dimension it cannot take
-        ws = _workspace(self._workspace, nbytes, B, 0, dev)
+        ws = _glue.workspace(self._workspace, nbytes, B, 0, dev)
         cell, lin, mb = self.memory_updater.memory_updater, self.embedding_module.linear_layer, self.memory_bank
         rnn = _capi.RnnWeights(cell.weight_ih.data_ptr(), cell.weight_hh.data_ptr(), cell.bias_ih.data_ptr(), cell.bias_hh.data_ptr())
         st = _capi.TgnState(self.num_nodes, mb.node_memories.data_ptr(), mb.node_last_updated_times.data_ptr(), mb.msg.data_ptr(), mb.msg_time.data_ptr(),
@@ -169,15 +167,13 @@ class DyRep(MemoryModel):
         out = torch.empty((2, B, self.node_feat_dim), dtype=torch.float32, device=dev)      # one block: the library writes it in place
         if B == 0:
             return out[0], out[1]
-        for p in self.parameters():
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise _capi.DygnnError("parameters must be contiguous float32")
+        _glue.require_f32_params(self.parameters())
         cfg = _capi.TgatConfig(self.node_feat_dim, self.edge_feat_dim, self.time_feat_dim, self.num_layers, self.num_heads, int(num_neighbors))
         em, cell = self.embedding_module, self.memory_updater.memory_updater
         w = _tgat_weights(self.time_encoder, em.temporal_conv_layers, em.merge_layers, self.num_layers)
         rnn = _capi.RnnWeights(cell.weight_ih.data_ptr(), cell.weight_hh.data_ptr(), cell.bias_ih.data_ptr(), cell.bias_hh.data_ptr())
         st = self._state()
-        ws = _workspace(self._workspace, self._lib.dygnn_dyrep_workspace_bytes(C.byref(cfg), self.num_nodes, B), B, num_neighbors, dev)
+        ws = _glue.workspace(self._workspace, self._lib.dygnn_dyrep_workspace_bytes(C.byref(cfg), self.num_nodes, B), B, num_neighbors, dev)
         tail = (self.node_raw_features.data_ptr(), self.edge_raw_features.data_ptr(), C.byref(st), src.data_ptr(), dst.data_ptr(), tms.data_ptr(),
                 eids.data_ptr() if eids is not None else None, B, n_pos, out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), ws.numel(),
                 _capi.current_stream_ptr())

@@ -21,10 +21,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _capi
-from .modules import TimeEncoder, TransformerEncoder, fill_encoder_layer_weights      # TransformerEncoder: re-exported (it used to live here)
+from . import _capi, _glue
+from .modules import TimeEncoder, TransformerEncoder, fill_encoder_layer_weights
 from .neighbor_sampler import NeighborSampler
-from .tgat import _to_dev, _workspace
 
 
 class _TclTrainFunction(torch.autograd.Function):
@@ -53,7 +52,7 @@ class _TclTrainFunction(torch.autograd.Function):
                                                 int(seed), out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), nbytes, _capi.current_stream_ptr()))
         ctx.cfg, ctx.w, ctx.ws, ctx.dropout_p, ctx.seed = cfg, w, ws, float(dropout_p), int(seed)
         ctx.feats = (model.node_raw_features, model.edge_raw_features)        # regathered by the backward pass
-        ctx.param_versions = [(p.data_ptr(), p._version) for p in params]
+        ctx.param_versions = _glue.param_versions(params)
         return out
 
     @staticmethod
@@ -63,15 +62,10 @@ class _TclTrainFunction(torch.autograd.Function):
         if ctx.B == 0:
             return (None,) * (6 + len(params))
         dev = ctx.ws.device
-        g_src = (g_src if g_src is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
-        g_dst = (g_dst if g_dst is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
-        # the backward pass re-reads the CURRENT parameter values: they must be the ones the forward used
-        if [(p.data_ptr(), p._version) for p in params] != ctx.param_versions:
-            raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
-                               "a TCL parameter changed between this call's forward and its backward")
-        sizes = [p.numel() for p in params]
-        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)       # one fill for all gradient buffers
-        grads = [g.view_as(p) for g, p in zip(flat.split(sizes), params)]
+        g_src = _glue.grad_or_zeros(g_src, (ctx.B, model.node_feat_dim), dev)
+        g_dst = _glue.grad_or_zeros(g_dst, (ctx.B, model.node_feat_dim), dev)
+        _glue.check_param_versions(params, ctx.param_versions, "TCL")
+        grads = _glue.zero_grads(params, dev)
         gstruct = model._weights({id(p): g for p, g in zip(params, grads)})
         _capi.check(model._lib.dygnn_tcl_backward(C.byref(ctx.cfg), C.byref(ctx.w), C.byref(gstruct), g_src.data_ptr(), g_dst.data_ptr(), ctx.B,
                                                   ctx.dropout_p, ctx.seed, ctx.ws.data_ptr(), ctx.ws.numel(), _capi.current_stream_ptr()))
@@ -108,10 +102,7 @@ class TCL(nn.Module):
 
     def set_neighbor_sampler(self, neighbor_sampler: NeighborSampler):
         """models/TCL.py:179-188."""
-        self.neighbor_sampler = neighbor_sampler
-        if self.neighbor_sampler.sample_neighbor_strategy in ["uniform", "time_interval_aware"]:
-            assert self.neighbor_sampler.seed is not None
-            self.neighbor_sampler.reset_random_state()
+        _glue.reset_sampler(self, neighbor_sampler)
 
     # ---- the reference's entry point ---------------------------------------------------------------------------------------------------
     def compute_src_dst_node_temporal_embeddings(self, src_node_ids, dst_node_ids, node_interact_times, num_neighbors: int = 20,
@@ -129,10 +120,7 @@ class TCL(nn.Module):
                 raise NotImplementedError("tcl: taps are an inference facility; the training path does not return intermediates")
             if len(self.transformers) != self.num_layers or self.num_layers > _capi.DYGNN_MAX_LAYERS:
                 raise NotImplementedError(f"tcl: num_layers {self.num_layers} not supported (1..{_capi.DYGNN_MAX_LAYERS})")
-            seed = getattr(self, "_fixed_dropout_seed", None)             # tests pin the masks; normally torch.manual_seed governs them
-            if seed is None:
-                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-            return _TclTrainFunction.apply(self, sides, B, int(num_neighbors), float(self.dropout), seed, *self.parameters())
+            return _TclTrainFunction.apply(self, sides, B, int(num_neighbors), float(self.dropout), _glue.dropout_seed(self), *self.parameters())
         idx = np.arange(B, dtype=np.int32)
         out = self._forward(*sides, idx, idx + B, num_neighbors, taps)
         return out if taps is None else (out[0], out[1], out[2])
@@ -160,30 +148,22 @@ class TCL(nn.Module):
         """Refuse what is not built (autograd recording outside the training call, a CPU model), validate host ids like the reference
         (IndexError; a root id of 0 is an AssertionError: the reference returns NaN rows for it, every key being masked), and move ids (int64)
         and times (float64) to the model's device.  `trainable`: the caller has a differentiable path for train mode."""
-        if torch.is_grad_enabled() and (self.training or any(p.requires_grad for p in self.parameters())) and not (trainable and self.training):
-            raise NotImplementedError("this TCL call is inference-only on the HIP path: call it under torch.no_grad().  Gradients flow through "
-                                      "compute_src_dst_node_temporal_embeddings in train mode only (eval mode and compute_step_embeddings "
-                                      "have no backward pass)")
+        _glue.refuse_untrainable(self, trainable, "this TCL call is inference-only on the HIP path: call it under torch.no_grad().  Gradients flow "
+                                 "through compute_src_dst_node_temporal_embeddings in train mode only (eval mode and compute_step_embeddings "
+                                 "have no backward pass)")
         self.neighbor_sampler._check_strategy()
         assert num_neighbors > 0, "Number of sampled neighbors for each node should be greater than 0!"          # utils/utils.py:157
         assert num_neighbors + 1 == self.depth_embedding.weight.shape[0], \
             f"tcl: num_neighbors + 1 ({num_neighbors + 1}) must equal num_depths ({self.depth_embedding.weight.shape[0]})"      # models/TCL.py:173
         dev = self.output_layer.weight.device
-        if dev.type != "cuda":
-            raise _capi.DygnnError("dyglib_amd.TCL runs on an MI355X only; there is no CPU fallback")
-        if self.node_raw_features.device != dev:
-            self.node_raw_features = self.node_raw_features.to(dev)
-            self.edge_raw_features = self.edge_raw_features.to(dev)
-        csr = self.neighbor_sampler.csr
-        if getattr(self, "_validated_csr", None) is not csr:
-            csr.check_tables(self.node_raw_features.shape[0], self.edge_raw_features.shape[0])
-            self._validated_csr = csr
+        _glue.require_cuda_tables(self, dev)
+        n_nodes = self.node_raw_features.shape[0]
+        _glue.validate_ids(self, self.neighbor_sampler.csr, id_arrays, n_nodes, n_nodes, self.edge_raw_features.shape[0])
         for ids in id_arrays:
-            csr.check_query_ids(ids, limit=self.node_raw_features.shape[0])
             if not isinstance(ids, torch.Tensor) and np.asarray(ids).size:
                 assert int(np.asarray(ids).min()) > 0, "tcl: node id 0 is the padding node: as a root it has no valid attention key"
-        parts = [_to_dev(ids, torch.int64, dev).reshape(-1) for ids in id_arrays]
-        tms = _to_dev(node_interact_times, torch.float64, dev).reshape(-1)
+        parts = [_glue.to_dev(ids, torch.int64, dev).reshape(-1) for ids in id_arrays]
+        tms = _glue.to_dev(node_interact_times, torch.float64, dev).reshape(-1)
         assert all(p.numel() == tms.numel() for p in parts)
         return parts, tms
 
@@ -205,9 +185,7 @@ class TCL(nn.Module):
     def _weights(self, replace: Optional[dict] = None) -> "_capi.TclWeights":
         """ctypes view of the parameters; `replace` maps id(parameter) to another tensor of the same shape (the gradient buffers of the
         backward pass)."""
-        for p in self.parameters():
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise _capi.DygnnError("parameters must be contiguous float32")
+        _glue.require_f32_params(self.parameters())
         w = _capi.TclWeights()
         p = (lambda t: t.data_ptr()) if replace is None else (lambda t: replace[id(t)].data_ptr())
         w.time_w, w.time_b, w.depth_w = p(self.time_encoder.w.weight), p(self.time_encoder.w.bias), p(self.depth_embedding.weight)
@@ -230,7 +208,7 @@ class TCL(nn.Module):
         nbytes = self._lib.dygnn_tcl_workspace_bytes(C.byref(cfg), n_sides, P)
         if nbytes == 0:                                  # AssertionError (bad argument) or NotImplementedError (unsupported) with the library's message
             _capi.check(self._lib.dygnn_tcl_check(C.byref(cfg)))
-        ws = _workspace(self._workspace, nbytes, (n_sides, P), num_neighbors, dev)
+        ws = _glue.workspace(self._workspace, nbytes, (n_sides, P), num_neighbors, dev)
         d, S = self.node_feat_dim, int(num_neighbors) + 1
         out_a = torch.empty((P, d), dtype=torch.float32, device=dev)
         out_b = torch.empty((P, d), dtype=torch.float32, device=dev)

@@ -18,19 +18,12 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _capi
+from . import _capi, _glue
 from .modules import MergeLayer, TimeEncoder
 from .neighbor_sampler import NeighborSampler
 
 
 # ---- ctypes glue shared with memory_model.py (TGN runs the same library layers) ------------------------------------------------
-def _to_dev(x, dtype, dev) -> torch.Tensor:
-    """A contiguous `dtype` tensor on `dev` from a tensor or an array-like (int64 ids, float64 times)."""
-    if isinstance(x, torch.Tensor):
-        return x.to(device=dev, dtype=dtype).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(x, dtype={torch.int64: np.int64, torch.float64: np.float64}[dtype])).to(dev)
-
-
 def _tgat_weights(time_encoder, temporal_conv_layers, merge_layers, num_layers: int, replace: Optional[dict] = None) -> "_capi.TgatWeights":
     """ctypes view of the time encoder and the first `num_layers` attention / merge layers; `replace` maps id(parameter) to another tensor of
     the same shape (the gradient buffers of the backward pass)."""
@@ -62,19 +55,6 @@ def _tgat_levels(ids: dict, eid: dict, dts: dict, dev):
     return lv, keep
 
 
-def _workspace(cache: Dict[tuple, torch.Tensor], nbytes: int, batch: int, num_neighbors: int, dev) -> torch.Tensor:
-    """The model's workspace for (batch, num_neighbors, current stream) of at least `nbytes` (0: the library refused the config)."""
-    if nbytes == 0:
-        _capi.check(-1)                      # AssertionError with the library's message (e.g. num_neighbors <= 0)
-    key = (batch, int(num_neighbors), torch.cuda.current_stream(dev).cuda_stream)
-    ws = cache.get(key)
-    if ws is None or ws.numel() < nbytes or ws.device != dev:
-        if len(cache) > 8:
-            cache.clear()
-        ws = cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    return ws
-
-
 class _TgatTrainFunction(torch.autograd.Function):
     """compute_src_dst_node_temporal_embeddings with gradients: forward = dygnn_tgat_train_forward, backward = dygnn_tgat_backward.  The
     parameters are passed as inputs only so that autograd routes their gradients; the workspace belongs to this one call (a training step
@@ -100,23 +80,18 @@ class _TgatTrainFunction(torch.autograd.Function):
         ctx.model, ctx.cfg, ctx.w, ctx.ws, ctx.B, ctx.dropout_p, ctx.seed = model, cfg, w, ws, B, float(dropout_p), int(seed)
         ctx.feats = (model.node_raw_features, model.edge_raw_features)        # read again by the backward pass
         ctx.levels = levels                                                    # the level tensors outlive the asynchronous copies
-        ctx.param_versions = [(p.data_ptr(), p._version) for p in params]
+        ctx.param_versions = _glue.param_versions(params)
         return out[0], out[1]
 
     @staticmethod
     def backward(ctx, g_src, g_dst):
         model = ctx.model
         dev = ctx.ws.device
-        g_src = (g_src if g_src is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
-        g_dst = (g_dst if g_dst is not None else torch.zeros((ctx.B, model.node_feat_dim), device=dev)).contiguous().float()
+        g_src = _glue.grad_or_zeros(g_src, (ctx.B, model.node_feat_dim), dev)
+        g_dst = _glue.grad_or_zeros(g_dst, (ctx.B, model.node_feat_dim), dev)
         params = model._param_list()
-        # the backward pass re-reads the CURRENT parameter values: they must be the ones the forward used
-        if [(p.data_ptr(), p._version) for p in params] != ctx.param_versions:
-            raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
-                               "a TGAT parameter changed between this call's forward and its backward")
-        sizes = [p.numel() for p in params]
-        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)       # one fill for all gradient buffers
-        grads = [g.view_as(p) for g, p in zip(flat.split(sizes), params)]
+        _glue.check_param_versions(params, ctx.param_versions, "TGAT")
+        grads = _glue.zero_grads(params, dev)
         gstruct = _tgat_weights(model.time_encoder, model.temporal_conv_layers, model.merge_layers, model.num_layers,
                                 {id(p): g for p, g in zip(params, grads)})
         _capi.check(model._lib.dygnn_tgat_backward(C.byref(ctx.cfg), C.byref(ctx.w), C.byref(gstruct), g_src.data_ptr(), g_dst.data_ptr(), ctx.B,
@@ -168,10 +143,7 @@ class TGAT(nn.Module):
 
     def set_neighbor_sampler(self, neighbor_sampler: NeighborSampler):
         """models/TGAT.py:138-147."""
-        self.neighbor_sampler = neighbor_sampler
-        if self.neighbor_sampler.sample_neighbor_strategy in ["uniform", "time_interval_aware"]:
-            assert self.neighbor_sampler.seed is not None
-            self.neighbor_sampler.reset_random_state()
+        _glue.reset_sampler(self, neighbor_sampler)
 
     def compute_src_dst_node_temporal_embeddings(self, src_node_ids, dst_node_ids, node_interact_times,
                                                  num_neighbors: int = 20) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -185,7 +157,8 @@ class TGAT(nn.Module):
         random_strategy = self.neighbor_sampler.sample_neighbor_strategy != "recent"
         self.neighbor_sampler._check_strategy()
         dev = self._prepare(src_node_ids, dst_node_ids)
-        src, dst, tms = _to_dev(src_node_ids, torch.int64, dev), _to_dev(dst_node_ids, torch.int64, dev), _to_dev(node_interact_times, torch.float64, dev)
+        src, dst = _glue.to_dev(src_node_ids, torch.int64, dev), _glue.to_dev(dst_node_ids, torch.int64, dev)
+        tms = _glue.to_dev(node_interact_times, torch.float64, dev)
         B = src.numel()
         assert dst.numel() == B and tms.numel() == B
         if train and B > 0:
@@ -199,7 +172,7 @@ class TGAT(nn.Module):
         if B == 0:
             return out_src, out_dst
         cfg, w = self._config_and_weights(num_neighbors)
-        ws = _workspace(self._workspace, self._lib.dygnn_tgat_workspace_bytes(C.byref(cfg), B), B, num_neighbors, dev)
+        ws = _glue.workspace(self._workspace, self._lib.dygnn_tgat_workspace_bytes(C.byref(cfg), B), B, num_neighbors, dev)
         if random_strategy:
             lv, keep = self._sample_levels_host(src.cpu().numpy(), dst.cpu().numpy(), tms.cpu().numpy(), int(num_neighbors), dev)
             _capi.check(self._lib.dygnn_tgat_forward_levels(C.byref(cfg), C.byref(w), C.byref(lv), self.node_raw_features.data_ptr(),
@@ -227,8 +200,8 @@ class TGAT(nn.Module):
             raise NotImplementedError("compute_step_embeddings is inference-only: call it under torch.no_grad(), or issue the two "
                                       "compute_src_dst_node_temporal_embeddings calls of the reference for training")
         dev = self._prepare(src_node_ids, dst_node_ids, neg_dst_node_ids)
-        parts_i = [_to_dev(ids, torch.int64, dev) for ids in (src_node_ids, dst_node_ids, neg_dst_node_ids)]
-        tms = _to_dev(node_interact_times, torch.float64, dev)
+        parts_i = [_glue.to_dev(ids, torch.int64, dev) for ids in (src_node_ids, dst_node_ids, neg_dst_node_ids)]
+        tms = _glue.to_dev(node_interact_times, torch.float64, dev)
         B = parts_i[0].numel()
         assert parts_i[1].numel() == B and parts_i[2].numel() == B and tms.numel() == B
         pad = (3 * B) % 2                                   # the library takes an even number of roots: repeat the last one
@@ -239,7 +212,7 @@ class TGAT(nn.Module):
         if B == 0:
             return out[:0], out[:0], out[:0]
         cfg, w = self._config_and_weights(num_neighbors)
-        ws = _workspace(self._workspace, self._lib.dygnn_tgat_workspace_bytes(C.byref(cfg), n // 2), n // 2, num_neighbors, dev)
+        ws = _glue.workspace(self._workspace, self._lib.dygnn_tgat_workspace_bytes(C.byref(cfg), n // 2), n // 2, num_neighbors, dev)
         self._last_call = (cfg, n // 2, ws)
         _capi.check(self._lib.dygnn_tgat_forward_roots(C.byref(cfg), C.byref(w), self.neighbor_sampler.csr.on_device(dev), self.node_raw_features.data_ptr(),
                                                        self.edge_raw_features.data_ptr(), roots.data_ptr(), times.data_ptr(), n, out.data_ptr(),
@@ -251,17 +224,9 @@ class TGAT(nn.Module):
         sampler's graph (once per sampler: every id reachable through it is inside them) and the query ids against the node table
         (IndexError like the reference, models/TGAT.py:85).  Returns the device."""
         dev = self.merge_layers[0].fc1.weight.device
-        if dev.type != "cuda":
-            raise _capi.DygnnError("dyglib_amd.TGAT runs on an MI355X only; there is no CPU fallback")
-        if self.node_raw_features.device != dev:
-            self.node_raw_features = self.node_raw_features.to(dev)
-            self.edge_raw_features = self.edge_raw_features.to(dev)
-        csr = self.neighbor_sampler.csr
-        if getattr(self, "_validated_csr", None) is not csr:
-            csr.check_tables(self.node_raw_features.shape[0], self.edge_raw_features.shape[0])
-            self._validated_csr = csr
-        for ids in id_arrays:
-            csr.check_query_ids(ids, limit=self.node_raw_features.shape[0])
+        _glue.require_cuda_tables(self, dev)
+        n_nodes = self.node_raw_features.shape[0]
+        _glue.validate_ids(self, self.neighbor_sampler.csr, id_arrays, n_nodes, n_nodes, self.edge_raw_features.shape[0])
         return dev
 
     def _config_and_weights(self, num_neighbors: int):
@@ -272,13 +237,8 @@ class TGAT(nn.Module):
         return list(self.parameters())
 
     def _dropout_and_seed(self):
-        for p in self._param_list():
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise _capi.DygnnError("parameters must be contiguous float32")
-        seed = getattr(self, "_fixed_dropout_seed", None)             # tests pin the masks; normally torch.manual_seed governs them
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        return (float(self.dropout) if self.training else 0.0), seed
+        _glue.require_f32_params(self._param_list())
+        return (float(self.dropout) if self.training else 0.0), _glue.dropout_seed(self)
 
     def compute_node_temporal_embeddings(self, node_ids, node_interact_times, current_layer_num: int, num_neighbors: int = 20) -> torch.Tensor:
         """models/TGAT.py:66-136: the embedding of `node_ids` at `node_interact_times` after `current_layer_num` layers ([n, node_feat_dim]).
