@@ -19,6 +19,7 @@ DYGNN_MAX_LAYERS = 8
 ABI_VERSION = 21
 TABLE_NODE_ZERO, TABLE_EDGE_ZERO = 1, 2      # table_flags of dygnn_dygformer_forward_tables (include/dygnn.h)
 TABLE_NODE_PROJ, TABLE_EDGE_PROJ = 4, 8      # ... and of dygnn_dygformer_forward_projected: the channel's projected table is passed
+TABLE_CONST_QKV = 32                         # ... layer 0's Q/K/V products take the constant (flagged-zero) channel prefix as one rank-3 term
 PROJ_ROW_FLOATS = 64                         # floats per (table row, patch slot) of a projected table
 
 c_i32p = C.POINTER(C.c_int32)
@@ -201,6 +202,8 @@ SIGNATURES = {
                                          C.c_int32, C.c_void_p]),
     "dygnn_dygformer_pack_plan_host": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "dygnn_dygformer_pair_tokens_host": (None, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "dygnn_dygformer_qkv_tile_row_host": (C.c_int32, [C.c_int32, C.c_int32]),
+    "dygnn_dygformer_qkv0_const_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "dygnn_dygformer_workspace_bytes": (C.c_size_t, [C.POINTER(DygformerConfig), C.c_int64]),
     "dygnn_dygformer_workspace_bytes_for": (C.c_size_t, [C.POINTER(DygformerConfig), C.c_int64, C.c_int32]),
     "dygnn_dygformer_forward": (C.c_int, [C.POINTER(DygformerConfig), C.POINTER(DygformerWeights), C.c_void_p, C.POINTER(Csr),

@@ -1,5 +1,6 @@
 // C-ABI entry points for the DyGFormer forward path + the fused link-predictor head (the general GEMM's are in gemm.hip).
 #include "dygformer_layout.h"
+#include "fused3_plan.h"
 #include "gemm.h"
 
 namespace dygnn {
@@ -366,7 +367,7 @@ static int pack_impl(const dygnn_dygformer_config* cfg, const dygnn_dygformer_we
     if (!(fused_only && fused3_supported(d)))
         if (int rc = pack_generic(d, pl, w, static_cast<float*>(packed), as_stream(stream))) return rc;
     if (fused3_supported(d))
-        if (int rc = pack_fused3(d, pl, w, static_cast<float*>(packed), as_stream(stream), reuse_desc)) return rc;
+        if (int rc = pack_fused3(d, pl, w, static_cast<float*>(packed), as_stream(stream), reuse_desc, fused_only)) return rc;
     return DYGNN_OK;
 }
 
@@ -438,14 +439,17 @@ extern "C" int dygnn_dygformer_forward_projected(const dygnn_dygformer_config* c
                                                  const dygnn_dygformer_taps* taps, int32_t impl, dygnn_stream_t stream, uint32_t table_flags,
                                                  const float* node_proj, const float* edge_proj) {
     if (int rc = check_config(cfg)) return rc;
-    DYGNN_REQUIRE((table_flags & ~(uint32_t)(DYGNN_TABLE_NODE_ZERO | DYGNN_TABLE_EDGE_ZERO | DYGNN_TABLE_NODE_PROJ | DYGNN_TABLE_EDGE_PROJ)) == 0,
+    DYGNN_REQUIRE((table_flags & ~(uint32_t)(DYGNN_TABLE_NODE_ZERO | DYGNN_TABLE_EDGE_ZERO | DYGNN_TABLE_NODE_PROJ | DYGNN_TABLE_EDGE_PROJ | DYGNN_TABLE_CONST_QKV)) == 0,
                   "forward: unknown table_flags bit");
     DYGNN_REQUIRE(!(table_flags & DYGNN_TABLE_NODE_PROJ) || node_proj != nullptr, "forward: table_flags names a projected node table, node_proj is NULL");
     DYGNN_REQUIRE(!(table_flags & DYGNN_TABLE_EDGE_PROJ) || edge_proj != nullptr, "forward: table_flags names a projected edge table, edge_proj is NULL");
     DYGNN_REQUIRE(((reinterpret_cast<uintptr_t>(node_proj) | reinterpret_cast<uintptr_t>(edge_proj)) & 15) == 0, "forward: projected tables must be 16-byte aligned");
     const bool off = proj_tables_off();
+    // DYGNN_CONST_QKV = 0 / 1 overrides the caller's bit (DYGNN_PROJ_TABLES has no say in it)
+    const int cq = const_qkv_env();
+    const uint32_t const_qkv = cq < 0 ? (table_flags & DYGNN_TABLE_CONST_QKV) : cq ? DYGNN_TABLE_CONST_QKV : 0u;
     return forward_impl(cfg, w, packed, csr, node_feat, edge_feat, src, dst, times, batch, group_size, pair_stride, out_src, out_dst, workspace,
-                        workspace_bytes, taps, impl, stream, table_flags & (uint32_t)(DYGNN_TABLE_NODE_ZERO | DYGNN_TABLE_EDGE_ZERO),
+                        workspace_bytes, taps, impl, stream, (table_flags & (uint32_t)(DYGNN_TABLE_NODE_ZERO | DYGNN_TABLE_EDGE_ZERO)) | const_qkv,
                         !off && (table_flags & DYGNN_TABLE_NODE_PROJ) ? node_proj : nullptr, !off && (table_flags & DYGNN_TABLE_EDGE_PROJ) ? edge_proj : nullptr);
 }
 
@@ -456,6 +460,18 @@ extern "C" int dygnn_dygformer_forward(const dygnn_dygformer_config* cfg, const 
                                        int32_t impl, dygnn_stream_t stream) {
     return dygnn_dygformer_forward_tables(cfg, w, packed, csr, node_feat, edge_feat, src, dst, times, batch, group_size, pair_stride, out_src, out_dst,
                                           workspace, workspace_bytes, taps, impl, stream, 0);
+}
+
+// host mirrors of the constant-channel arithmetic (fused3_plan.h; tests, no GPU)
+extern "C" int32_t dygnn_dygformer_qkv_tile_row_host(int32_t tile, int32_t c) {
+    if (tile < 0 || tile >= v3::kQkvTiles || c < 0 || c >= 16) return -2;
+    return v3::qkv_tile_row(tile, c);
+}
+extern "C" int dygnn_dygformer_qkv0_const_host(const float* in_proj_weight, const float* gamma, const float* beta, const float* bias, int32_t k0, float* out) {
+    DYGNN_REQUIRE(in_proj_weight && gamma && beta && bias && out, "qkv0_const: null pointer");
+    DYGNN_REQUIRE(k0 == 48 || k0 == 96, "qkv0_const: k0 must be 48 or 96");
+    for (int i = 0; i < v3::kQkvTiles * 64; ++i) out[i] = v3::qkv0_const(in_proj_weight, gamma, beta, bias, k0, i / 64, i % 64);
+    return DYGNN_OK;
 }
 
 // Which forward kernel a call takes: 0 = G (k_merge_sigmoid, one workgroup per row), 1 = R1 (k_merge_sigmoid_rows4<1>, 4 rows per workgroup),

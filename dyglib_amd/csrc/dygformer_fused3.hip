@@ -41,6 +41,12 @@ int forward_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_
     if (table_flags & DYGNN_TABLE_EDGE_ZERO) edge_proj = nullptr;
     drop_zero_channels(a, table_flags | (node_proj ? DYGNN_TABLE_NODE_ZERO : 0u) | (edge_proj ? DYGNN_TABLE_EDGE_ZERO : 0u));
     a.pt_node = node_proj; a.pt_edge = edge_proj;
+    // DYGNN_TABLE_CONST_QKV: the rows of the encoder input that stay at the projection bias are a PREFIX of the model dimension only while the
+    // node table is flagged zero (rows 0 .. 49), and the edge table too for the longer one (rows 0 .. 99); a projected table is not constant
+    if (table_flags & DYGNN_TABLE_CONST_QKV) {
+        a.qkv0_skip = !(table_flags & DYGNN_TABLE_NODE_ZERO) ? 0 : (table_flags & DYGNN_TABLE_EDGE_ZERO) ? 6 : 3;
+        a.qkv0c = packed + pl.fused3 + f.qkv0c + (a.qkv0_skip == 6 ? kQkvTiles * 64 : 0);
+    }
     if (taps && taps->seq_lens) DYGNN_HIP(hipMemcpyAsync(taps->seq_lens, ws + wl.dims + 2 * sizeof(int32_t), 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     if (taps && taps->ev_kernel_start) DYGNN_HIP(hipEventRecord(static_cast<hipEvent_t>(taps->ev_kernel_start), s));
     a.pair_stride = (f.np == 2 && pair_stride > 0) ? pair_stride : 0;      // one pair per workgroup (128 tokens): nothing to share inside a workgroup

@@ -4,6 +4,7 @@
 
 #include "fused3_device.h"
 #include "fused3_host.h"
+#include "fused3_plan.h"
 
 namespace dygnn {
 namespace v3 {
@@ -73,6 +74,15 @@ __global__ void k_pack_vec3(const float* __restrict__ src, int n_valid, int src_
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_total) return;
     dst[dst_off + i] = i < n_valid ? src[src_off + i] : 0.f;
+}
+
+// layer 0's constant-channel operands, both prefix lengths: dst[p][tile][lane], K0 = 48 (p = 0) and 96 (p = 1); `bias` = the packed bias_x
+__global__ void k_pack_qkv0_const(const float* __restrict__ in_proj, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                  const float* __restrict__ bias, float* __restrict__ dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2 * kQkvTiles * 64) return;
+    const int p = i / (kQkvTiles * 64), r = i % (kQkvTiles * 64);
+    dst[i] = qkv0_const(in_proj, gamma, beta, bias, 48 * (p + 1), r / 64, r % 64);
 }
 
 // host mirror of WStream's position rule
@@ -270,6 +280,7 @@ PackLayout3 make_layout3(const Dims& d) {
     f.nstages_p = (int)((f.nfrag_p + kStage - 1) / kStage);
     f.stream_p = take((size_t)(f.nstages_p + 1) * kStage * kFrag);
     f.w2 = take((size_t)kW2Frags * kFrag);
+    f.qkv0c = take((size_t)2 * kQkvTiles * 64);
     f.desc = take(((size_t)(f.nfrag + f.naux + f.nproj + d.NL * (kBwdFfnFrags + f.bwa_frags) + f.nfrag_p + kW2Frags) * sizeof(FragDesc) + 3) / 4);
     // prologue LDS split: pairs per workgroup, window arrays (5 x 2 sides x Smax ints per pair), projection slab
     const int per_pair = 5 * 2 * ((d.Smax + 3) & ~3);
@@ -318,12 +329,19 @@ static int pack_vec(const float* src, int n_valid, int src_off, float* dst, int 
 
 // reuse_desc: the weights changed IN PLACE since the last full pack into this buffer (same addresses): the fragment descriptor table that
 // pack left in the buffer is still right, so only the gather kernels run — no host work, no synchronisation (one optimizer step = one repack)
-int pack(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, float* packed, hipStream_t s, bool reuse_desc) {
+int pack(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, float* packed, hipStream_t s, bool reuse_desc, bool training) {
     const PackLayout3 f = make_layout3(d);
     float* base = packed + pl.fused3;
     if (!reuse_desc) DYGNN_HIP(hipMemsetAsync(base, 0, f.total * sizeof(float), s));
     hipLaunchKernelGGL(k_pack_bias4, dim3(1), dim3(256), 0, s, w->proj_node_b, w->proj_edge_b, w->proj_time_b, w->proj_cooc_b, base + f.bias_x);
     DYGNN_LAUNCH_CHECK();
+    // inference only (a training repack leaves them stale, like the other inference sections, until the next full refresh)
+    if (!training) {
+        const dygnn_encoder_layer_weights& L0 = w->layers[0];
+        hipLaunchKernelGGL(k_pack_qkv0_const, dim3((2 * kQkvTiles * 64 + 255) / 256), dim3(256), 0, s, L0.in_proj_weight, L0.norm0_weight, L0.norm0_bias,
+                           base + f.bias_x, base + f.qkv0c);
+        DYGNN_LAUNCH_CHECK();
+    }
     if (reuse_desc) {
         // table order (as laid down by the full pack below): stream | aux | proj | NL x FFN backward | NL x attention backward | pooled stream | W2
         PackRanges r{};
@@ -401,8 +419,8 @@ int pack(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w
 
 bool fused3_supported(const Dims& d) { return v3::supported(d); }
 size_t fused3_packed_floats(const Dims& d) { return v3::packed_floats(d); }
-int pack_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, float* packed, hipStream_t s, bool reuse_desc) {
-    return v3::pack(d, pl, w, packed, s, reuse_desc);
+int pack_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, float* packed, hipStream_t s, bool reuse_desc, bool training) {
+    return v3::pack(d, pl, w, packed, s, reuse_desc, training);
 }
 
 }  // namespace dygnn

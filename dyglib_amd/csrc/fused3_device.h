@@ -21,6 +21,7 @@
 // the MFMA / LDS-DMA primitives, the weight stream and the products that more than one kernel runs.
 #pragma once
 #include "dygformer_layout.h"
+#include "fused3_plan.h"
 
 // The K = 200 products (QKV, FFN W1) spend 2 instead of 4 MFMAs on their last k-chunk (192..207: only 8 real k: mma_group2 / kpack), the
 // head-dim contractions (Q K^T, out-projection) 1 instead of 4 on theirs (96..111: only 4 real k: mma_group1 / kpack4); the packer lays the
@@ -331,18 +332,37 @@ __device__ __forceinline__ void layernorm(f4 (&xn)[kNT], const f4 (&x)[kNT], con
 
 // acc[NT] += W(NT tiles of one head's q, k or v) . xn : 13 stream steps of NT fragments [k-chunk][tile], each multiplied
 // as sub-groups of 4 and NT - 4 tiles whose fragments are read one sub-group ahead (8 fragments live instead of 14)
+// skip > 0 (layer 0 of the inference kernels with constant input channels, fused3_plan.h): the first `skip` (3 or 6) k-chunks multiply rows of
+// LN(x) that depend on the token through (mean, rstd) alone.  Their fragments are stepped over in place — the same fit / advance sequence, no
+// LDS reads, no MFMAs: the stream, the packer's padding rule and the stage barriers stay as they are — and ONE MFMA per tile adds their sum
+// at the end: A operand cst[64 u + lane] (cst wave-uniform; this lane's element of tile u: A | G | Bt | 0 by lane group), B operand ck
+// (rs | -mean rs | 1 | 0 by lane group).  The order of a row's sum is bias, chunks skip .. 12, the rank-3 term, in every instance.  The
+// operands are plain global loads issued at the group's head; hipcc waits for them (vmcnt) in front of the rank-3 MFMAs, by which time
+// several stage crossings have drained them.
+// Measured and NOT kept (profiles/const_qkv_ab.md): the operands loaded by inline asm (no wait of hipcc's in front of their use) together with
+// a counted vmcnt(N) instead of vmcnt(0) at the stage crossings of the skipped chunks (N = the loads issued since the crossing before):
+// slower than this form (-0.8 % against the parent where this form has -1.6 %).  The skip length as a template argument, with instances of their
+// own for layer 0: 28 spilled VGPRs in the eight-wave kernels.  (The scalar test per unrolled chunk of this form is not free: a call WITHOUT
+// constant channels runs 0.6 % slower than before the test was there; with them the kernel is 1.4 - 1.6 % faster.)
 template <int NT>
-__device__ __forceinline__ void qkv_group(f4 (&acc)[NT], const f4 (&xn)[kNT], const float xk0, const float xk1, WStream& ws, const float* ringl, bool active) {
+__device__ __forceinline__ void qkv_group(f4 (&acc)[NT], const f4 (&xn)[kNT], const float xk0, const float xk1, WStream& ws, const float* ringl, bool active,
+                                          const int skip = 0, const float* cst = nullptr, const int lane = 0, const float ck = 0.f) {
     constexpr int N2 = NT - 4;
     f4 fs[2][4];
+    float ca[NT];
     ws.fit(NT);
     if (active) {
+        if (skip == 0) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) fs[0][u] = lds4(ringl + (ws.pos + u) * kFrag);
+            for (int u = 0; u < 4; ++u) fs[0][u] = lds4(ringl + (ws.pos + u) * kFrag);
+        } else {
+#pragma unroll
+            for (int u = 0; u < NT; ++u) ca[u] = cst[64 * u + lane];
+        }
     }
 #pragma unroll
     for (int kc = 0; kc < kKC; ++kc) {
-        if (active) {
+        if (active && (kc >= kQkvSkipMax || kc >= skip)) {
 #pragma unroll
             for (int u = 0; u < N2; ++u) fs[1][u] = lds4(ringl + (ws.pos + 4 + u) * kFrag);
             __builtin_amdgcn_sched_barrier(0);
@@ -359,6 +379,14 @@ __device__ __forceinline__ void qkv_group(f4 (&acc)[NT], const f4 (&xn)[kNT], co
         }
         ws.advance(NT);
         if (kc + 1 < kKC) ws.fit(NT);
+        if (kc < kQkvSkipMax && active && kc + 1 == skip) {      // the first chunk that runs reads its own first sub-group (nobody read ahead for it)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) fs[0][u] = lds4(ringl + (ws.pos + u) * kFrag);
+        }
+    }
+    if (active && skip > 0) {
+#pragma unroll
+        for (int u = 0; u < NT; ++u) acc[u] = mfma(ca[u], ck, acc[u]);
     }
 }
 

@@ -46,6 +46,8 @@ struct Args {
     int nchunk[4];
     const float *pt_node, *pt_edge;   // inference only: the channel's table already projected per (row, patch slot), [rows][P][kProjRow] (dygformer_proj_tables.hip);
                                   // its chunks have left the walk like a zero table's (nchunk = 0) and the token owner adds P rows instead.  nullptr: the MFMA path
+    const float* qkv0c;           // inference only: layer 0's constant-channel operands of the prefix length in use, [38 tiles][64 lanes] (fused3_plan.h)
+    int qkv0_skip;                // ... and the k-chunks of layer 0's Q/K/V products they stand for: 0 (none), 3 or 6
     float qscale;
     train::TrainOut tr;           // training forward only (k_dygformer_fused3<.., true>): the dense activations the backward pass reads
 };
@@ -730,6 +732,15 @@ __device__ __forceinline__ void fused3_body(const Args& a) {
         auto& xo = [&]() -> f4 (&)[kNT] { if constexpr (TR) return ao; else return x; }();      // where the out-projection accumulates
         float xk0 = 0.f, xk1 = 0.f;      // LN(x) rows 192..199 as the two packed B operands of the last k-chunk
         kpack(xn[kKC - 1], xk0, xk1);
+        // layer 0 with constant input channels: the k-chunks the rank-3 term stands for and its per-token operand (qkv_group)
+        int skip0 = 0;
+        float ck0 = 0.f;
+        if constexpr (!TR) {
+            if (l == 0 && a.qkv0_skip > 0) {
+                skip0 = a.qkv0_skip;
+                ck0 = g == 0 ? ln_rstd : g == 1 ? -ln_mean * ln_rstd : g == 2 ? 1.0f : 0.f;
+            }
+        }
         TACC(T_LN);
 
 #pragma unroll 1
@@ -742,7 +753,7 @@ __device__ __forceinline__ void fused3_body(const Args& a) {
 #pragma unroll
                 for (int j = 0; j < 7; ++j) qa[j] = lds4(bq + 16 * j);
                 ws.advance(1);
-                qkv_group(qa, xn, xk0, xk1, ws, ringl, active);
+                qkv_group(qa, xn, xk0, xk1, ws, ringl, active, skip0, a.qkv0c + 64 * (19 * h), lane, ck0);
                 // Tile 6 is the COMBINED tile of the head (FragDesc kmode 8): lane group 0 holds rows 96 .. 99 of Q^T, group 1 those of K^T, group 2
                 // those of V^T (the K and V parts below run 6 tiles instead of 7: 9.5 % of the layer's QKV MFMAs).  Every wave passed a stream
                 // barrier since its last read of the previous head's K / V (the out-projection and this group lie in between): their rows
@@ -771,7 +782,7 @@ __device__ __forceinline__ void fused3_body(const Args& a) {
 #pragma unroll
                 for (int j = 0; j < 6; ++j) acc[j] = lds4(bk + 16 * j);
                 ws.advance(1);
-                qkv_group(acc, xn, xk0, xk1, ws, ringl, active);
+                qkv_group(acc, xn, xk0, xk1, ws, ringl, active, skip0, a.qkv0c + 64 * (19 * h + 7 + 6 * kv), lane, ck0);
                 if (active) {
                     float* row = (kv ? Vb : Kb) + (tokbase + 16 * tt + c) * kKV + 4 * g;
 #pragma unroll

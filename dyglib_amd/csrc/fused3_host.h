@@ -27,6 +27,7 @@ struct PackLayout3 {       // float offsets relative to PackedLayout.fused3
     size_t bwa[DYGNN_MAX_LAYERS]; int bwa_nstages; int64_t bwa_frags;      // ... and of its attention block
     size_t stream_p; int64_t nfrag_p; int nstages_p;       // ring stream of the pooled inference kernels (build_stream, pooled)
     size_t w2;                                     // ... and their last layer's W2 fragments (build_w2)
+    size_t qkv0c;                                  // layer 0's constant-channel operands (fused3_plan.h: qkv0_const): [K0 = 48 | 96][38 tiles][64 lanes]
     size_t desc;           // FragDesc table (device copy), 8-byte aligned
     size_t total;
 };
@@ -67,13 +68,20 @@ constexpr int kProjRow = 64;
 // DYGNN_PROJ_TABLES = 0: a forward call ignores the projected tables it is handed (the MFMA path; tests, A/B runs).  Read on every call.
 inline bool proj_tables_off() { const char* e = getenv("DYGNN_PROJ_TABLES"); return e && e[0] == '0' && e[1] == '\0'; }
 
+// DYGNN_CONST_QKV = 0 / 1: no / every dygnn_dygformer_forward_projected call carries DYGNN_TABLE_CONST_QKV; anything else: the caller's bit.
+// Read on every call.  Returns -1 (unset), 0 or 1.
+inline int const_qkv_env() {
+    const char* e = getenv("DYGNN_CONST_QKV");
+    return (e && (e[0] == '0' || e[0] == '1') && e[1] == '\0') ? e[0] - '0' : -1;
+}
+
 // dygformer_generic.hip
 int window_lengths_device(const Dims& d, const dygnn_csr* csr, const int64_t* src, const int64_t* dst, const double* times,
                           int64_t B, int64_t G, char* ws, const WorkspaceLayout& wl, hipStream_t s);
 // dygformer_fused3_pack.hip
 bool fused3_supported(const Dims& d);
 size_t fused3_packed_floats(const Dims& d);
-int pack_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, float* packed, hipStream_t s, bool reuse_desc);
+int pack_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, float* packed, hipStream_t s, bool reuse_desc, bool training);
 // dygformer_fused3.hip
 int forward_fused3(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, const float* packed,
                    const dygnn_csr* csr, const float* node_feat, const float* edge_feat, const int64_t* src,

@@ -1,6 +1,7 @@
 // Token compaction and pair packing of the fused DyGFormer inference kernels: the arithmetic that the kernels, the plan kernel
 // (dygformer_pack_plan.hip) and the host (tests) share.  Everything here is integer arithmetic on the window lengths of a call.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #if defined(__HIPCC__)
@@ -98,6 +99,37 @@ DYGNN_HD inline PlanSlot plan_slot(const PackPlan& p, int k, int32_t rank) {
     }
     const int i = rank - full;
     return {p.baseE + p.lo_wg[k][i], p.lo_fw[k][i]};
+}
+
+// ---- constant input channels of layer 0 (DESIGN §4.3 "Constant input channels").  A channel whose table is flagged all zero leaves its
+// rows of the encoder input at the projection bias b for every token, so the first K0 rows of LN0(x0) depend on the token through its
+// LayerNorm mean mu and reciprocal standard deviation rs alone:  LN(x0)[k] = rs . gamma_k b_k - mu rs . gamma_k + beta_k  (k < K0), and
+//     sum_{k < K0} W[n][k] LN(x0)[k] = rs A[n] + (-mu rs) G[n] + Bt[n],   A = sum W gamma b,  G = sum W gamma,  Bt = sum W beta
+// — a K = 3 product, one MFMA per output tile in place of the K0 / 16 k-chunks (K0 = 48: node table zero; 96: node and edge).
+// A layer's Q/K/V product has 38 output tiles in stream order: per head the q group's 7 (the seventh = the combined tile of rows 96 .. 99 of
+// q | k | v: FragDesc kmode 8), then 6 of k, then 6 of v.
+constexpr int kQkvTiles = 38;
+constexpr int kQkvSkipMax = 6;           // k-chunks the rank-3 term can stand for: 3 (K0 = 48) or 6 (K0 = 96)
+// in_proj row (0 .. 599: q | k | v blocks of 200, head h at 100 h) of row c (0 .. 15) of output tile `tile`; -1: the row is padding
+DYGNN_HD inline int qkv_tile_row(int tile, int c) {
+    const int h = tile / 19, t = tile % 19;
+    if (t == 6) return (c >> 2) < 3 ? 200 * (c >> 2) + 100 * h + 96 + (c & 3) : -1;
+    const int part = t < 6 ? 0 : (t - 7) / 6 + 1, j = t < 6 ? t : (t - 7) % 6;
+    return 200 * part + 100 * h + 16 * j + c;
+}
+// element `lane` (c = lane & 15: the tile's row, g = lane >> 4: the k column) of the rank-3 term's MFMA A operand of `tile`: A | G | Bt | 0 of
+// the row.  in_proj: [600][200] of layer 0; gamma, beta: norm_layers.0; bias: the projection biases in model-dim order (>= K0 floats).  Every
+// sum is one float64 chain over k ascending, rounded to fp32 once.
+DYGNN_HD inline float qkv0_const(const float* in_proj, const float* gamma, const float* beta, const float* bias, int K0, int tile, int lane) {
+    const int row = qkv_tile_row(tile, lane & 15), g = lane >> 4;
+    if (row < 0 || g == 3) return 0.f;
+    const float* wr = in_proj + (size_t)row * 200;
+    double s = 0.0;
+    for (int k = 0; k < K0; ++k) {
+        const double m = g == 0 ? (double)gamma[k] * (double)bias[k] : g == 1 ? (double)gamma[k] : (double)beta[k];
+        s += (double)wr[k] * m;
+    }
+    return (float)s;
 }
 
 }  // namespace v3

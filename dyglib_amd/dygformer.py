@@ -152,6 +152,8 @@ class DyGFormer(nn.Module):
         # projected feature tables (_projected_tables): a table whose projected form is larger than this keeps the kernel's MFMA path
         self.proj_table_max_bytes = 1 << 30
         self.__dict__["_proj"] = None
+        # constant input channels of layer 0 (_const_qkv_flag); False keeps the full product (profiles/const_qkv_ab.md has the measurements)
+        self.const_qkv = True
 
     # ---- feature tables ------------------------------------------------------------------------
     def _set_table(self, which: str, table: torch.Tensor, all_zero: Optional[bool] = None) -> None:
@@ -236,6 +238,13 @@ class DyGFormer(nn.Module):
             self.__dict__["_proj"] = cache
         return self._proj_flags(plan), cache.get("node"), cache.get("edge")
 
+    def _const_qkv_flag(self) -> int:
+        """DYGNN_TABLE_CONST_QKV for an inference call: with the node table flagged all zero (and the edge table for the longer prefix)
+        layer 0's Q/K/V products replace the k-chunks of the constant rows by one rank-3 term (include/dygnn.h).  `const_qkv =
+        False` keeps the full product.  Like the projected tables it goes with the library's own choice of kernel (impl = 0): impl = 3 names the full
+        product.  The library reads DYGNN_CONST_QKV=0|1 per call and lets it override this bit."""
+        return _capi.TABLE_CONST_QKV if self.const_qkv and int(self.impl) == 0 and self.__dict__["_node_all_zero"] else 0
+
     # ---- reference API -------------------------------------------------------------------------
     def set_neighbor_sampler(self, neighbor_sampler: NeighborSampler):
         """models/DyGFormer.py:308-317."""
@@ -287,7 +296,7 @@ class DyGFormer(nn.Module):
             self.node_raw_features.data_ptr(), self.edge_raw_features.data_ptr(),
             src.data_ptr(), dst.data_ptr(), tms.data_ptr(), B, int(_group_size), int(_pair_stride), out_src.data_ptr(), out_dst.data_ptr(),
             ws.data_ptr(), ws.numel(), C.byref(taps_struct) if taps_struct is not None else None,
-            int(self.impl), _capi.current_stream_ptr(), self.table_flags | proj_flags,
+            int(self.impl), _capi.current_stream_ptr(), self.table_flags | proj_flags | self._const_qkv_flag(),
             proj_node.data_ptr() if proj_node is not None else None, proj_edge.data_ptr() if proj_edge is not None else None)
         _capi.check(rc)
         return out_src, out_dst

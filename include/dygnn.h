@@ -186,6 +186,13 @@ size_t dygnn_dygformer_workspace_bytes_for(const dygnn_dygformer_config* cfg_hos
  * to a workgroup by the plan kernel's own arithmetic -> wg[i], first_wave[i]; returns the workgroups used, -1 on a bad tile count. */
 void dygnn_dygformer_pair_tokens_host(int32_t len_s, int32_t len_d, int32_t L, int32_t P, int32_t T_s, int32_t T_d, int32_t* out);
 int64_t dygnn_dygformer_pack_plan_host(const int32_t* tiles, int64_t n, int32_t* wg, int32_t* first_wave);
+/* ... and of layer 0's constant input channels (DYGNN_TABLE_CONST_QKV below).  qkv_tile_row: the in_proj row (0 .. 599) that row c (0 .. 15)
+ * of output tile `tile` (0 .. 37, stream order: per head 7 q tiles — the seventh combines rows 96 .. 99 of q | k | v — 6 k tiles, 6 v tiles)
+ * holds; -1: padding, -2: bad arguments.  qkv0_const: out[38][64] = the rank-3 term's MFMA A operands for the prefix k0 = 48 or 96 — lane
+ * (c = lane & 15, g = lane >> 4) of a tile holds A | G | Bt | 0 (g = 0 .. 3) of its row, float64 sums rounded once; in_proj_weight [600][200],
+ * gamma / beta = norm_layers.0 [200], bias = the node then the edge projection bias (>= k0 floats).  All host pointers. */
+int32_t dygnn_dygformer_qkv_tile_row_host(int32_t tile, int32_t c);
+int dygnn_dygformer_qkv0_const_host(const float* in_proj_weight, const float* gamma, const float* beta, const float* bias, int32_t k0, float* out);
 
 /* One launch sequence for `batch` (src,dst,t) pairs.  group_size = G splits the pairs into consecutive
  * groups of G that are padded independently (each group has its own S_src/S_dst, models/DyGFormer.py:219-226):
@@ -251,9 +258,19 @@ int dygnn_dygformer_forward_tables(const dygnn_dygformer_config* cfg_host, const
  *     A pointer whose bit is not set is ignored; a set bit with a NULL pointer is an error.  A channel flagged all zero ignores its
  *     projected table.  The flags are the caller's promise, as above: a stale projected table gives wrong results.  The environment
  *     variable DYGNN_PROJ_TABLES=0 (read on every call) makes the call ignore both, which is dygnn_dygformer_forward_tables; so do the
- *     generic path and the training entry points.  Without projected bits the call IS dygnn_dygformer_forward_tables, bit for bit. */
+ *     generic path and the training entry points.  Without projected bits the call IS dygnn_dygformer_forward_tables, bit for bit.
+ *       DYGNN_TABLE_CONST_QKV  (this entry point only; dygnn_dygformer_forward_tables rejects it)  With DYGNN_TABLE_NODE_ZERO the first 50
+ *     rows of every token's encoder input are the node projection bias, so the first 48 rows of layer 0's LayerNorm output depend on the
+ *     token through its mean and reciprocal standard deviation alone: layer 0's Q/K/V products leave out those 3 k-chunks and add
+ *     rs A + (-mean rs) G + Bt instead, one MFMA per output tile, with A, G, Bt summed once per weights version (dygnn_dygformer_pack, and
+ *     dygnn_dygformer_repack with fused_only = 0).  With DYGNN_TABLE_EDGE_ZERO as well the prefix is 96 rows = 6 k-chunks.  The rule is the
+ *     constant PREFIX: without DYGNN_TABLE_NODE_ZERO the bit changes nothing, and a projected table is not constant.  The sums are taken
+ *     in another order, so q, k, v of layer 0 differ from the call without the bit in the last bits (1e-6 of values up to 3); they do not
+ *     depend on kernel shape, batch size, group_size, pair_stride or taps.  DYGNN_CONST_QKV=0 / 1 (read on every call) clears / sets
+ *     the bit whatever the caller passed; DYGNN_PROJ_TABLES does not touch it.  The generic path ignores it. */
 #define DYGNN_TABLE_NODE_PROJ 4u
 #define DYGNN_TABLE_EDGE_PROJ 8u
+#define DYGNN_TABLE_CONST_QKV 32u      /* (16u stays an unknown bit) */
 size_t dygnn_dygformer_projected_bytes(const dygnn_dygformer_config* cfg_host, int64_t rows);
 int dygnn_dygformer_project_table(const dygnn_dygformer_config* cfg_host, const dygnn_dygformer_weights* w_host, int32_t channel,
                                   const float* table, int64_t rows, void* projected, size_t projected_bytes, dygnn_stream_t stream);
