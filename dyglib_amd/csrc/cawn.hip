@@ -24,12 +24,12 @@
 #include "common.h"
 #include "encoder_block.h"
 #include "mfma_tile.h"
-#include "tgat_attn.h"
+#include "time_encoding.h"
 
 namespace dygnn {
 namespace cawn {
 
-using attn::cos_time_t;
+using timeenc::cos_time;
 using encoder::k_encoder_post;
 using tile::f4;
 using tile::kThreads;
@@ -375,10 +375,10 @@ __global__ __launch_bounds__(kThreads) void k_cawn_lstm(LstmArgs a) {
                             else if (seg == 3) v = load_w4(s_pf[j], col, a.Pd, (a.Pd & 3) == 0);
                             else {
                                 const float dt = s_dt[j];
-                                v.x = cos_time_t(fmaf(dt, a.time_w[col], a.time_b[col]));
-                                v.y = cos_time_t(fmaf(dt, a.time_w[col + 1], a.time_b[col + 1]));
-                                v.z = cos_time_t(fmaf(dt, a.time_w[col + 2], a.time_b[col + 2]));
-                                v.w = cos_time_t(fmaf(dt, a.time_w[col + 3], a.time_b[col + 3]));
+                                v.x = cos_time(fmaf(dt, a.time_w[col], a.time_b[col]));
+                                v.y = cos_time(fmaf(dt, a.time_w[col + 1], a.time_b[col + 1]));
+                                v.z = cos_time(fmaf(dt, a.time_w[col + 2], a.time_b[col + 2]));
+                                v.w = cos_time(fmaf(dt, a.time_w[col + 3], a.time_b[col + 3]));
                             }
                         }
                         *reinterpret_cast<f4*>(A + j * lda + f) = v;

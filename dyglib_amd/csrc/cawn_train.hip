@@ -41,12 +41,12 @@
 #include "encoder_block_train.h"
 #include "gemm.h"
 #include "mfma_tile.h"
-#include "tgat_attn.h"
+#include "time_encoding.h"
 
 namespace dygnn {
 namespace cawnt {
 
-using attn::cos_time_t;
+using timeenc::cos_time;
 using tile::wave_sum;
 using train::colsum;
 
@@ -225,7 +225,7 @@ __global__ void k_cawnt_gather(const float* __restrict__ node_feat, const float*
     float v = 0.f;
     if (valid[g]) {
         if (col < Fn) v = node_feat[(size_t)nid[g] * Fn + col];
-        else if (col < Fn + Ft) v = cos_time_t(fmaf(dtv[g], tw[col - Fn], tb[col - Fn]));
+        else if (col < Fn + Ft) v = cos_time(fmaf(dtv[g], tw[col - Fn], tb[col - Fn]));
         else if (col < Fn + Ft + Fe) v = edge_feat[(size_t)eidc[g] * Fe + col - Fn - Ft];
         else {
             int64_t q;

@@ -14,6 +14,7 @@
 #include "dygformer_layout.h"
 #include "gemm.h"
 #include "dropout.h"
+#include "time_encoding.h"
 
 namespace dygnn {
 
@@ -252,29 +253,6 @@ __global__ void k_lut_fwd(const float* __restrict__ w0, const float* __restrict_
         lut[c * C + j] = acc;
     }
 }
-// sin of the time encoder's argument (up to ~3e6 rad): the range reduction of the forward's cosine (fused3_device.h cos_time) a quarter
-// turn on: x / (2 pi) as a two-float product, the fraction folded to [0, 0.25], cos(2 pi u) by an even polynomial; libm's sinf takes its slow
-// Payne-Hanek path for such arguments and is kept only beyond the product's accuracy
-__device__ __forceinline__ float sin_time(float x) {
-    if (!(fabsf(x) <= 3.0e7f)) return sinf(x);
-    const float INV_HI = 0.15915493667125702f, INV_LO = 6.4206382432985265e-09f;
-    const float p = x * INV_HI;
-    const float e = fmaf(x, INV_HI, -p);
-    const float q = fmaf(x, INV_LO, e);
-    float t = ((p - rintf(p)) + q) - 0.25f;               // sin(2 pi t') = cos(2 pi (t' - 1/4))
-    t -= rintf(t);
-    float u = fabsf(t);
-    const bool flip = u > 0.25f;
-    const float v = flip ? 0.5f - u : u;
-    const float z = v * v;
-    float r = fmaf(7.903536371318467f, z, -26.42625678337438f);
-    r = fmaf(r, z, 60.24464137187666f);
-    r = fmaf(r, z, -85.45681720669373f);
-    r = fmaf(r, z, 64.93939402266829f);
-    r = fmaf(r, z, -19.739208802178716f);
-    r = fmaf(r, z, 1.0f);
-    return flip ? -r : r;
-}
 // time-encoder gradients from dPt [M][P*Ft]: pre = w dt + b, d cos = -sin(pre).  One workgroup per pair, thread = column k = pp * Ft + f of
 // the pair's rows (coalesced), its sums over the T tokens in registers; the P columns of a feature meet in LDS, one atomic per feature.
 __global__ __launch_bounds__(256) void k_time_bwd(const float* __restrict__ dPt, const int32_t* __restrict__ ids, const float* __restrict__ dts,
@@ -293,7 +271,7 @@ __global__ __launch_bounds__(256) void k_time_bwd(const float* __restrict__ dPt,
             const int pos = (tok < Ts ? tok * P : Ss + (tok - Ts) * P) + pp;
             if (ids[b * S + pos] == 0) continue;
             const float dt = dts[b * S + pos];
-            const float gsin = -sin_time(fmaf(dt, w, bb)) * dPt[(b * T + tok) * Kt + k];
+            const float gsin = -timeenc::sin_time(fmaf(dt, w, bb)) * dPt[(b * T + tok) * Kt + k];
             gw = fmaf(gsin, dt, gw); gb += gsin;
         }
         atomicAdd(&part[f], gw);

@@ -22,6 +22,7 @@
 #pragma once
 #include "dygformer_layout.h"
 #include "fused3_plan.h"
+#include "time_encoding.h"
 
 // The K = 200 products (QKV, FFN W1) spend 2 instead of 4 MFMAs on their last k-chunk (192..207: only 8 real k: mma_group2 / kpack), the
 // head-dim contractions (Q K^T, out-projection) 1 instead of 4 on theirs (96..111: only 4 real k: mma_group1 / kpack4); the packer lays the
@@ -156,58 +157,10 @@ __device__ __forceinline__ float row_sum16_dpp(float v) {
     return v;
 }
 
-// cos for the time encoder.  The argument w*dt+b reaches 2.7e6 rad where libm's cosf takes its slow Payne-Hanek path; here x/(2 pi) is
-// formed as a two-float product (INV_HI + INV_LO = 1/(2 pi) to 2^-52), its fractional part u in [0, 0.5] is folded to [0, 0.25] and
-// cos(2 pi u) evaluated by an even degree-12 minimax polynomial (|err| <= 6e-8 on the folded range); beyond 3e7 the product's rounding
-// error would exceed 1e-7 turns and libm is called instead (tests/test_dygformer_gpu.py::test_large_timestamps_take_the_libm_cosine_path).
+// The time encoder's cosine is time_encoding.h; the fused kernels take the select form of its guard.
+using timeenc::f2;
+using timeenc::pk_fma;
 // erf for the exact GELU: Abramowitz & Stegun 7.1.26 (|err| <= 1.5e-7), branch-free.
-__device__ __forceinline__ float cos_time_fast(float x) {      // |x| <= 3e7 (branch-free; cos_time checks)
-    const float INV_HI = 0.15915493667125702f, INV_LO = 6.4206382432985265e-09f;
-    const float p = x * INV_HI;
-    const float e = fmaf(x, INV_HI, -p);
-    const float q = fmaf(x, INV_LO, e);
-    const float t = (p - rintf(p)) + q;
-    float u = fabsf(t);
-    u = u > 0.5f ? 1.0f - u : u;
-    const bool flip = u > 0.25f;
-    const float v = flip ? 0.5f - u : u;
-    const float z = v * v;
-    float r = fmaf(7.903536371318467f, z, -26.42625678337438f);
-    r = fmaf(r, z, 60.24464137187666f);
-    r = fmaf(r, z, -85.45681720669373f);
-    r = fmaf(r, z, 64.93939402266829f);
-    r = fmaf(r, z, -19.739208802178716f);
-    r = fmaf(r, z, 1.0f);
-    return flip ? -r : r;
-}
-__device__ __forceinline__ float cos_time(float x) { return fabsf(x) <= 3.0e7f ? cos_time_fast(x) : cosf(x); }
-// the same operations on two arguments at once, written on 2-vectors so that hipcc emits packed fp32 instructions (v_pk_mul / v_pk_fma /
-// v_pk_add_f32: two results in ~1.6 issue slots, tools/coissue_ubench.hip; VALU instructions take matrix-pipe time in this kernel)
-using f2 = __attribute__((ext_vector_type(2))) float;
-__device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f2 cos_time_fast2(f2 x) {
-    const f2 INV_HI = {0.15915493667125702f, 0.15915493667125702f}, INV_LO = {6.4206382432985265e-09f, 6.4206382432985265e-09f};
-    const f2 p = x * INV_HI;
-    const f2 e = pk_fma(x, INV_HI, -p);
-    const f2 q = pk_fma(x, INV_LO, e);
-    const f2 rp = {rintf(p.x), rintf(p.y)};
-    const f2 t = (p - rp) + q;
-    f2 u = {fabsf(t.x), fabsf(t.y)};
-    const f2 one_u = f2{1.0f, 1.0f} - u;
-    u = f2{u.x > 0.5f ? one_u.x : u.x, u.y > 0.5f ? one_u.y : u.y};
-    const bool fx = u.x > 0.25f, fy = u.y > 0.25f;
-    const f2 half_u = f2{0.5f, 0.5f} - u;
-    const f2 v = {fx ? half_u.x : u.x, fy ? half_u.y : u.y};
-    const f2 z = v * v;
-    auto c2 = [](float c) { return f2{c, c}; };
-    f2 r = pk_fma(c2(7.903536371318467f), z, c2(-26.42625678337438f));
-    r = pk_fma(r, z, c2(60.24464137187666f));
-    r = pk_fma(r, z, c2(-85.45681720669373f));
-    r = pk_fma(r, z, c2(64.93939402266829f));
-    r = pk_fma(r, z, c2(-19.739208802178716f));
-    r = pk_fma(r, z, c2(1.0f));
-    return f2{fx ? -r.x : r.x, fy ? -r.y : r.y};
-}
 __device__ __forceinline__ float erf_as(float x) {
     const float ax = fabsf(x);
     const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));

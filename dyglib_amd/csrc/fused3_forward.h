@@ -511,7 +511,7 @@ __device__ __forceinline__ void fused3_body(const Args& a) {
         };
         auto t_finish = [&](const bool ok, const f4 arg, f4 cs) -> f4 {      // rare: an argument beyond the fast cosine's range takes libm's
             if (!(fabsf(arg.x) <= 3.0e7f && fabsf(arg.y) <= 3.0e7f && fabsf(arg.z) <= 3.0e7f && fabsf(arg.w) <= 3.0e7f)) {
-                cs.x = cos_time(arg.x); cs.y = cos_time(arg.y); cs.z = cos_time(arg.z); cs.w = cos_time(arg.w);
+                cs.x = timeenc::cos_time_select(arg.x); cs.y = timeenc::cos_time_select(arg.y); cs.z = timeenc::cos_time_select(arg.z); cs.w = timeenc::cos_time_select(arg.w);
             }
             return ok ? cs : zero4();
         };
@@ -527,7 +527,7 @@ __device__ __forceinline__ void fused3_body(const Args& a) {
                 __builtin_amdgcn_sched_barrier(0);
                 const f2 dt2 = {tc.dt, tc.dt};
                 const f2 a01 = pk_fma(dt2, f2{w.x, w.y}, f2{bb.x, bb.y}), a23 = pk_fma(dt2, f2{w.z, w.w}, f2{bb.z, bb.w});
-                const f2 c01 = cos_time_fast2(a01), c23 = cos_time_fast2(a23);
+                const f2 c01 = timeenc::cos_fast2(a01), c23 = timeenc::cos_fast2(a23);
                 const f4 arg = {a01.x, a01.y, a23.x, a23.y}, cs = {c01.x, c01.y, c23.x, c23.y};
                 const bool okc = tc.ok;
                 t_advance(tc);                                 // the cursor arithmetic and the next position's (valid, dt) reads: same region
@@ -547,7 +547,7 @@ __device__ __forceinline__ void fused3_body(const Args& a) {
                 f4 arg;
                 arg.x = fmaf(tc.dt, w.x, bb.x); arg.y = fmaf(tc.dt, w.y, bb.y); arg.z = fmaf(tc.dt, w.z, bb.z); arg.w = fmaf(tc.dt, w.w, bb.w);
                 f4 cs;
-                cs.x = cos_time_fast(arg.x); cs.y = cos_time_fast(arg.y); cs.z = cos_time_fast(arg.z); cs.w = cos_time_fast(arg.w);
+                cs.x = timeenc::cos_fast(arg.x); cs.y = timeenc::cos_fast(arg.y); cs.z = timeenc::cos_fast(arg.z); cs.w = timeenc::cos_fast(arg.w);
                 bnx = t_finish(tc.ok, arg, cs);
                 t_advance(tc);
             }

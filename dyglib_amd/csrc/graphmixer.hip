@@ -11,12 +11,12 @@
 #include "common.h"
 #include "graphmixer.h"
 #include "mfma_tile.h"
-#include "tgat_attn.h"
+#include "time_encoding.h"
 
 namespace dygnn {
 namespace gm {
 
-using attn::cos_time_t;
+using timeenc::cos_time;
 using tile::f4;
 using tile::kThreads;
 using tile::kWaves;
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(kThreads) void k_gm_proj(Csr g, const float* __rest
         float v = 0.f;
         if (j < K) {
             if (f < C) v = edge_feat[(size_t)s_eid[j] * C + f];        // a padded slot reads edge row 0
-            else if (f < Kdim && j >= pad) v = cos_time_t(fmaf(s_dt[j], tw[f - C], tb[f - C]));      // time features of a padded slot are zero
+            else if (f < Kdim && j >= pad) v = cos_time(fmaf(s_dt[j], tw[f - C], tb[f - C]));      // time features of a padded slot are zero
         }
         smem[j * lda + f] = v;
     }

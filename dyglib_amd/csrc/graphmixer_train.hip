@@ -38,12 +38,12 @@
 #include "gemm.h"
 #include "graphmixer.h"
 #include "mfma_tile.h"
-#include "tgat_attn.h"
+#include "time_encoding.h"
 
 namespace dygnn {
 namespace gmt {
 
-using attn::cos_time_t;
+using timeenc::cos_time;
 using gm::Csr;
 using gm::gelu;
 using gm::history;
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void k_gmt_rows(Csr g, const float* __restrict
         const int j = i / W, f = i - j * W;
         float v = 0.f;
         if (f < C) v = edge_feat[(size_t)s_eid[j] * C + f];            // a padded slot reads edge row 0
-        else if (j >= pad) v = cos_time_t(fmaf(s_dt[j], tw[f - C], tb[f - C]));      // time features of a padded slot are zero
+        else if (j >= pad) v = cos_time(fmaf(s_dt[j], tw[f - C], tb[f - C]));      // time features of a padded slot are zero
         TOK[((size_t)q * K + j) * W + f] = v;
     }
 }

@@ -19,12 +19,12 @@
 #include "encoder_block.h"
 #include "mfma_tile.h"
 #include "tcl.h"
-#include "tgat_attn.h"
+#include "time_encoding.h"
 
 namespace dygnn {
 namespace tcl {
 
-using attn::cos_time_t;
+using timeenc::cos_time;
 using encoder::k_encoder_post;
 using encoder::load_rows;
 using tile::f4;
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(kThreads) void k_tcl_encode(const float* __restrict
             if (j < S && f < dim) {
                 if (part == 0) v = node_feat[(size_t)s_id[j] * Fn + f];
                 else if (part == 1) v = edge_feat[(size_t)s_eid[j] * Fe + f];
-                else v = cos_time_t(fmaf(s_dt[j], w.time_w[f], w.time_b[f]));
+                else v = cos_time(fmaf(s_dt[j], w.time_w[f], w.time_b[f]));
             }
             smem[j * lda + f] = v;
         }

@@ -36,12 +36,12 @@
 #include "gemm.h"
 #include "mfma_tile.h"
 #include "tcl.h"
-#include "tgat_attn.h"
+#include "time_encoding.h"
 
 namespace dygnn {
 namespace tclt {
 
-using attn::cos_time_t;
+using timeenc::cos_time;
 using tile::f4;
 using tile::mfma4;
 using tile::round16;
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(256) void k_tclt_enc_rows(const float* const* __res
         else if (f < Fn + Fe) EF[r * Fe + f - Fn] = edge_feat[(size_t)s_eid[j] * Fe + f - Fn];
         else {
             const int c = f - Fn - Fe;
-            TF[r * Ft + c] = cos_time_t(fmaf(s_dt[j], tw[c], tb[c]));
+            TF[r * Ft + c] = cos_time(fmaf(s_dt[j], tw[c], tb[c]));
         }
     }
 }

@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void k_tgat_qrows(const float* __restrict__ h_
     for (int f = lane; f < Ft; f += kWave) o[Fn + f] = cosf(fmaf(0.0f, tw[f], tb[f]));      // the encoding of dt = 0 (models/TGAT.py:84)
 }
 
-using attn::cos_time_t;
+using timeenc::cos_time;
 
 // C[M][N] = act(A[M][K] . W[N][K]^T + bias): fp32 MFMA, operands straight from global memory (both are K-contiguous, so
 // lane (c,g) of a 16x16x4 fragment reads the float4 at [row c][k0 + 4g]); a wave computes a 64 x 64 block (4x4 tiles).
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void k_tgat_attn_lin(const float* __restrict__
         const int f = kk - Fn - Fe;
         const float dt = nbr_dt[r];
         const f4 w = *reinterpret_cast<const f4*>(tw + f), b = *reinterpret_cast<const f4*>(tb + f);
-        return f4{cos_time_t(fmaf(dt, w.x, b.x)), cos_time_t(fmaf(dt, w.y, b.y)), cos_time_t(fmaf(dt, w.z, b.z)), cos_time_t(fmaf(dt, w.w, b.w))};
+        return f4{cos_time(fmaf(dt, w.x, b.x)), cos_time(fmaf(dt, w.y, b.y)), cos_time(fmaf(dt, w.z, b.z)), cos_time(fmaf(dt, w.w, b.w))};
     };
     auto dot4 = [](const f4 a, const f4 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w))); };
     const f4 zero = f4{0.f, 0.f, 0.f, 0.f};
@@ -217,8 +217,8 @@ __global__ __launch_bounds__(256) void k_tgat_attn_lin(const float* __restrict__
 #pragma unroll 1
                 for (int j = 0; j < k; ++j) {
                     const float dt = nbr_dt[i * k + j];
-                    *reinterpret_cast<f4*>(tf + j * Ft + f) = f4{cos_time_t(fmaf(dt, w.x, b.x)), cos_time_t(fmaf(dt, w.y, b.y)), cos_time_t(fmaf(dt, w.z, b.z)),
-                                                                cos_time_t(fmaf(dt, w.w, b.w))};
+                    *reinterpret_cast<f4*>(tf + j * Ft + f) = f4{cos_time(fmaf(dt, w.x, b.x)), cos_time(fmaf(dt, w.y, b.y)), cos_time(fmaf(dt, w.z, b.z)),
+                                                                cos_time(fmaf(dt, w.w, b.w))};
                 }
             }
         }

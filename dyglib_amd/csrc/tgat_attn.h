@@ -2,34 +2,12 @@
 // tgat_chain.hip, which runs it on its own rows and keeps z in LDS).  gfx950 only.
 #pragma once
 #include "common.h"
+#include "time_encoding.h"
 
 namespace dygnn {
 namespace attn {
 
 using af4 = __attribute__((ext_vector_type(4))) float;
-
-__device__ __attribute__((noinline)) float cos_libm(float x) { return cosf(x); }
-__device__ __forceinline__ float cos_time_t(float x) {      // same range reduction + polynomial as fused3_device.h
-    if (!(fabsf(x) <= 3.0e7f)) return cos_libm(x);
-    const float INV_HI = 0.15915493667125702f, INV_LO = 6.4206382432985265e-09f;
-    const float p = x * INV_HI;
-    const float e = fmaf(x, INV_HI, -p);
-    const float q = fmaf(x, INV_LO, e);
-    const float t = (p - rintf(p)) + q;
-    float u = fabsf(t);
-    u = u > 0.5f ? 1.0f - u : u;
-    const bool flip = u > 0.25f;
-    const float v = flip ? 0.5f - u : u;
-    const float z = v * v;
-    float r = fmaf(7.903536371318467f, z, -26.42625678337438f);
-    r = fmaf(r, z, 60.24464137187666f);
-    r = fmaf(r, z, -85.45681720669373f);
-    r = fmaf(r, z, 64.93939402266829f);
-    r = fmaf(r, z, -19.739208802178716f);
-    r = fmaf(r, z, 1.0f);
-    return flip ? -r : r;
-}
-
 
 // LDS floats the two-waves-per-node attention needs for `waves` waves (waves / 2 nodes at a time): partial scores [waves/2][2][H][KC],
 // time staging [waves][KC][TW], probabilities [waves][H][KC]
@@ -40,7 +18,7 @@ __host__ __device__ inline int pair_smem_floats(int waves, int H, int KC, int Ft
 
 // Wave `hf` (0 / 1) of node slot `slot` owns the float4 columns 2*lane + hf of the 444-wide input rows, so a lane keeps KC float4 (80 VGPRs
 // at k = 20) instead of 2*KC; the kernel is bound by gather latency, so occupancy is what pays.  Phases: (A) the pair's cosines, spread over
-// the lanes, into LDS -- BEFORE any gather is in flight, so the out-of-line libm fallback of cos_time_t has nothing live to spill; (B) all k
+// the lanes, into LDS -- BEFORE any gather is in flight, so the out-of-line libm fallback of timeenc::cos_time has nothing live to spill; (B) all k
 // gathers back to back; (C) partial scores per half -> LDS -> WORKGROUP BARRIER (every wave of the workgroup must call this function) -> both
 // waves run the same softmax on lanes (h, j); (D) weighted sum of the cached rows, stored at zrow + h * zhs (head stride): the node's z
 // [H][Dkv] in global memory or in LDS.  A dead slot (live = false: i is a stand-in) stores nothing, or zeros with zero_dead.
@@ -65,7 +43,7 @@ __device__ __forceinline__ void pair_node(const float* __restrict__ qk, const fl
         const int f = 4 * (2 * (lane >> 2) + par) + (lane & 3);
         const float w = tw[f], b = tb[f];
 #pragma unroll 1
-        for (int j = 0; j < k; ++j) tf[j * TW + lane] = cos_time_t(fmaf(nbr_dt[r0 + j], w, b));
+        for (int j = 0; j < k; ++j) tf[j * TW + lane] = timeenc::cos_time(fmaf(nbr_dt[r0 + j], w, b));
     }
     // (B) gathers
     const int col = 2 * lane + hf, kk = 4 * col;

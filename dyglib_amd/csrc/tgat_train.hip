@@ -19,7 +19,7 @@
 #include "common.h"
 #include "dropout.h"
 #include "gemm.h"
-#include "tgat_attn.h"
+#include "time_encoding.h"
 #include "tgat_levels.h"
 #include "tgat_train.h"
 #include "train_rows.h"
@@ -55,8 +55,8 @@ struct XRows {
         if (kk < Fn + Fe) return *reinterpret_cast<const f4*>(edge_feat + (size_t)eid[r] * Fe + (kk - Fn));
         const int f = kk - Fn - Fe;
         const float d = dt[r];
-        return f4{attn::cos_time_t(fmaf(d, tw[f], tb[f])), attn::cos_time_t(fmaf(d, tw[f + 1], tb[f + 1])), attn::cos_time_t(fmaf(d, tw[f + 2], tb[f + 2])),
-                  attn::cos_time_t(fmaf(d, tw[f + 3], tb[f + 3]))};
+        return f4{timeenc::cos_time(fmaf(d, tw[f], tb[f])), timeenc::cos_time(fmaf(d, tw[f + 1], tb[f + 1])), timeenc::cos_time(fmaf(d, tw[f + 2], tb[f + 2])),
+                  timeenc::cos_time(fmaf(d, tw[f + 3], tb[f + 3]))};
     }
     __device__ __forceinline__ void fetch(int64_t r, int lane, f4 (&xs)[NC]) const {
 #pragma unroll

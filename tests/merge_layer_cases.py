@@ -1,5 +1,5 @@
 """Cases, seeded inputs and the float64 reference of the link-predictor head (MergeLayer: dyglib_amd/modules.py over
-dygnn_merge_layer_sigmoid / _logits / _backward, dyglib_amd/csrc/dygformer_api.hip).  Importable without a GPU.
+dygnn_merge_layer_sigmoid / _logits / _backward, dyglib_amd/csrc/merge_layer.hip).  Importable without a GPU.
 
 The head picks one of four forward kernels by (n, dim, hidden): G = one workgroup per row, R1 = 4 rows per workgroup, R4 = 16 rows per
 workgroup (both on the 4x4x1 MFMA, 16-wide k chunks through a four-deep register ring, one wave per 16 hidden units), M = one wave per 16 rows

@@ -1,4 +1,4 @@
-"""The link-predictor head on every kernel it dispatches to (dygnn_merge_layer_sigmoid / _logits / _backward, dyglib_amd/csrc/dygformer_api.hip,
+"""The link-predictor head on every kernel it dispatches to (dygnn_merge_layer_sigmoid / _logits / _backward, dyglib_amd/csrc/merge_layer.hip,
 behind dyglib_amd.modules.MergeLayer) against the float64 reference of tests/merge_layer_cases.py.
 
 Forward: the four kernels G / R1 / R4 / M at the widths and ragged row counts of the case table, logits and probabilities within the project's
