@@ -322,6 +322,7 @@ SIGNATURES = {
     "dygnn_mm_plan": (C.c_int32, [C.POINTER(MmArgs), c_i32p, c_i32p]),
     "dygnn_mm_gathers_rows": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "dygnn_dw_grouped": (C.c_int, [C.c_int32, C.POINTER(DwPair), C.c_int32, C.c_void_p]),
+    "dygnn_timeenc_probe": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),      # test-only (time_encoding_probe.hip)
 }
 
 _lib: Optional[C.CDLL] = None

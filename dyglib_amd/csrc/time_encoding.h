@@ -4,6 +4,9 @@
 // (kInvHi + kInvLo = 1 / (2 pi) to 2^-52), its fractional part u in [0, 0.5] is folded to [0, 0.25] and cos(2 pi u) evaluated by an even
 // degree-12 minimax polynomial (|err| <= 6e-8 on the folded range); beyond 3e7 the product's rounding error would exceed 1e-7 turns and
 // libm is called instead (tests/test_dygformer_gpu.py::test_large_timestamps_take_the_libm_cosine_path).
+// Every form below is exported alone by time_encoding_probe.hip and held to these figures by tests/test_time_encoding_gpu.py (|err| <= 7.5e-7
+// = 2 pi 1e-7 + 6e-8 + 2^-24 against float64; observed 3.6e-7 for cos, 5.0e-7 for sin, whose quarter-turn shift rounds once more); every
+// backbone runs with arguments in (2.7e6, 3e7] and beyond 3e7 in tests/test_large_timestamps_gpu.py.
 //
 // There are TWO guarded cosines on purpose, same values, different code around the rare libm call:
 //   * cos_time: an early return into the out-of-line cos_libm.  libm's slow path needs scratch; kept behind a call it costs the caller

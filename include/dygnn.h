@@ -935,6 +935,12 @@ typedef struct dygnn_dw_pair {
 
 int dygnn_dw_grouped(int32_t K, const dygnn_dw_pair* pairs, int32_t npairs, dygnn_stream_t stream);
 
+/* Test-only: the cosine forms of the time encoder (csrc/time_encoding.h) on n device floats, one thread per element: out[i] = f(x[i]).
+ * form: 0 cos_fast, 1 cos_fast2 on the consecutive pairs (x[2j], x[2j + 1]) (an odd n's last element is paired with 0), 2 cos_time,
+ * 3 cos_time_select, 4 sin_fast, 5 sin_time.  Forms 0, 1 and 4 are unguarded: their result is unspecified for |x| > 3e7.
+ * Another form, negative n or n > 2^31, a NULL array with n > 0: DYGNN_E_INVALID.  No backbone calls it. */
+int dygnn_timeenc_probe(int32_t form, const float* x, int64_t n, float* out, dygnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
