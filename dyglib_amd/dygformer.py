@@ -235,8 +235,28 @@ class DyGFormer(nn.Module):
                 _capi.check(self._lib.dygnn_dygformer_project_table(C.byref(self._cfg), C.byref(weights), ch, table.data_ptr(), int(table.shape[0]),
                                                                     buf.data_ptr(), buf.numel(), _capi.current_stream_ptr()))
                 cache[which] = buf
+            cache["built"] = self._built_mark(dev)      # the build is launches only: a call on another stream must not read the tables before it ran
             self.__dict__["_proj"] = cache
+        self._order_after(cache["built"], dev)
         return self._proj_flags(plan), cache.get("node"), cache.get("edge")
+
+    # ---- caches shared between streams ---------------------------------------------------------
+    @staticmethod
+    def _built_mark(dev):
+        """(stream, event recorded on it now): what a cache keeps of the stream that has just queued its build.  The caches (kernel-ready
+        weights, projected tables) belong to the model, not to a stream, so ordering their build before their readers is the library's job."""
+        stream = torch.cuda.current_stream(dev)
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        return stream.cuda_stream, ev
+
+    @staticmethod
+    def _order_after(mark, dev) -> None:
+        """Make the current stream wait for a cache's build when another stream queued it (hipStreamWaitEvent: nothing blocks the host)."""
+        if mark is not None:
+            stream = torch.cuda.current_stream(dev)
+            if stream.cuda_stream != mark[0]:
+                stream.wait_event(mark[1])
 
     def _const_qkv_flag(self) -> int:
         """DYGNN_TABLE_CONST_QKV for an inference call: with the node table flagged all zero (and the edge table for the longer prefix)
@@ -499,6 +519,7 @@ class DyGFormer(nn.Module):
             _capi.check(self._lib.dygnn_dygformer_repack(C.byref(self._cfg), C.byref(self._weights_cached), self._packed.data_ptr(), self._packed.numel(), 0,
                                                          _capi.current_stream_ptr()))
             self.__dict__["_packed_complete"] = True
+            self.__dict__["_packed_built"] = self._built_mark(dev)
         if self._packed is None or self._packed_key != key:
             _glue.require_f32_params(plist)
             weights = self._weights_cached = self._weights_struct()
@@ -523,6 +544,12 @@ class DyGFormer(nn.Module):
             self.__dict__["_packed_ptrs"] = ptrs
             self._packed_key = key
             self.__dict__["_pack_gen"] = self.__dict__.get("_pack_gen", 0) + 1      # the projected tables of the previous weights are stale
+            # a repack is launches only, so a call on another stream has to wait for it.  The full pack of a shape the fused kernel takes
+            # ends in a synchronisation of its stream (its descriptor tables are copied from host vectors): every launch after it, on any
+            # stream, finds the buffer written and the event below complete, so waiting for it costs nothing; a shape that only the generic
+            # path takes packs with launches alone and needs the event like a repack.  One mark serves both.
+            self.__dict__["_packed_built"] = self._built_mark(dev)
+        self._order_after(self.__dict__.get("_packed_built"), dev)
         return self._weights_cached, self._packed
 
     def _workspace_for(self, B: int, dev) -> torch.Tensor:

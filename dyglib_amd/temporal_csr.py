@@ -109,7 +109,10 @@ class TemporalCSR:
 
     # ---- device residency ---------------------------------------------------------------------
     def on_device(self, device) -> "_capi.Csr":
-        """ctypes view of the CSR resident on `device` (uploaded on first use, then cached)."""
+        """ctypes view of the CSR resident on `device` (uploaded on first use, then cached).  The upload is a blocking `.to()` from pageable
+        host memory: it returns only after the copies have completed, so every launch issued afterwards, on whichever stream, finds the arrays
+        written.  The cache therefore needs no event of its own (unlike DyGFormer's kernel-ready weights and projected tables, which are built
+        by launches alone)."""
         device = torch.device(device)
         key = str(device)
         if key not in self._dev:
