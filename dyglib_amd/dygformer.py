@@ -24,6 +24,7 @@ import torch.nn as nn
 from torch.nn import MultiheadAttention
 
 from . import _capi, _glue
+from ._dygformer_caches import PackedWeights, ProjectedTables
 from .modules import TimeEncoder
 from .neighbor_sampler import NeighborSampler
 
@@ -108,6 +109,9 @@ class DyGFormer(nn.Module):
                  time_feat_dim: int, channel_embedding_dim: int, patch_size: int = 1, num_layers: int = 2, num_heads: int = 2,
                  dropout: float = 0.1, max_input_sequence_length: int = 512, device: str = "cpu"):
         super().__init__()
+        self._weights = PackedWeights()         # the kernel-ready weight copy and the projected feature tables (_dygformer_caches.py)
+        self._tables = ProjectedTables()
+        self._params = None                     # _param_list()
         # plain attributes, not buffers: they are not part of the state_dict (models/DyGFormer.py:32-33).  Whether a table is all zero
         # (the reference's preprocessing writes zero node features for every dataset) is established here, on the host arrays, once: the
         # fused kernel then leaves that channel out of the patch projection (table_flags of dygnn_dygformer_forward_tables)
@@ -145,13 +149,10 @@ class DyGFormer(nn.Module):
         self._lib = _capi.load()           # fails loudly when the HIP library is missing
         self._cfg = _capi.DygformerConfig(self.node_feat_dim, self.edge_feat_dim, self.time_feat_dim, self.channel_embedding_dim,
                                           self.patch_size, self.num_layers, self.num_heads, self.max_input_sequence_length)
-        self._packed: Optional[torch.Tensor] = None
-        self._packed_key = None
         self._workspace: Dict[tuple, torch.Tensor] = {}
         self.impl = 0                      # 0 auto, 1 generic, 3 fused (see include/dygnn.h)
-        # projected feature tables (_projected_tables): a table whose projected form is larger than this keeps the kernel's MFMA path
+        # projected feature tables (_proj_plan): a table whose projected form is larger than this keeps the kernel's MFMA path
         self.proj_table_max_bytes = 1 << 30
-        self.__dict__["_proj"] = None
         # constant input channels of layer 0 (_const_qkv_flag); False keeps the full product (profiles/const_qkv_ab.md has the measurements)
         self.const_qkv = True
 
@@ -160,7 +161,7 @@ class DyGFormer(nn.Module):
         """Store a feature table with its "all zero" bit; all_zero=None looks at the tensor (one reduction, a host sync on a GPU)."""
         self.__dict__["_" + which + "_raw_features"] = table
         self.__dict__["_" + which + "_all_zero"] = bool(not table.any().item()) if all_zero is None else bool(all_zero)
-        self.__dict__["_proj"] = None       # the projected tables were built from the table this one replaces
+        self._tables.drop()                 # the projected tables were built from the table this one replaces
 
     @property
     def node_raw_features(self) -> torch.Tensor:
@@ -211,53 +212,6 @@ class DyGFormer(nn.Module):
     def _proj_flags(self, plan: Dict[str, int]) -> int:
         return (_capi.TABLE_NODE_PROJ if "node" in plan else 0) | (_capi.TABLE_EDGE_PROJ if "edge" in plan else 0)
 
-    def _projected_tables(self, dev, weights) -> Tuple[int, Optional[torch.Tensor], Optional[torch.Tensor]]:
-        """(projected bits of table_flags, projected node table, projected edge table) for an inference call.  Built lazily on the first
-        inference call after a (re)pack of the weights — they live exactly as long as that kernel-ready copy — and dropped with it and
-        whenever a table is assigned."""
-        plan = self._proj_plan()
-        if not plan:
-            return 0, None, None
-        key = (self.__dict__.get("_pack_gen", 0), str(dev), tuple(sorted(plan.items())))
-        cache = self.__dict__["_proj"]
-        if cache is None or cache["key"] != key:
-            old = cache or {}
-            cache = {"key": key}
-            for ch, which in enumerate(("node", "edge")):
-                if which not in plan:
-                    continue
-                table = self.__dict__["_" + which + "_raw_features"]
-                if table.dtype != torch.float32 or not table.is_contiguous():
-                    raise _capi.DygnnError("feature tables must be contiguous float32")
-                buf = old.get(which)
-                if buf is None or buf.numel() != plan[which] or buf.device != dev:
-                    buf = torch.empty(plan[which], dtype=torch.uint8, device=dev)
-                _capi.check(self._lib.dygnn_dygformer_project_table(C.byref(self._cfg), C.byref(weights), ch, table.data_ptr(), int(table.shape[0]),
-                                                                    buf.data_ptr(), buf.numel(), _capi.current_stream_ptr()))
-                cache[which] = buf
-            cache["built"] = self._built_mark(dev)      # the build is launches only: a call on another stream must not read the tables before it ran
-            self.__dict__["_proj"] = cache
-        self._order_after(cache["built"], dev)
-        return self._proj_flags(plan), cache.get("node"), cache.get("edge")
-
-    # ---- caches shared between streams ---------------------------------------------------------
-    @staticmethod
-    def _built_mark(dev):
-        """(stream, event recorded on it now): what a cache keeps of the stream that has just queued its build.  The caches (kernel-ready
-        weights, projected tables) belong to the model, not to a stream, so ordering their build before their readers is the library's job."""
-        stream = torch.cuda.current_stream(dev)
-        ev = torch.cuda.Event()
-        ev.record(stream)
-        return stream.cuda_stream, ev
-
-    @staticmethod
-    def _order_after(mark, dev) -> None:
-        """Make the current stream wait for a cache's build when another stream queued it (hipStreamWaitEvent: nothing blocks the host)."""
-        if mark is not None:
-            stream = torch.cuda.current_stream(dev)
-            if stream.cuda_stream != mark[0]:
-                stream.wait_event(mark[1])
-
     def _const_qkv_flag(self) -> int:
         """DYGNN_TABLE_CONST_QKV for an inference call: with the node table flagged all zero (and the edge table for the longer prefix)
         layer 0's Q/K/V products replace the k-chunks of the constant rows by one rank-3 term (include/dygnn.h).  `const_qkv =
@@ -293,7 +247,7 @@ class DyGFormer(nn.Module):
                               "for backward); wrap evaluation in torch.no_grad() for the fused inference kernel", RuntimeWarning, stacklevel=2)
                 self._warned_eval_grad = True
             p_drop, seed = self._dropout_and_seed()
-            seq_lens = self._seq_lens_side_stream(src_node_ids, dst_node_ids, node_interact_times, src, dst, tms, dev)
+            seq_lens = self._seq_lens_groups(src_node_ids, dst_node_ids, node_interact_times, src[None], dst[None], tms[None], dev)[0]
             return _TrainFunction.apply(self, src, dst, tms, p_drop, seed, seq_lens, *self._param_list())
         out_src = torch.empty((B, self.node_feat_dim), dtype=torch.float32, device=dev)
         out_dst = torch.empty_like(out_src)
@@ -310,7 +264,7 @@ class DyGFormer(nn.Module):
             taps_struct = _capi.DygformerTaps()
             taps_struct.ev_kernel_start, taps_struct.ev_kernel_stop = e0.cuda_event, e1.cuda_event
         csr = self.neighbor_sampler.csr.on_device(dev)
-        proj_flags, proj_node, proj_edge = self._projected_tables(dev, weights)
+        proj_flags, proj_node, proj_edge = self._tables.get(self, dev, weights, self._weights.generation)
         rc = self._lib.dygnn_dygformer_forward_projected(
             C.byref(self._cfg), C.byref(weights), packed.data_ptr(), csr,
             self.node_raw_features.data_ptr(), self.edge_raw_features.data_ptr(),
@@ -362,71 +316,37 @@ class DyGFormer(nn.Module):
         return (float(self.dropout) if self.training else 0.0), _glue.dropout_seed(self)
 
     def _seq_lens_groups(self, src_in, dst_in, t_in, src: torch.Tensor, dst: torch.Tensor, tms: torch.Tensor, dev):
-        """(S_src, S_dst) of each of the N calls in [N, B] inputs, on the side stream (one synchronisation of IT, not of the main stream:
-        the host keeps queueing this step while the GPU still works on the previous one).  Host inputs are uploaded a second time on the
-        side stream; device inputs make the side stream wait for the main stream's copy of them."""
+        """(S_src, S_dst) of each of the N calls in [N, B] device inputs (one call: [1, B] views), on the side stream: one synchronisation
+        of IT, not of the main stream, so the host keeps queueing this step while the GPU still works on the previous one.  Host inputs
+        (`*_in`, N * B elements each) are uploaded a second time on the side stream, ids in one copy and times in another; device inputs
+        make the side stream wait for the main stream's copy of them."""
         side = getattr(self, "_side", None)
         if side is None or side.device != dev:
             side = self._side = torch.cuda.Stream(dev)
         L, P = self.max_input_sequence_length, self.patch_size
         N, B = src.shape
         host = not any(isinstance(x, torch.Tensor) for x in (src_in, dst_in, t_in))
-        ev = None
-        if not host:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
+        ev = None if host else torch.cuda.current_stream(dev).record_event()
         with torch.cuda.stream(side):
             if host:
-                src = torch.from_numpy(np.ascontiguousarray(src_in, dtype=np.int64)).to(dev)
-                dst = torch.from_numpy(np.ascontiguousarray(dst_in, dtype=np.int64)).to(dev)
-                tms = torch.from_numpy(np.ascontiguousarray(t_in, dtype=np.float64)).to(dev)
+                ids = np.stack([np.asarray(src_in, dtype=np.int64).reshape(N, B), np.asarray(dst_in, dtype=np.int64).reshape(N, B)])
+                sides = torch.from_numpy(ids).to(dev)
+                times = torch.from_numpy(np.ascontiguousarray(t_in, dtype=np.float64).reshape(N, B)).to(dev)
             else:
                 side.wait_event(ev)
+                sides, times = (src, dst), tms
             hist = torch.empty(B, dtype=torch.int32, device=dev)
             end = torch.empty(B, dtype=torch.int64, device=dev)
             maxw = torch.zeros(N, 2, dtype=torch.int32, device=dev)
             csr = self.neighbor_sampler.csr.on_device(dev)
             for i in range(N):
-                for half, nodes in enumerate((src[i], dst[i])):
-                    _capi.check(self._lib.dygnn_window_lengths(csr, nodes.data_ptr(), tms[i].data_ptr(), B, L, hist.data_ptr(), end.data_ptr(),
-                                                               maxw[i, half:half + 1].data_ptr(), side.cuda_stream))
+                for half in (0, 1):
+                    _capi.check(self._lib.dygnn_window_lengths(csr, sides[half][i].data_ptr(), times[i].data_ptr(), B, L, hist.data_ptr(),
+                                                               end.data_ptr(), maxw[i, half:half + 1].data_ptr(), side.cuda_stream))
             m = maxw.cpu()                               # synchronises the side stream only
         if not host:
             src.record_stream(side); dst.record_stream(side); tms.record_stream(side)
         return [tuple((int(v) + 1) + (P - (int(v) + 1) % P) % P for v in row) for row in m.tolist()]
-
-    def _seq_lens_side_stream(self, src_in, dst_in, t_in, src, dst, tms, dev):
-        """(S_src, S_dst) of this call, computed on a side stream so that the training forward does not have to synchronise the main
-        stream (which would serialise the host's launch work with everything still queued on the GPU).  Host inputs are uploaded a
-        second time on the side stream; device inputs make the side stream wait for the main stream's copy of them."""
-        side = getattr(self, "_side", None)
-        if side is None or side.device != dev:
-            side = self._side = torch.cuda.Stream(dev)
-        L, P = self.max_input_sequence_length, self.patch_size
-        B = src.numel()
-        host = not any(isinstance(x, torch.Tensor) for x in (src_in, dst_in, t_in))
-        ev = None
-        if not host:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            if host:
-                nodes = torch.from_numpy(np.concatenate([np.asarray(src_in, dtype=np.int64), np.asarray(dst_in, dtype=np.int64)])).to(dev)
-                times = torch.from_numpy(np.concatenate([np.asarray(t_in, dtype=np.float64)] * 2)).to(dev)
-            else:
-                side.wait_event(ev)
-                nodes, times = torch.cat([src, dst]), torch.cat([tms, tms])
-            hist = torch.empty(2 * B, dtype=torch.int32, device=dev)
-            end = torch.empty(2 * B, dtype=torch.int64, device=dev)
-            maxw = torch.zeros(2, dtype=torch.int32, device=dev)
-            csr = self.neighbor_sampler.csr.on_device(dev)
-            for half in (0, 1):
-                sl = slice(half * B, (half + 1) * B)
-                _capi.check(self._lib.dygnn_window_lengths(csr, nodes[sl].data_ptr(), times[sl].data_ptr(), B, L, hist[sl].data_ptr(),
-                                                           end[sl].data_ptr(), maxw[half:half + 1].data_ptr(), side.cuda_stream))
-            m = maxw.cpu()                               # synchronises the side stream only
-        S = [int(v) + 1 for v in m.tolist()]
-        return tuple(s_ + (P - s_ % P) % P for s_ in S)
 
     # ---- plumbing ------------------------------------------------------------------------------
     def _validate_ids(self, *id_arrays) -> None:
@@ -440,19 +360,19 @@ class DyGFormer(nn.Module):
         (optimizer steps, load_state_dict, .to()), on every train()/eval() switch and by this call; writes through `p.data` do not
         bump the version counter, so code that edits weights that way (custom init, EMA) calls this afterwards.  The projected feature
         tables go with it."""
-        self._packed_key = None
-        self.__dict__["_proj"] = None
+        self._weights.drop()
+        self._tables.drop()
 
     def train(self, mode: bool = True):
-        self._packed_key = None
+        self._weights.drop()
         return super().train(mode)
 
     def _apply(self, fn, *args, **kwargs):
-        self._packed_key = None
+        self._weights.drop()
         return super()._apply(fn, *args, **kwargs)
 
     def load_state_dict(self, *args, **kwargs):
-        self._packed_key = None
+        self._weights.drop()
         return super().load_state_dict(*args, **kwargs)
 
     def _device(self) -> torch.device:
@@ -469,20 +389,12 @@ class DyGFormer(nn.Module):
     def _to_dev(x, dtype, dev) -> torch.Tensor:
         return _glue.to_dev(x, dtype, dev, non_blocking=True)
 
-    def _weights_struct(self, replace: Optional[dict] = None) -> "_capi.DygformerWeights":
-        """ctypes view of the parameters; `replace` maps parameter names to other tensors of the same shapes (the gradient
+    def _weights_struct(self, replace: Optional[list] = None) -> "_capi.DygformerWeights":
+        """ctypes view of the parameters, or of `replace`: other tensors of the same shapes in the order of _param_list() (the gradient
         buffers of the backward pass)."""
         w = _capi.DygformerWeights()
-        if replace is None:
-            p = lambda t: t.data_ptr()
-        elif isinstance(replace, dict):
-            by_id = {id(t): replace[n] for n, t in self.named_parameters()}
-            p = lambda t: by_id[id(t)].data_ptr()
-        else:                           # a list aligned with self._param_list() (the backward pass: no module traversal per step)
-            index = self.__dict__.get("_pindex")
-            if index is None:
-                index = self.__dict__["_pindex"] = {id(t): i for i, t in enumerate(self._param_list())}
-            p = lambda t: replace[index[id(t)]].data_ptr()
+        tensors = self._param_list() if replace is None else replace          # no module traversal per step
+        p = lambda t: tensors[self._param_slot[id(t)]].data_ptr()
         enc = self.neighbor_co_occurrence_encoder.neighbor_co_occurrence_encode_layer
         w.time_w, w.time_b = p(self.time_encoder.w.weight), p(self.time_encoder.w.bias)
         w.cooc_w0, w.cooc_b0, w.cooc_w1, w.cooc_b1 = p(enc[0].weight), p(enc[0].bias), p(enc[2].weight), p(enc[2].bias)
@@ -504,53 +416,14 @@ class DyGFormer(nn.Module):
         return w
 
     def _param_list(self):
-        plist = self.__dict__.get("_plist")
-        if plist is None:
-            plist = self.__dict__["_plist"] = list(self.parameters())          # parameters are never added after construction
-        return plist
+        if self._params is None:            # parameters are never added after construction
+            self._params = list(self.parameters())
+            self._param_slot = {id(t): i for i, t in enumerate(self._params)}
+        return self._params
 
     def _packed_weights(self, dev, training: bool = False):
-        """(ctypes view of the parameters, kernel-ready weight copy); both rebuilt whenever any parameter was written (optimizer
-        step, load_state_dict) — detected through the tensors' version counters and addresses."""
-        plist = self._param_list()
-        key = tuple([(p.data_ptr(), p._version) for p in plist]) + (str(dev),)
-        if self._packed is not None and self._packed_key == key and not training and not self.__dict__.get("_packed_complete", True):
-            # the training path refreshed the fragment streams only: bring the inference sections up to date too
-            _capi.check(self._lib.dygnn_dygformer_repack(C.byref(self._cfg), C.byref(self._weights_cached), self._packed.data_ptr(), self._packed.numel(), 0,
-                                                         _capi.current_stream_ptr()))
-            self.__dict__["_packed_complete"] = True
-            self.__dict__["_packed_built"] = self._built_mark(dev)
-        if self._packed is None or self._packed_key != key:
-            _glue.require_f32_params(plist)
-            weights = self._weights_cached = self._weights_struct()
-            nbytes = self._lib.dygnn_dygformer_packed_bytes(C.byref(self._cfg))
-            if nbytes == 0:
-                _capi.check(-1)
-            fresh = self._packed is None or self._packed.numel() != nbytes or self._packed.device != dev
-            if fresh:
-                self._packed = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-            ptrs = tuple(k[0] for k in key[:-1]) + (self._packed.data_ptr(),)
-            # an optimizer step changes the values, not the addresses: the fragment descriptors already in the buffer stay valid and the
-            # refresh is kernel launches only (no host synchronisation inside the training loop)
-            repack = not fresh and self.__dict__.get("_packed_ptrs") == ptrs
-            self.__dict__["_packed_ptrs"] = None
-            if repack:
-                _capi.check(self._lib.dygnn_dygformer_repack(C.byref(self._cfg), C.byref(weights), self._packed.data_ptr(), nbytes, 1 if training else 0,
-                                                             _capi.current_stream_ptr()))
-                self.__dict__["_packed_complete"] = not training
-            else:
-                _capi.check(self._lib.dygnn_dygformer_pack(C.byref(self._cfg), C.byref(weights), self._packed.data_ptr(), nbytes, _capi.current_stream_ptr()))
-                self.__dict__["_packed_complete"] = True
-            self.__dict__["_packed_ptrs"] = ptrs
-            self._packed_key = key
-            self.__dict__["_pack_gen"] = self.__dict__.get("_pack_gen", 0) + 1      # the projected tables of the previous weights are stale
-            # a repack is launches only, so a call on another stream has to wait for it.  The full pack of a shape the fused kernel takes
-            # ends in a synchronisation of its stream (its descriptor tables are copied from host vectors): every launch after it, on any
-            # stream, finds the buffer written and the event below complete, so waiting for it costs nothing; a shape that only the generic
-            # path takes packs with launches alone and needs the event like a repack.  One mark serves both.
-            self.__dict__["_packed_built"] = self._built_mark(dev)
-        self._order_after(self.__dict__.get("_packed_built"), dev)
-        return self._weights_cached, self._packed
+        """(ctypes view of the parameters, kernel-ready weight copy), current for this call and ordered before it on its stream."""
+        return self._weights.get(self, dev, training)
 
     def _workspace_for(self, B: int, dev) -> torch.Tensor:
         # one workspace per (batch size, stream): calls issued on different HIP streams may overlap

@@ -106,9 +106,11 @@ def test_which_channel_gets_a_table_and_the_bits_that_say_so(model, monkeypatch)
 
 
 def test_assigning_a_table_or_invalidating_the_weights_drops_the_projected_tables(model):
-    model.__dict__["_proj"] = {"key": None}
+    held = {"node": torch.empty(0), "edge": torch.empty(0)}
+    model._tables.buffers = dict(held)
+    assert model._tables.built == {"node", "edge"}
     model.edge_raw_features = model.edge_raw_features
-    assert model.__dict__["_proj"] is None
-    model.__dict__["_proj"] = {"key": None}
+    assert model._tables.built == set()
+    model._tables.buffers = dict(held)
     model.invalidate_packed()
-    assert model.__dict__["_proj"] is None
+    assert model._tables.built == set()

@@ -34,8 +34,7 @@ def _call(model, *args, **kw):
 
 def _uses_tables(model, want):
     """the projected tables this model's last inference call was given"""
-    cache = model.__dict__["_proj"]
-    assert ({k for k in ("node", "edge") if cache and k in cache} == set(want)), (cache or {}).keys()
+    assert model._tables.built == set(want), model._tables.built
 
 
 @pytest.fixture(autouse=True)

@@ -238,7 +238,7 @@ def test_projected_tables_built_on_one_stream_are_ready_on_another(pair, tables)
         f.infer(0)                                   # the full pack (it synchronises its stream); no tables yet
         tables.setenv("DYGNN_PROJ_TABLES", "1")
         torch.cuda.synchronize()
-        assert f.model.__dict__["_proj"] is None
+        assert f.model._tables.built == set()
         return f
     twin = prepared(9101)                            # the same sequence once without a hold, on a twin: its host time sizes the hold
     a, b = pair
@@ -252,7 +252,7 @@ def test_projected_tables_built_on_one_stream_are_ready_on_another(pair, tables)
     torch.cuda.synchronize()
     f = prepared(9102)
     out_a, out_b = _hand_off(pair, "c1 projected tables", enqueue_ms, lambda: f.infer(0), lambda: f.infer(1))
-    assert {k for k in ("node", "edge") if k in f.model.__dict__["_proj"]} == {"node", "edge"}
+    assert f.model._tables.built == {"node", "edge"}
     f.check(out_b, 1, "c1: call on B while the tables' build was held on A")
     f.check(out_a, 0, "c1: the building call on A")
 
