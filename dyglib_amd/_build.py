@@ -22,7 +22,7 @@ LIB_PATH = os.path.join(CSRC, LIB_NAME)
 SOURCES = ["csr_host.cpp", "sampler.hip", "cooccurrence.hip", "dygformer_generic.hip", "dygformer_fused3.hip", "dygformer_fused3_train.hip",
            "dygformer_fused3_bwd.hip", "dygformer_fused3_pack.hip", "dygformer_pack_plan.hip", "dygformer_pooled_tail.hip", "dygformer_proj_tables.hip", "dygformer_train.hip",
            "dygformer_api.hip", "merge_layer.hip", "gemm.hip", "tgat.hip", "tgat_chain.hip", "tgat_train.hip", "tgn.hip", "tgn_train.hip", "graphmixer.hip", "graphmixer_train.hip", "tcl.hip", "tcl_train.hip", "cawn.hip",
-           "cawn_train.hip", "metrics.hip", "edgebank.hip", "memory_rnn.hip", "time_encoding_probe.hip"]
+           "cawn_train.hip", "metrics.hip", "edgebank.hip", "memory_rnn.hip", "time_encoding_probe.hip", "gelu_probe.hip"]
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
             "-ffp-contract=off"]   # contractions are written explicitly (fmaf) where the oracle has them

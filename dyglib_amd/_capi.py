@@ -323,6 +323,8 @@ SIGNATURES = {
     "dygnn_mm_gathers_rows": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "dygnn_dw_grouped": (C.c_int, [C.c_int32, C.POINTER(DwPair), C.c_int32, C.c_void_p]),
     "dygnn_timeenc_probe": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),      # test-only (time_encoding_probe.hip)
+    "dygnn_gelu_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),         # test-only (gelu_probe.hip)
+    "dygnn_gelu_table_host": (C.c_int, [C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -281,6 +281,7 @@ PackLayout3 make_layout3(const Dims& d) {
     f.stream_p = take((size_t)(f.nstages_p + 1) * kStage * kFrag);
     f.w2 = take((size_t)kW2Frags * kFrag);
     f.qkv0c = take((size_t)2 * kQkvTiles * 64);
+    f.gelu = take((size_t)kGeluTabFloats);
     f.desc = take(((size_t)(f.nfrag + f.naux + f.nproj + d.NL * (kBwdFfnFrags + f.bwa_frags) + f.nfrag_p + kW2Frags) * sizeof(FragDesc) + 3) / 4);
     // prologue LDS split: pairs per workgroup, window arrays (5 x 2 sides x Smax ints per pair), projection slab
     const int per_pair = 5 * 2 * ((d.Smax + 3) & ~3);
@@ -356,6 +357,10 @@ int pack(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w
         DYGNN_LAUNCH_CHECK();
         return DYGNN_OK;
     }
+    // the GELU table does not depend on the weights: written here, behind the memset of a full pack, and left alone by every repack that
+    // reuses the descriptors.  (One host copy per process: the asynchronous copy may read it after this call has returned.)
+    static const std::vector<float> gelu_tab = [] { std::vector<float> t(kGeluTabFloats); gelu_table_fill(t.data()); return t; }();
+    DYGNN_HIP(hipMemcpyAsync(base + f.gelu, gelu_tab.data(), kGeluTabFloats * sizeof(float), hipMemcpyHostToDevice, s));
     StreamBuilder sb;
     int nchunk[4];
     build_stream(d, w, sb, nchunk);

@@ -9,6 +9,16 @@
 //     an accumulator tile is the B operand of the product that sums over its rows).
 // Only K and V of ONE head at a time live in LDS ([128 tokens][100], 2 x 51.2 KB); heads run back to back.
 //
+// LDS map (float offsets into the one dynamic array, 160 KB):
+//   kLdsK     0 .. 12799      K of one head [128][100]     | prologue: window arrays, projection slab | pooled layer: gpool [8][2][800]
+//   kLdsV 12800 .. 25599      V of one head [128][100]     | prologue: the same                       | epilogue: pool [8][2][208], mean, mean_g
+//     kLdsGelu 16128 .. 24319   inference, FFN phases only: the GELU table [4096][2] (gelu_table.h), staged by LDS-DMA once per FFN phase over
+//                               V rows 33 .. 115 (dead from the last out-projection of a layer to the next layer's first K/V stores); it lies
+//                               behind pool and over mean / mean_g, which are written after the FFN loop and its barrier
+//   25600 .. 25615            slack (tile 6 of the last K/V row reads 12 floats past it)
+//   kLdsRing 25616 .. 38927   weight ring, 52 fragments of 1 KiB
+//   kLdsMisc 38928 ..         FFN hidden bias [2][800], time-encoder w | b
+//
 // Weights: all 8 waves consume the SAME fragments in the SAME order, so the whole model is ONE linear stream of
 // 1-KiB MFMA-A fragments per kernel, brought on chip once per workgroup by LDS-DMA (global_load_lds, no VGPRs)
 // into a 52-fragment LDS ring and read with ds_read_b128.  (Measured in tools/v3_ubench.hip: weight fragments
@@ -22,6 +32,7 @@
 #pragma once
 #include "dygformer_layout.h"
 #include "fused3_plan.h"
+#include "gelu_table.h"
 #include "time_encoding.h"
 
 // The K = 200 products (QKV, FFN W1) spend 2 instead of 4 MFMAs on their last k-chunk (192..207: only 8 real k: mma_group2 / kpack), the
@@ -172,6 +183,49 @@ __device__ __forceinline__ float erf_as(float x) {
     return copysignf(fmaf(-p * t, e, 1.0f), x);
 }
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erf_as(v * 0.70710678118654752440f)); }
+
+// ---- the inference kernels' GELU: v Phi(v), Phi interpolated in the LDS table of gelu_table.h.  Seven VALU instructions and one
+// ds_read_b64 per element (fma, v_med3, v_cvt_i32, v_fract, v_lshl_add, fma, mul), no transcendental; the training kernels keep gelu_erf,
+// whose derivative the backward takes from hpre.  v <= -6 reads cell 0 at fraction 0: Phi = 0 and the result is -0 (or NaN for -inf, as
+// 0.5 v (1 + erf) gives); v >= 6 reads the last cell, whose knots are 1.0f; a NaN clamps or converts to a cell inside the table and
+// leaves through the final product.
+constexpr int kLdsGelu = kLdsV + 8 * 2 * kDP;       // behind pool_sides' [8 waves][2 sides][208] in the V region, which is dead during every FFN phase
+static_assert(kLdsGelu + kGeluTabFloats <= kLdsRing, "the GELU table ends inside the V region");
+static_assert((kLdsGelu * 4) % 16 == 0 && kGeluTabFloats % kFrag == 0, "the table is staged in whole, 16-byte aligned LDS-DMA pieces");
+static_assert(kLdsGelu * 4 < 65536, "the table's base fits the offset field of ds_read_b64");
+// In two halves, so that a caller with several elements issues all their reads before it consumes the first (gelu_table_n): cell -> the
+// cell's (base, step) read is issued, the position inside the cell comes back in `frac`; finish -> v Phi.
+__device__ __forceinline__ f2 gelu_table_cell(float v, const float* tab, float& frac) {
+    float t = fmaf(v, kGeluInvH, kGeluMid);
+    t = __builtin_amdgcn_fmed3f(t, 0.0f, kGeluTMax);
+    const int i = (int)t;
+    frac = __builtin_amdgcn_fractf(t);
+    return *reinterpret_cast<const f2*>(tab + 2 * i);
+}
+// (the empty asm keeps Phi scalar: paired into v_pk_fma_f32 / v_pk_mul_f32 the two halves of every ds_read_b64 result are first moved into
+//  pairs of their own — three v_mov_b32 per two elements, five instructions where the scalar form has four)
+__device__ __forceinline__ float gelu_table_finish(float v, float frac, const f2 e) { return v * keep_scalar(fmaf(frac, e.y, e.x)); }
+template <int N>
+__device__ __forceinline__ void gelu_table_n(float (&v)[N], const float* tab) {
+    f2 e[N];
+    float fr[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) e[k] = gelu_table_cell(v[k], tab, fr[k]);
+    __builtin_amdgcn_sched_barrier(0);           // N reads in flight, one LDS round trip (left alone hipcc consumes them two by two)
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = gelu_table_finish(v[k], fr[k], e[k]);
+}
+__device__ __forceinline__ float gelu_table(float v, const float* tab) {
+    float w[1] = {v};
+    gelu_table_n<1>(w, tab);
+    return w[0];
+}
+// The table into LDS at float offset lds_off: kGeluTabFloats / kFrag = 32 pieces of 1 KiB split over the workgroup's nw waves.  The caller
+// waits for its own pieces (s_waitcnt vmcnt(0)) and passes a barrier before anyone reads the table.
+// gtab_lane = table + lane * 4 (per lane).
+__device__ __forceinline__ void stage_gelu_table(const float* gtab_lane, int lds_off, int wave, int nw) {
+    for (int j = wave; j < kGeluTabFloats / kFrag; j += nw) dma_frag(gtab_lane + j * kFrag, lds_off + j * kFrag);
+}
 
 // load / LDS-DMA source for rows that do not exist (static: one copy per translation unit, the build has no relocatable device code)
 [[maybe_unused]] static __device__ __attribute__((aligned(16))) float g_zero16[4] = {0.f, 0.f, 0.f, 0.f};

@@ -48,14 +48,22 @@ struct Args {
                                   // its chunks have left the walk like a zero table's (nchunk = 0) and the token owner adds P rows instead.  nullptr: the MFMA path
     const float* qkv0c;           // inference only: layer 0's constant-channel operands of the prefix length in use, [38 tiles][64 lanes] (fused3_plan.h)
     int qkv0_skip;                // ... and the k-chunks of layer 0's Q/K/V products they stand for: 0 (none), 3 or 6
+    const float* gelu_tab;        // inference only: the GELU table [4096][2] (gelu_table.h), staged into LDS once per FFN phase
     float qscale;
     train::TrainOut tr;           // training forward only (k_dygformer_fused3<.., true>): the dense activations the backward pass reads
 };
 
-__device__ __forceinline__ void gelu_tiles(f4 (&t)[2]) {
+// DyGFormer.py:458.  TAB (every inference instance): Phi from the LDS table at `tab` (fused3_device.h: gelu_table); the training instances keep
+// the erf form, whose derivative their backward takes from hpre
+template <bool TAB>
+__device__ __forceinline__ void gelu_tiles(f4 (&t)[2], const float* tab) {
+    if constexpr (TAB) {
+        float v[8] = {t[0].x, t[0].y, t[0].z, t[0].w, t[1].x, t[1].y, t[1].z, t[1].w};
+        gelu_table_n<8>(v, tab);
+        t[0] = f4{v[0], v[1], v[2], v[3]}; t[1] = f4{v[4], v[5], v[6], v[7]};
+    } else {
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        t[u].x = gelu_erf(t[u].x); t[u].y = gelu_erf(t[u].y); t[u].z = gelu_erf(t[u].z); t[u].w = gelu_erf(t[u].w);   // DyGFormer.py:458
+        for (int u = 0; u < 2; ++u) { t[u].x = gelu_erf(t[u].x); t[u].y = gelu_erf(t[u].y); t[u].z = gelu_erf(t[u].z); t[u].w = gelu_erf(t[u].w); }
     }
 }
 template <int TPW>
@@ -135,6 +143,9 @@ constexpr int kLdsPool = kLdsV;                     // [8 waves][2 sides][208] p
 constexpr int kLdsMean = kLdsPool + 8 * 2 * kDP;    // [4 columns][208] per-side token means, column = 2 * pair + side
 constexpr int kLdsMeanG = kLdsMean + 4 * kDP;       // [4 columns][800] per-side token means of gelu(h)
 static_assert(8 * 2 * kHid <= kLdsV && kLdsMeanG + 4 * kHid <= kLdsRing, "the pooled sums fit the K/V region");
+// the GELU table (fused3_device.h) during the pooled layer's FFN loop: gpool (K region) and pool end in front of it; mean and mean_g, which it
+// lies over, are written after the loop and the barrier behind it
+static_assert(kLdsGPool + 8 * 2 * kHid <= kLdsGelu && kLdsPool + 8 * 2 * kDP <= kLdsGelu && kLdsMean >= kLdsGelu, "the GELU table and the pooled sums");
 
 // ================================================================================================
 // TR = false: inference.  TR = true: the training forward — dropout at the reference's four sites per layer and every
@@ -894,6 +905,16 @@ __device__ __forceinline__ void fused3_body(const Args& a) {
             proj_t(xo, oa, ws, ringl, active);
             TACC(T_OPROJ);
         }
+        if constexpr (!TR) {
+            // The GELU table into the V region (kLdsGelu), by every wave, with or without tokens.  Every wave is past the stage barriers of head
+            // 1's out-projection, and its last read of V (the P V product of head 1) lies in front of the first of them: V is dead.  The DMA
+            // lands behind the bias add and LN1; the wait and the barrier in front of the FFN loop publish it.  After the loop nothing has
+            // to be waited for: the next layer's first K/V stores follow its Q product — seven stage barriers after any wave's last GELU —
+            // and the epilogue's columns over the table (kLdsMean, kLdsMeanG) are written behind the barrier that follows the loop.
+            int gl4 = lane * 4;
+            asm volatile("" : "+v"(gl4));      // (the per-lane source address is formed here, not kept — spilled — through the layers)
+            stage_gelu_table(a.gelu_tab + gl4, kLdsGelu, wave, NW);
+        }
         // out-projection bias (one vector fragment)
         ws.fit(1);
         {
@@ -923,6 +944,12 @@ __device__ __forceinline__ void fused3_body(const Args& a) {
         const uint32_t sk2 = TR ? a.tr.dr.site_key((uint32_t)(4 * l + 2)) : 0u;
         TACC(T_LN);
         ws.align26();
+        if constexpr (!TR) {
+            // ffn_w1 consumes its 26 fragments without a crossing and align26 crosses a stage only where the position asks for it: the table's
+            // own wait and barrier
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        }
         const bool last = PL != 0 && l == a.NL - 1;      // the pooled layer
         const int ptok = 16 * tt + c;
         if (last) {
@@ -979,7 +1006,7 @@ __device__ __forceinline__ void fused3_body(const Args& a) {
                         *reinterpret_cast<f4*>(hp) = h[0]; *reinterpret_cast<f4*>(hp + 16) = h[1];
                     }
                 }
-                gelu_tiles(h);
+                gelu_tiles<!TR>(h, lds + kLdsGelu);
                 if constexpr (TR) {      // dropout on the activation (DyGFormer.py:458): element (row, hidden unit n) draws mask(site, row * 800 + n)
 #pragma unroll
                     for (int u = 0; u < 2; ++u)
@@ -1148,6 +1175,7 @@ inline int fused3_args(const Dims& d, const PackedLayout& pl, const dygnn_dygfor
     }
     a.outfrag = base + f.aux;
     a.w2frag = base + f.w2; a.b2_last = w->layers[d.NL - 1].ffn1_bias;
+    a.gelu_tab = base + f.gelu;
     a.projw = base + f.proj; a.proj_frags = (int)f.nproj; a.slab_chunks = f.slab_chunks; a.scr_floats = f.scr_floats;
     a.slab_in_ring = f.slab_in_ring;
     a.tab_off = f.tab_off; a.tab_slots = f.tab_slots; a.tab_bits = f.tab_bits;

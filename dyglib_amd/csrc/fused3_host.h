@@ -28,6 +28,7 @@ struct PackLayout3 {       // float offsets relative to PackedLayout.fused3
     size_t stream_p; int64_t nfrag_p; int nstages_p;       // ring stream of the pooled inference kernels (build_stream, pooled)
     size_t w2;                                     // ... and their last layer's W2 fragments (build_w2)
     size_t qkv0c;                                  // layer 0's constant-channel operands (fused3_plan.h: qkv0_const): [K0 = 48 | 96][38 tiles][64 lanes]
+    size_t gelu;                                   // the GELU table of the inference kernels (gelu_table.h): [4096][2], independent of the weights
     size_t desc;           // FragDesc table (device copy), 8-byte aligned
     size_t total;
 };

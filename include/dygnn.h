@@ -941,6 +941,14 @@ int dygnn_dw_grouped(int32_t K, const dygnn_dw_pair* pairs, int32_t npairs, dygn
  * Another form, negative n or n > 2^31, a NULL array with n > 0: DYGNN_E_INVALID.  No backbone calls it. */
 int dygnn_timeenc_probe(int32_t form, const float* x, int64_t n, float* out, dygnn_stream_t stream);
 
+/* Test-only: the GELU of the fused DyGFormer forward on n device floats: out[i] = gelu(in[i]).  form 0: the table form of the inference
+ * kernels — the probe stages the table (csrc/gelu_table.h) into LDS by the kernels' routine, at the kernels' offset, and runs their device
+ * function; form 1: the erf form (Abramowitz & Stegun 7.1.26) of the training kernels.  The call returns after the work is done.
+ * Another form, negative n or n > 2^31, a NULL array with n > 0: DYGNN_E_INVALID.  No backbone calls it.
+ * gelu_table_host: the table as the packed buffer holds it, out[4096][2] = (Phi(x_i), Phi(x_{i+1}) - Phi(x_i)), x_i = -6 + 12 i / 4096 (host). */
+int dygnn_gelu_probe(const float* in, float* out, int64_t n, int32_t form, dygnn_stream_t stream);
+int dygnn_gelu_table_host(float* out);
+
 #ifdef __cplusplus
 }
 #endif
