@@ -203,6 +203,7 @@ SIGNATURES = {
     "dygnn_dygformer_pack_plan_host": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "dygnn_dygformer_pair_tokens_host": (None, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "dygnn_dygformer_qkv_tile_row_host": (C.c_int32, [C.c_int32, C.c_int32]),
+    "dygnn_dygformer_pool_sum_slot_host": (None, [C.c_int32, C.c_void_p]),
     "dygnn_dygformer_qkv0_const_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "dygnn_dygformer_workspace_bytes": (C.c_size_t, [C.POINTER(DygformerConfig), C.c_int64]),
     "dygnn_dygformer_workspace_bytes_for": (C.c_size_t, [C.POINTER(DygformerConfig), C.c_int64, C.c_int32]),

@@ -87,3 +87,10 @@ extern "C" void dygnn_dygformer_pair_tokens_host(int32_t len_s, int32_t len_d, i
     const dygnn::v3::PairTokens t = dygnn::v3::pair_tokens(len_s, len_d, L, P, T_s, T_d);
     out[0] = t.Rs; out[1] = t.Rd; out[2] = t.ms; out[3] = t.md; out[4] = t.Tc;
 }
+// where the pooled layer's reduce-scatter leaves its sums (tests): out = {1 if the lane stores, tile, first row, input of result 0, of result 1}
+extern "C" void dygnn_dygformer_pool_sum_slot_host(int32_t lane, int32_t* out) {
+    using namespace dygnn::v3;
+    const int bank = (lane & 15) >> 2;
+    out[0] = pool_sum_stores(lane) ? 1 : 0; out[1] = pool_sum_tile(lane); out[2] = pool_sum_row(lane);
+    out[3] = pool_sum_input(0, bank); out[4] = pool_sum_input(1, bank);
+}

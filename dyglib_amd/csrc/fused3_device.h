@@ -155,17 +155,47 @@ __device__ __forceinline__ float row_sum16(float v) {
     v += dpp_mov<0x140>(v);
     return v;
 }
-// The same four additions for the per-side pooling sums (pool_sides, and gelu(h) in the pooled layer), each as ONE instruction.  Written as above, hipcc pairs the
-// additions of two sums into a v_pk_add_f32, which has no DPP form: every stage then costs a v_mov_b32_dpp per value plus the packed
-// add.  An empty asm on each stage's result keeps the sums scalar, and the DPP move folds into its add (v_add_f32_dpp): one VALU
-// instruction per value and stage instead of 1.5, same operands, same order, same bits.
+// An empty asm keeps a value scalar where hipcc would pair it with a neighbour into a v_pk_* instruction (gelu_table_finish)
 __device__ __forceinline__ float keep_scalar(float v) { asm("" : "+v"(v)); return v; }
-__device__ __forceinline__ float row_sum16_dpp(float v) {
-    v = keep_scalar(v + dpp_mov<0xB1>(v));
-    v = keep_scalar(v + dpp_mov<0x4E>(v));
-    v = keep_scalar(v + dpp_mov<0x141>(v));
-    v = keep_scalar(v + dpp_mov<0x140>(v));
-    return v;
+// The per-side pooling sums (pool_sides, and gelu(h) in the pooled layer) as a REDUCE-SCATTER: eight values per lane (two accumulator tiles,
+// or one tile of either side) are summed over the 16 tokens of the row, and every partial sum is computed once instead of in all sixteen
+// lanes.  Lane bits 3 and 2 are folded by v_add_f32_dpp with a bank mask — the enabled banks take value + rotated value, the disabled
+// ones keep what the register held, so one instruction per input register halves the registers: 8 -> 4 (row_ror:8: banks 0, 1 keep the
+// first tile, banks 2, 3 the second), 4 -> 2 (row_ror:12 / row_ror:4: even banks keep registers 0, 1, odd banks registers 2, 3; lane c
+// reads lane c - n mod 16).  Bits 1 and 0 are two quad_perm adds on the two registers that remain.  16 VALU instructions for eight
+// sums, where eight row_sum16 take 32.  Afterwards every lane of bank b = (lane & 15) >> 2 holds in result j the sum of input
+// pool_sum_input(j, b) (fused3_plan.h); one lane per bank stores its two adjacent words.
+// Every value takes the same tree whatever register or bank it ends in — ((c + c^8) + (c^4 + c^12)) per lane, then the quad's lanes ^1, ^2
+// — and a float add commutes, so a row's bits depend on its sixteen tokens alone.
+// Inline asm: __builtin_amdgcn_update_dpp with a bank mask comes out as a move and an add.  The hazard "VALU write of a VGPR, then a DPP
+// read of it: 2 wait states" is the asm's own business (hipcc does not look inside): the leading s_nop covers the inputs, the instruction
+// order and the two s_nop 0 cover the chain, and nothing after the last add reads with DPP.  The outputs are early-clobber: an input
+// must not share a register with one of them, equal value or not.
+__device__ __forceinline__ timeenc::f2 row_sums8(const f4 a, const f4 b) {
+    float v0 = a.x, v1 = a.y, v2 = a.z, v3 = a.w;
+    const float v4 = b.x, v5 = b.y, v6 = b.z, v7 = b.w;
+    asm("s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+        "v_add_f32_dpp %1, %1, %1 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+        "v_add_f32_dpp %2, %2, %2 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+        "v_add_f32_dpp %3, %3, %3 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+        "v_add_f32_dpp %0, %4, %4 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %1, %5, %5 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %2, %6, %6 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %3, %7, %7 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"
+        "v_add_f32_dpp %1, %1, %1 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"
+        "v_add_f32_dpp %0, %2, %2 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"
+        "v_add_f32_dpp %1, %3, %3 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"
+        "s_nop 0\n\t"
+        "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
+        : "+&v"(v0), "+&v"(v1), "+&v"(v2), "+&v"(v3)
+        : "v"(v4), "v"(v5), "v"(v6), "v"(v7));
+    return timeenc::f2{v0, v1};
 }
 
 // The time encoder's cosine is time_encoding.h; the fused kernels take the select form of its guard.

@@ -122,20 +122,25 @@ __device__ __forceinline__ void residual_dropped(f4 (&x)[kNT], const float* xin,
     }
 }
 
-// per-side sums over the 16 tokens of this wave's tile of the 13 register tiles: pool[wave][side][208] (lane c == 0 of every row stores)
+// per-side sums over the 16 tokens of this wave's tile of the 13 register tiles: pool[wave][side][208].  row_sums8 takes the tiles two by
+// two per side, and tile 12 as the pair (source form, destination form); the first lane of every bank stores its two words (fused3_plan.h)
 // wsrc / wdst: how often this lane's token counts on either side (0, 1, or the padding token's multiplicity; x * 1 is x)
-__device__ __forceinline__ void pool_sides(const f4 (&x)[kNT], float* pool, int wave, int c, int g, float wsrc, float wdst) {
+__device__ __forceinline__ void pool_sides(const f4 (&x)[kNT], float* pool, int wave, int lane, float wsrc, float wdst) {
+    const bool st = pool_sum_stores(lane);
+    float* ps = pool + wave * 2 * kDP + pool_sum_row(lane);
+    float* pt = ps + 16 * pool_sum_tile(lane);
 #pragma unroll
-    for (int i = 0; i < kNT; ++i) {
-        f4 vs = wsrc != 0.f ? x[i] * wsrc : zero4();
-        f4 vd = wdst != 0.f ? x[i] * wdst : zero4();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { vs[r] = row_sum16_dpp(vs[r]); vd[r] = row_sum16_dpp(vd[r]); }
-        if (c == 0) {
-            *reinterpret_cast<f4*>(pool + (wave * 2 + 0) * kDP + 16 * i + 4 * g) = vs;
-            *reinterpret_cast<f4*>(pool + (wave * 2 + 1) * kDP + 16 * i + 4 * g) = vd;
+    for (int i = 0; i + 1 < kNT; i += 2) {
+        const f2 zs = row_sums8(wsrc != 0.f ? x[i] * wsrc : zero4(), wsrc != 0.f ? x[i + 1] * wsrc : zero4());
+        const f2 zd = row_sums8(wdst != 0.f ? x[i] * wdst : zero4(), wdst != 0.f ? x[i + 1] * wdst : zero4());
+        if (st) {
+            *reinterpret_cast<f2*>(pt + 16 * i) = zs;
+            *reinterpret_cast<f2*>(pt + kDP + 16 * i) = zd;
         }
     }
+    static_assert(kNT % 2 == 1, "the last tile is left over: its two sides are one block");
+    const f2 z = row_sums8(wsrc != 0.f ? x[kNT - 1] * wsrc : zero4(), wdst != 0.f ? x[kNT - 1] * wdst : zero4());
+    if (st) *reinterpret_cast<f2*>(ps + kDP * pool_sum_tile(lane) + 16 * (kNT - 1)) = z;
 }
 // pooled last layer: where its sums live in the K/V region (dead from the last out-projection on)
 constexpr int kLdsGPool = 0;                        // [8 waves][2 sides][800] per-wave sums of gelu(h) over the wave's tokens = the K region
@@ -959,39 +964,36 @@ __device__ __forceinline__ void fused3_body(const Args& a) {
             int ptk = ptok;
             if constexpr (!TR) asm volatile("" : "+v"(ptk));      // (the weights are formed here, not kept through the layers)
             side_weights(ptk, wsrc, wdst);
-            pool_sides(x, lds + kLdsPool, wave, c, g, wsrc, wdst);
+            pool_sides(x, lds + kLdsPool, wave, lane, wsrc, wdst);
         }
         // wave-uniform: the tile holds tokens of both sides, or the padding token (which counts on both)
         const bool straddle = (16 * tt < Ts && Ts < 16 * (tt + 1)) || (16 * tt <= padtok && padtok < 16 * (tt + 1));
         const bool dst_tile = 16 * tt >= Ts;
-        // sums of gelu(h) over the tile's tokens of either side (DPP row sums, as pool_sides); a tile of one side sums once: the other
-        // side's sum of zeros is zero, so the bits do not depend on which form ran
+        // sums of gelu(h) over the tile's tokens of either side (row_sums8 on the step's two hidden tiles, as pool_sides); a tile of one side
+        // sums once: the other side's sum of zeros is zero, so the bits do not depend on which form ran
         const bool g_pad = ptok == padtok;
         const bool g_src = ptok < Ts || (g_pad && ms > 0), g_dst = (ptok >= Ts && ptok < T && !g_pad) || (g_pad && md > 0);
         const float msf = (float)ms, mdf = (float)md;
         auto gelu_sums = [&](const f4 (&h)[2], int p) {
-            float* gp = lds + kLdsGPool + wave * 2 * kHid + 32 * p + 4 * g;
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                f4 vs, vd;
-                if (straddle) {
-                    // (the weights are formed here from lane masks and scalars: kept in two VGPRs through the FFN loop they spill)
-                    float one = 1.0f;
-                    asm volatile("" : "+v"(one));
-                    const float wsrc = g_pad ? msf : one, wdst = g_pad ? mdf : one;
-                    vs = g_src ? h[u] * wsrc : zero4();
-                    vd = g_dst ? h[u] * wdst : zero4();
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { vs[r] = row_sum16_dpp(vs[r]); vd[r] = row_sum16_dpp(vd[r]); }
-                } else {
-                    f4 v = ptok < T ? h[u] : zero4();
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = row_sum16_dpp(v[r]);
-                    vs = dst_tile ? zero4() : v;
-                    vd = dst_tile ? v : zero4();
-                }
-                if (c == 0) { *reinterpret_cast<f4*>(gp + 16 * u) = vs; *reinterpret_cast<f4*>(gp + kHid + 16 * u) = vd; }
+            // (the store address is formed here from the lane, like the weights below, so that it is not live through the FFN loop)
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            float* gp = lds + kLdsGPool + wave * 2 * kHid + 32 * p + 16 * pool_sum_tile(ln) + pool_sum_row(ln);
+            timeenc::f2 zs, zd;
+            if (straddle) {
+                // (the weights are formed here from lane masks and scalars: kept in two VGPRs through the FFN loop they spill)
+                float one = 1.0f;
+                asm volatile("" : "+v"(one));
+                const float wsrc = g_pad ? msf : one, wdst = g_pad ? mdf : one;
+                zs = row_sums8(g_src ? h[0] * wsrc : zero4(), g_src ? h[1] * wsrc : zero4());
+                zd = row_sums8(g_dst ? h[0] * wdst : zero4(), g_dst ? h[1] * wdst : zero4());
+            } else {
+                const timeenc::f2 z = row_sums8(ptok < T ? h[0] : zero4(), ptok < T ? h[1] : zero4());
+                const timeenc::f2 none{0.f, 0.f};
+                zs = dst_tile ? none : z;
+                zd = dst_tile ? z : none;
             }
+            if (pool_sum_stores(ln)) { *reinterpret_cast<timeenc::f2*>(gp) = zs; *reinterpret_cast<timeenc::f2*>(gp + kHid) = zd; }
         };
         // W1(p) | W2(p) per step; W2 accumulates straight into the residual registers (no separate FFN accumulator: 52 VGPRs fewer)
 #pragma unroll 1
@@ -1056,7 +1058,7 @@ __device__ __forceinline__ void fused3_body(const Args& a) {
         if constexpr (PL == 0) {
             float wsrc, wdst;
             side_weights(tok, wsrc, wdst);
-            pool_sides(x, pool, wave, c, g, wsrc, wdst);
+            pool_sides(x, pool, wave, lane, wsrc, wdst);
             TACC(T_POOL1);
             __syncthreads();
         }

@@ -132,5 +132,16 @@ DYGNN_HD inline float qkv0_const(const float* in_proj, const float* gamma, const
     return (float)s;
 }
 
+// ---- the per-side token sums of the pooled layer (row_sums8, fused3_device.h): where the reduce-scatter leaves its sums.  Its eight inputs per
+// lane are two register tiles, input k = 4 u + r = row 4 g + r of tile u in lane group g = lane >> 4; the 16 lanes of a group are the
+// row's 16 tokens, in four banks of four lanes.  Afterwards every lane of bank `bank` holds in result j (0, 1) the token sum of input
+DYGNN_HD inline int pool_sum_input(int j, int bank) { return 4 * (bank >> 1) + 2 * (bank & 1) + j; }
+// The first lane of every bank stores its two results as one pair of words.  Inside a block of two consecutive tiles [2][16] rows (gpool's
+// 32 hidden units of a step, pool's tiles 2 i and 2 i + 1) the pair begins at row pool_sum_row(lane) of tile pool_sum_tile(lane); where the
+// two input tiles are one tile's source and destination form (pool's tile 12), pool_sum_tile is the side.
+DYGNN_HD inline bool pool_sum_stores(int lane) { return (lane & 3) == 0; }
+DYGNN_HD inline int pool_sum_tile(int lane) { return (lane >> 3) & 1; }
+DYGNN_HD inline int pool_sum_row(int lane) { return 4 * (lane >> 4) + ((lane >> 1) & 2); }
+
 }  // namespace v3
 }  // namespace dygnn

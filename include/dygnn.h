@@ -193,6 +193,10 @@ int64_t dygnn_dygformer_pack_plan_host(const int32_t* tiles, int64_t n, int32_t*
  * gamma / beta = norm_layers.0 [200], bias = the node then the edge projection bias (>= k0 floats).  All host pointers. */
 int32_t dygnn_dygformer_qkv_tile_row_host(int32_t tile, int32_t c);
 int dygnn_dygformer_qkv0_const_host(const float* in_proj_weight, const float* gamma, const float* beta, const float* bias, int32_t k0, float* out);
+/* ... and of the pooled layer's per-side token sums.  The kernels sum eight values per lane (input k = 4 u + r: row 4 (lane >> 4) + r of
+ * register tile u) over the 16 lanes of a lane group by a reduce-scatter; pool_sum_slot: out = {1 if `lane` (0 .. 63) stores, the tile u and
+ * the first row (0 .. 15) of the two adjacent words it stores, the inputs whose sums its two results hold}. */
+void dygnn_dygformer_pool_sum_slot_host(int32_t lane, int32_t* out);
 
 /* One launch sequence for `batch` (src,dst,t) pairs.  group_size = G splits the pairs into consecutive
  * groups of G that are padded independently (each group has its own S_src/S_dst, models/DyGFormer.py:219-226):
