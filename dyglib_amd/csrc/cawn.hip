@@ -38,7 +38,6 @@ using tile::lds_limit;
 using tile::mfma4;
 using tile::round16;
 using tile::wave_product;
-using tile::wave_sum;
 using tile::z4;
 
 constexpr int kMaxWalks = 128;      // M = k^W: two keys per lane in k_cawn_attn
@@ -509,9 +508,7 @@ __global__ __launch_bounds__(kThreads) void k_cawn_attn(const float* __restrict_
             }
             s0 = on0 ? s0 * scale : -INFINITY;
             s1 = on1 ? s1 * scale : -INFINITY;
-            float m = fmaxf(s0, s1);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+            const float m = wave_max(fmaxf(s0, s1));
             const float e0 = on0 ? expf(s0 - m) : 0.f, e1 = on1 ? expf(s1 - m) : 0.f;
             const float sum = wave_sum(e0 + e1);
             const float p0 = e0 / sum, p1 = e1 / sum;

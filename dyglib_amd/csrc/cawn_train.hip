@@ -47,7 +47,6 @@ namespace dygnn {
 namespace cawnt {
 
 using timeenc::cos_time;
-using tile::wave_sum;
 using train::colsum;
 
 constexpr int kMaxWalks = 64;       // M = k^W: one key per lane in the attention kernels
@@ -312,9 +311,7 @@ __global__ __launch_bounds__(256) void k_cawnt_attn_fwd(const float* __restrict_
         const float* kr = Ks + (on ? lane : 0) * kLdh;
         for (int cc = 0; cc < dh; ++cc) s = fmaf(Qs[r * kLdh + cc], kr[cc], s);
         s = on ? s * scale : -INFINITY;
-        float m = s;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+        const float m = wave_max(s);
         const float ex = on ? expf(s - m) : 0.f;
         const float p = ex / wave_sum(ex);
         float pd = 0.f;

@@ -71,7 +71,7 @@ static __global__ __launch_bounds__(256) void k_colsum_fin(const float* __restri
     if (c >= cols) return;                                           // wave-uniform
     float s = 0.f;
     for (int b = lane; b < nblk; b += 64) s += part[(size_t)b * cols + c];
-    s = tile::wave_sum(s);
+    s = wave_sum(s);
     if (lane == 0) out.add(c, s);
 }
 // out (ColOut or ColSegs) += the column sums of A [rows][cols];  part: ceil(rows / kColRows) * cols floats of scratch

@@ -23,6 +23,24 @@ struct Carve {
     size_t take(size_t bytes) { const size_t r = o; o += (bytes + 255) & ~size_t(255); return r; }
 };
 
+// Sum / maximum over the 64 lanes of a wave, in every lane: the xor butterfly 32, 16, .. 1, so the order of the additions (and with it the
+// bits) is fixed.  T = float, double or unsigned long long.  All 64 lanes must call.
+__device__ __forceinline__ float larger(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double larger(double a, double b) { return fmax(a, b); }
+__device__ __forceinline__ unsigned long long larger(unsigned long long a, unsigned long long b) { return b > a ? b : a; }
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+    return v;
+}
+template <typename T>
+__device__ __forceinline__ T wave_max(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = larger(v, __shfl_xor(v, o, kWave));
+    return v;
+}
+
 // First index p in [lo, hi) with ts[p] >= t, or hi (np.searchsorted side='left' on an ascending CSR row).  A 64-ary search: every step the
 // wave probes 64 evenly spaced timestamps and one ballot+popcount picks the sub-range.  All 64 lanes must call (uniform lo/hi/t).
 __device__ __forceinline__ int64_t wave_lower_bound(const double* __restrict__ ts, int64_t lo, int64_t hi, double t, int lane) {

@@ -1,7 +1,9 @@
 // Dropout of the training path (models/DyGFormer.py:429, :456-460) and the dense activation set the backward pass reads.
-// Masks are never stored: the forward kernels (dygformer_train.hip unfused, fused3_forward.h fused) and the backward pass draw them
-// from the same counter-based hash of (seed, site, element index); site = 4 * layer + {0: attention probabilities, 1: attention output,
-// 2: FFN activation, 3: FFN output}, element index = the element's offset in the dense row-major activation of that site.
+// Masks are never stored: the forward kernels (unfused: k_softmax_fwd in dygformer_train.hip and the element kernels of train_elements.h;
+// fused: fused3_forward.h) and the backward pass draw them from the same counter-based hash of (seed, site, element index);
+// site = 4 * layer + {0: attention probabilities, 1: attention output, 2: FFN activation, 3: FFN output}, element index = the element's
+// offset in the dense row-major activation of that site.  The other backbones' training paths use the same generator with sites and
+// element numbers of their own (train_rows.h, graphmixer_train.hip).
 #pragma once
 #include "common.h"
 

@@ -5,22 +5,13 @@
 // padded lengths S_src/S_dst (models/DyGFormer.py:219-226) stay on the device in CallDims and
 // every kernel is launched for the worst case and skips rows beyond the actual token count.
 #include "dygformer_layout.h"
+#include "dygformer_rows.h"
+#include "gelu_exact.h"
 
 namespace dygnn {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------------
-// pack: transposes + co-occurrence LUT
+// pack: transposes + co-occurrence table
 // ------------------------------------------------------------------------------------------------
 __global__ void k_transpose(const float* __restrict__ W, float* __restrict__ Wt, int N, int K) {
     // W [N][K] -> Wt [K][N]
@@ -37,20 +28,24 @@ __global__ void k_transpose(const float* __restrict__ W, float* __restrict__ Wt,
     }
 }
 
-// f(c)[j] = b1[j] + sum_i W1[j][i] * relu(W0[i]*c + b0[i])     (models/DyGFormer.py:332-335)
+// f(c)[j] = b1[j] + sum_k W1[j][k] * relu(W0[k]*c + b0[k]) for the count c = blockIdx.x   (models/DyGFormer.py:332-335)
 // evaluated with the same operation order for every count c, so the table entry IS the value the
 // reference's MLP produces for that count (fma for the K=1 Linear like PyTorch's CPU addmm).
-__global__ void k_cooc_lut(const float* __restrict__ w0, const float* __restrict__ b0, const float* __restrict__ w1,
-                           const float* __restrict__ b1, int C, int rows, float* __restrict__ lut) {
+// hid (may be NULL): the hidden row, kept for the training backward.
+__global__ void k_cooc_table(const float* __restrict__ w0, const float* __restrict__ b0, const float* __restrict__ w1, const float* __restrict__ b1,
+                             int C, float* __restrict__ lut, float* __restrict__ hid) {
     const int c = blockIdx.x;
-    const int j = threadIdx.x;
-    if (c >= rows || j >= C) return;
-    float acc = b1[j];
-    for (int i = 0; i < C; ++i) {
-        const float h = fmaxf(fmaf((float)c, w0[i], b0[i]), 0.f);
-        acc = fmaf(h, w1[(size_t)j * C + i], acc);
+    extern __shared__ float h[];
+    for (int j = threadIdx.x; j < C; j += blockDim.x) {
+        h[j] = fmaxf(fmaf(w0[j], (float)c, b0[j]), 0.f);
+        if (hid) hid[c * C + j] = h[j];
     }
-    lut[(size_t)c * C + j] = acc;
+    __syncthreads();
+    for (int j = threadIdx.x; j < C; j += blockDim.x) {
+        float acc = b1[j];
+        for (int k = 0; k < C; ++k) acc = fmaf(w1[j * C + k], h[k], acc);
+        lut[c * C + j] = acc;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -121,7 +116,7 @@ __global__ __launch_bounds__(256) void k_embed(EmbedArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int64_t b = blockIdx.x;
     const CallDims cd = a.cd[b / a.G];
-    const int Ss = cd.S_s, Sd = cd.S_d, S = Ss + Sd;
+    const int Ss = cd.S_s, Sd = cd.S_d;
     int32_t* ids = reinterpret_cast<int32_t*>(smem);            // [2*Smax]
     int32_t* eids = ids + 2 * a.Smax;
     float* dts = reinterpret_cast<float*>(eids + 2 * a.Smax);
@@ -129,38 +124,8 @@ __global__ __launch_bounds__(256) void k_embed(EmbedArgs a) {
     int32_t* c1 = c0 + 2 * a.Smax;
     float* stage = reinterpret_cast<float*>(c1 + 2 * a.Smax);   // [4 waves][stage_floats]
 
-    const double t = a.times[b];
-    // ---- windows (pad_sequences, DyGFormer.py:228-245), left aligned, position 0 = target node
-    for (int p = threadIdx.x; p < S; p += blockDim.x) {
-        const bool is_dst = p >= Ss;
-        const int j = is_dst ? p - Ss : p;
-        const int64_t q = is_dst ? a.B + b : b;
-        const int32_t len = a.hist_len[q];
-        const int32_t m = len < a.L - 1 ? len : a.L - 1;
-        int32_t id = 0, e = 0;
-        float tn = 0.f;
-        if (j == 0) {
-            const int64_t qid = is_dst ? a.dst[b] : a.src[b];
-            id = qid < 0 || qid >= a.g.num_nodes ? 0 : (int32_t)qid;      // a bad query id is the padding node (never a fault)
-            tn = (float)t;
-        } else if (j <= m) {
-            const int64_t pos = a.end_pos[q] - m + (j - 1);
-            id = a.g.nbr[pos]; e = a.g.eid[pos]; tn = (float)a.g.ts[pos];
-        }
-        ids[p] = id; eids[p] = e;
-        dts[p] = (float)(t - (double)tn);                       // DyGFormer.py:263: f64 - f32 -> f64 -> .float()
-    }
-    __syncthreads();
-    // ---- co-occurrence counts (DyGFormer.py:337-393)
-    for (int p = threadIdx.x; p < S; p += blockDim.x) {
-        const int32_t v = ids[p];
-        int32_t cs = 0, cdn = 0;
-        for (int q = 0; q < Ss; ++q) cs += (ids[q] == v);
-        for (int q = Ss; q < S; ++q) cdn += (ids[q] == v);
-        if (v == 0) { cs = 0; cdn = 0; }
-        c0[p] = cs; c1[p] = cdn;
-    }
-    __syncthreads();
+    rows::fill_windows(rows::Csr{a.g.nbr, a.g.eid, a.g.ts, a.g.num_nodes}, a.src, a.dst, a.times, a.hist_len, a.end_pos, a.B, b, Ss, Sd, a.L, ids, eids,
+                       dts, c0, c1);
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float* st = stage + (size_t)wave * a.stage_floats;
@@ -180,8 +145,8 @@ __global__ __launch_bounds__(256) void k_embed(EmbedArgs a) {
                     float v;
                     if (ch == 0) v = a.node_feat[(size_t)ids[pp] * a.Fn + f];                      // DyGFormer.py:259
                     else if (ch == 1) v = a.edge_feat[(size_t)eids[pp] * a.Fe + f];                // :261
-                    else if (ch == 2) v = ids[pp] == 0 ? 0.f : cosf(fmaf(dts[pp], a.time_w[f], a.time_b[f]));  // :263-266
-                    else v = a.lut[(size_t)c0[pp] * a.C + f] + a.lut[(size_t)c1[pp] * a.C + f];    // :409-411
+                    else if (ch == 2) v = rows::time_feature(ids[pp], dts[pp], a.time_w, a.time_b, f);
+                    else v = rows::cooc_feature(a.lut, a.C, c0[pp], c1[pp], f);
                     st[k] = v;
                 }
             }
@@ -208,14 +173,8 @@ __global__ __launch_bounds__(256) void k_layernorm(const float* __restrict__ X, 
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= B * Tmax) return;
     if ((int)(row % Tmax) >= cd[(row / Tmax) / G].T) return;
-    const float* x = X + row * D;
-    float s = 0.f;
-    for (int k = lane; k < D; k += kWave) s += x[k];
-    const float mean = wave_sum(s) / (float)D;
-    float v = 0.f;
-    for (int k = lane; k < D; k += kWave) { const float d = x[k] - mean; v = fmaf(d, d, v); }
-    const float rstd = 1.0f / sqrtf(wave_sum(v) / (float)D + 1e-5f);
-    for (int k = lane; k < D; k += kWave) Y[row * D + k] = (x[k] - mean) * rstd * gamma[k] + beta[k];
+    float mean, rstd;
+    rows::layernorm_row(X + row * D, gamma, beta, D, lane, Y + row * D, mean, rstd);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -273,7 +232,7 @@ __global__ __launch_bounds__(256) void k_gemm(const float* __restrict__ A, const
             const int c = n0 + tx * 4 + j;
             if (c >= N) continue;
             float v = acc[i][j] + bias[c];
-            if (GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));   // exact erf GELU (F.gelu default)
+            if (GELU) v = gelu_exact(v);                                           // F.gelu default
             if (RESIDUAL) v += Cm[r * N + c];
             Cm[r * N + c] = v;
         }
@@ -376,9 +335,7 @@ static int transpose_into(const float* W, float* Wt, int N, int K, hipStream_t s
 int pack_generic(const Dims& d, const PackedLayout& pl, const dygnn_dygformer_weights* w, float* packed, hipStream_t s) {
     DYGNN_REQUIRE(w->cooc_w0 && w->cooc_b0 && w->cooc_w1 && w->cooc_b1, "pack: null co-occurrence weights");
     DYGNN_REQUIRE(d.C <= 1024, "pack: channel_embedding_dim too large");
-    hipLaunchKernelGGL(k_cooc_lut, dim3(d.lut_rows), dim3(((d.C + 63) / 64) * 64), 0, s, w->cooc_w0, w->cooc_b0, w->cooc_w1,
-                       w->cooc_b1, d.C, d.lut_rows, packed + pl.lut);
-    DYGNN_LAUNCH_CHECK();
+    if (int rc = cooc_table_device(w, d.lut_rows, d.C, packed + pl.lut, nullptr, s)) return rc;
     const float* pw[4] = {w->proj_node_w, w->proj_edge_w, w->proj_time_w, w->proj_cooc_w};
     const int K[4] = {d.P * d.Fn, d.P * d.Fe, d.P * d.Ft, d.P * d.C};
     for (int c = 0; c < 4; ++c)
@@ -398,6 +355,12 @@ static int launch_gemm(const float* A, const float* Wt, const float* bias, float
                        const CallDims* cd, int64_t G, hipStream_t s) {
     hipLaunchKernelGGL((k_gemm<GELU, RES>), dim3((unsigned)ceil_div(M, 64), (unsigned)ceil_div(N, 64)), dim3(256), 0, s, A, Wt, bias,
                        C, M, N, K, Tmax, cd, G);
+    DYGNN_LAUNCH_CHECK();
+    return DYGNN_OK;
+}
+
+int cooc_table_device(const dygnn_dygformer_weights* w, int rows, int C, float* lut, float* hid, hipStream_t s) {
+    hipLaunchKernelGGL(k_cooc_table, dim3((unsigned)rows), dim3(64), C * sizeof(float), s, w->cooc_w0, w->cooc_b0, w->cooc_w1, w->cooc_b1, C, lut, hid);
     DYGNN_LAUNCH_CHECK();
     return DYGNN_OK;
 }

@@ -12,9 +12,10 @@
 // kernels this file dispatches to are in dygformer_fused3_train.hip (forward) and dygformer_fused3_bwd.hip (backward).
 #include <cstdlib>
 #include "dygformer_layout.h"
+#include "dygformer_rows.h"
 #include "gemm.h"
-#include "dropout.h"
 #include "time_encoding.h"
+#include "train_elements.h"
 
 namespace dygnn {
 
@@ -22,27 +23,14 @@ namespace train {
 
 using f4 = __attribute__((ext_vector_type(4))) float;
 
-// ---- dropout: counter-based, identical in forward and backward (dropout.h) ----------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---- LayerNorm rows (eps 1e-5, biased variance; models/DyGFormer.py:438-439) ---------------------------------------
 __global__ __launch_bounds__(256) void k_ln_fwd(const float* __restrict__ X, const float* __restrict__ gamma, const float* __restrict__ beta, int64_t M,
                                                   int D, float* __restrict__ Y, float* __restrict__ mean_o, float* __restrict__ rstd_o) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
-    const float* x = X + row * D;
-    float s = 0.f;
-    for (int k = lane; k < D; k += 64) s += x[k];
-    const float mean = wave_sum(s) / (float)D;
-    float v = 0.f;
-    for (int k = lane; k < D; k += 64) { const float d = x[k] - mean; v = fmaf(d, d, v); }
-    const float rstd = 1.0f / sqrtf(wave_sum(v) / (float)D + 1e-5f);
-    for (int k = lane; k < D; k += 64) Y[row * D + k] = (x[k] - mean) * rstd * gamma[k] + beta[k];
+    float mean, rstd;
+    rows::layernorm_row(X + row * D, gamma, beta, D, lane, Y + row * D, mean, rstd);
     if (lane == 0) { mean_o[row] = mean; rstd_o[row] = rstd; }
 }
 // dX[row] += LN'(dY) ; dgamma += sum dY*xhat ; dbeta += sum dY.  A lane owns columns lane, lane+64, ...: its partial sums over the
@@ -115,8 +103,7 @@ __global__ __launch_bounds__(256) void k_softmax_fwd(const float* __restrict__ S
     const float* s = S + row * T;
     float mx = -INFINITY;
     for (int j = lane; j < T; j += 64) mx = fmaxf(mx, s[j]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    mx = wave_max(mx);
     float sum = 0.f;
     for (int j = lane; j < T; j += 64) sum += expf(s[j] - mx);
     const float inv = 1.0f / wave_sum(sum);
@@ -140,32 +127,6 @@ __global__ __launch_bounds__(256) void k_softmax_bwd(float* __restrict__ dPd, co
     }
 }
 
-// ---- element-wise pieces ------------------------------------------------------------------------------------------------
-__global__ void k_gelu_drop_fwd(const float* __restrict__ Hpre, int64_t n, Drop dr, uint32_t site, float* __restrict__ Hact) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float v = Hpre[i];
-    Hact[i] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)) * dr.mask(site, (uint64_t)i);       // F.gelu, DyGFormer.py:458
-}
-__global__ void k_gelu_drop_bwd(float* __restrict__ dH, const float* __restrict__ Hpre, int64_t n, Drop dr, uint32_t site) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float v = Hpre[i];
-    const float cdf = 0.5f * (1.0f + erff(v * 0.70710678118654752440f));
-    const float pdf = 0.39894228040143267794f * expf(-0.5f * v * v);
-    dH[i] = dH[i] * dr.mask(site, (uint64_t)i) * (cdf + v * pdf);
-}
-// Xout = Xin + dropout(Y)
-__global__ void k_drop_add_fwd(const float* __restrict__ Xin, const float* __restrict__ Y, int64_t n, Drop dr, uint32_t site, float* __restrict__ Xout) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) Xout[i] = Xin[i] + Y[i] * dr.mask(site, (uint64_t)i);
-}
-// dY = dXout * mask
-__global__ void k_drop_bwd(const float* __restrict__ dXout, int64_t n, Drop dr, uint32_t site, float* __restrict__ dY) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dY[i] = dXout[i] * dr.mask(site, (uint64_t)i);
-}
-
 // ---- embedding inputs: windows, co-occurrence counts, patch matrices -----------------------------------------------------
 struct EmbedArgs {
     const int64_t* indptr; const int32_t* nbr; const int32_t* eid; const double* ts;
@@ -185,30 +146,9 @@ __global__ __launch_bounds__(256) void k_embed_inputs(const EmbedArgs a) {
     int32_t* c0 = reinterpret_cast<int32_t*>(dts + S);
     int32_t* c1 = c0 + S;
     const int64_t b = blockIdx.x;
-    const double t = a.times[b];
-    for (int p = threadIdx.x; p < S; p += 256) {           // pad_sequences, DyGFormer.py:228-245
-        const bool is_dst = p >= a.Ss;
-        const int j = is_dst ? p - a.Ss : p;
-        const int64_t q = is_dst ? a.B + b : b;
-        const int32_t len = a.hist_len[q];
-        const int32_t m = len < a.L - 1 ? len : a.L - 1;
-        int32_t id = 0, e = 0;
-        float tn = 0.f;
-        if (j == 0) { const int64_t qid = is_dst ? a.dst[b] : a.src[b]; id = qid < 0 || qid >= a.num_nodes ? 0 : (int32_t)qid; tn = (float)t; }
-        else if (j <= m) { const int64_t pos = a.end_pos[q] - m + (j - 1); id = a.nbr[pos]; e = a.eid[pos]; tn = (float)a.ts[pos]; }
-        ids[p] = id; eids[p] = e; dts[p] = (float)(t - (double)tn);
-    }
-    __syncthreads();
-    for (int p = threadIdx.x; p < S; p += 256) {           // count_nodes_appearances, DyGFormer.py:337-393
-        const int32_t v = ids[p];
-        int32_t cs = 0, cdn = 0;
-        for (int q = 0; q < a.Ss; ++q) cs += (ids[q] == v);
-        for (int q = a.Ss; q < S; ++q) cdn += (ids[q] == v);
-        if (v == 0) { cs = 0; cdn = 0; }
-        c0[p] = cs; c1[p] = cdn;
-        if (blockIdx.y == 0) { a.ids[b * S + p] = v; a.dts[b * S + p] = dts[p]; a.c0[b * S + p] = cs; a.c1[b * S + p] = cdn; }
-    }
-    __syncthreads();
+    rows::fill_windows(rows::Csr{a.nbr, a.eid, a.ts, a.num_nodes}, a.src, a.dst, a.times, a.hist_len, a.end_pos, a.B, b, a.Ss, a.Sd, a.L, ids, eids, dts, c0, c1);
+    if (blockIdx.y == 0)                                    // the meta arrays the backward pass reads
+        for (int p = threadIdx.x; p < S; p += 256) { a.ids[b * S + p] = ids[p]; a.dts[b * S + p] = dts[p]; a.c0[b * S + p] = c0[p]; a.c1[b * S + p] = c1[p]; }
     // the patch matrices: the workgroups (b, 0 .. gridDim.y-1) of a pair share its tokens (each rebuilt the 128-position window
     // above, which is cheap); node / edge rows move as float4
     const int tok0 = (int)((int64_t)a.T * blockIdx.y / gridDim.y), ntok = (int)((int64_t)a.T * (blockIdx.y + 1) / gridDim.y) - tok0;
@@ -233,24 +173,11 @@ __global__ __launch_bounds__(256) void k_embed_inputs(const EmbedArgs a) {
         const int64_t row = b * a.T + tok;
         if (k < Kt) {
             const int pp = p0 + k / a.Ft, f = k % a.Ft;
-            a.Pt[row * Kt + k] = ids[pp] == 0 ? 0.f : cosf(fmaf(dts[pp], a.time_w[f], a.time_b[f]));                 // modules.py:37, DyGFormer.py:266
+            a.Pt[row * Kt + k] = rows::time_feature(ids[pp], dts[pp], a.time_w, a.time_b, f);
             continue;
         }
         k -= Kt;
-        { const int pp = p0 + k / a.C, f = k % a.C; a.Pc[row * Kc + k] = a.lut[(size_t)c0[pp] * a.C + f] + a.lut[(size_t)c1[pp] * a.C + f]; }
-    }
-}
-// f(c) = W1 relu(W0 c + b0) + b1 for c = 0 .. rows-1 (DyGFormer.py:332-335); hidden activations kept for the backward pass
-__global__ void k_lut_fwd(const float* __restrict__ w0, const float* __restrict__ b0, const float* __restrict__ w1, const float* __restrict__ b1,
-                          int rows, int C, float* __restrict__ lut, float* __restrict__ hid) {
-    const int c = blockIdx.x;
-    extern __shared__ float h[];
-    for (int j = threadIdx.x; j < C; j += blockDim.x) { h[j] = fmaxf(fmaf(w0[j], (float)c, b0[j]), 0.f); hid[c * C + j] = h[j]; }
-    __syncthreads();
-    for (int j = threadIdx.x; j < C; j += blockDim.x) {
-        float acc = b1[j];
-        for (int k = 0; k < C; ++k) acc = fmaf(w1[j * C + k], h[k], acc);
-        lut[c * C + j] = acc;
+        { const int pp = p0 + k / a.C, f = k % a.C; a.Pc[row * Kc + k] = rows::cooc_feature(a.lut, a.C, c0[pp], c1[pp], f); }
     }
 }
 // time-encoder gradients from dPt [M][P*Ft]: pre = w dt + b, d cos = -sin(pre).  One workgroup per pair, thread = column k = pp * Ft + f of
@@ -436,203 +363,200 @@ static int supported(const Dims& d) {
         DYGNN_LAUNCH_CHECK();                                                                                       \
     } while (0)
 
-}  // namespace train
-}  // namespace dygnn
-
-using namespace dygnn;
-using namespace dygnn::train;
-
-extern "C" size_t dygnn_dygformer_train_workspace_bytes(const dygnn_dygformer_config* cfg, int64_t batch) {
-    if (check_config(cfg) != DYGNN_OK || batch < 0) return 0;
-    const Dims d = make_dims(*cfg);
-    if (supported(d) != DYGNN_OK) return 0;
-    return make_plan(d, batch).total;
+// ---- one call -----------------------------------------------------------------------------------------------------------
+// What both entry points derive from their arguments: the sizes, the plan and the typed view of the workspace.
+struct Call {
+    Dims d;
+    Plan p;
+    char* ws;
+    hipStream_t s;
+    Drop dr;
+    int64_t B, M;                  // pairs; token rows M = B * T
+    int Ss, Sd, S, Ts, T;          // this call's padded lengths (set_lengths)
+    float scale;                   // 1 / sqrt(head dim)
+    float* F32(size_t off) const { return reinterpret_cast<float*>(ws + off); }
+    int32_t* I32(size_t off) const { return reinterpret_cast<int32_t*>(ws + off); }
+    void set_lengths(int ss, int sd) { Ss = ss; Sd = sd; S = ss + sd; Ts = ss / d.P; T = S / d.P; M = B * T; }
+};
+// config -> Dims, or why this path refuses it
+static int train_dims(const dygnn_dygformer_config* cfg, Dims& d) {
+    if (int rc = check_config(cfg)) return rc;
+    d = make_dims(*cfg);
+    return supported(d);
+}
+static int make_call(const Dims& d, int64_t batch, float dropout_p, uint64_t seed, void* workspace, size_t workspace_bytes, dygnn_stream_t stream,
+                     const char* who, Call& c) {
+    c.d = d;
+    c.p = make_plan(d, batch);
+    if (workspace_bytes < c.p.total) { set_error("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, c.p.total); return DYGNN_E_WORKSPACE; }
+    c.ws = static_cast<char*>(workspace);
+    c.s = as_stream(stream);
+    c.dr = make_drop(dropout_p, seed);
+    c.B = batch;
+    c.scale = (float)sqrt(1.0 / (double)d.hd);
+    return DYGNN_OK;
 }
 
-extern "C" int dygnn_dygformer_train_forward(const dygnn_dygformer_config* cfg, const dygnn_dygformer_weights* w, const dygnn_csr* csr,
-                                             const float* node_feat, const float* edge_feat, const int64_t* src, const int64_t* dst,
-                                             const double* times, int64_t batch, float dropout_p, uint64_t seed, float* out_src, float* out_dst,
-                                             void* workspace, size_t workspace_bytes, int32_t* seq_lens_host, const void* packed, dygnn_stream_t stream) {
-    if (int rc = check_config(cfg)) return rc;
-    const Dims d = make_dims(*cfg);
-    if (int rc = supported(d)) return rc;
-    DYGNN_REQUIRE(w && csr && csr->indptr && node_feat && edge_feat, "train_forward: null pointer");
-    DYGNN_REQUIRE(batch > 0 && src && dst && times && out_src && out_dst && workspace && seq_lens_host, "train_forward: bad arguments");
-    DYGNN_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "train_forward: dropout must be in [0, 1)");
-    const Plan p = make_plan(d, batch);
-    if (workspace_bytes < p.total) { set_error("train_forward: workspace too small (%zu < %zu bytes)", workspace_bytes, p.total); return DYGNN_E_WORKSPACE; }
-    hipStream_t s = as_stream(stream);
-    char* ws = static_cast<char*>(workspace);
-    auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto I32 = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
-    const int64_t B = batch;
-    // window lengths -> this call's padded lengths (one host sync: they size every product below)
-    if (int rc = window_lengths_device(d, csr, src, dst, times, B, B, ws, p.wl, s)) return rc;
-    // the padded lengths size every product below.  seq_lens_host = {0, 0}: read them back here (one host synchronisation of this
-    // stream); non-zero: the caller already knows them (e.g. from dygnn_window_lengths on a side stream) and the call stays asynchronous
-    if (seq_lens_host[0] <= 0 || seq_lens_host[1] <= 0) {
-        CallDims cd;
-        DYGNN_HIP(hipMemcpyAsync(&cd, ws + p.wl.dims, sizeof(CallDims), hipMemcpyDeviceToHost, s));
-        DYGNN_HIP(hipStreamSynchronize(s));
-        seq_lens_host[0] = cd.S_s; seq_lens_host[1] = cd.S_d;
-    }
-    const int Ss = seq_lens_host[0], Sd = seq_lens_host[1];
-    DYGNN_REQUIRE(Ss % d.P == 0 && Sd % d.P == 0 && Ss <= d.Smax && Sd <= d.Smax, "train_forward: bad sequence lengths");
-    const int Ts = Ss / d.P, T = (Ss + Sd) / d.P, S = Ss + Sd;
-    const int64_t M = B * T;
-    const int D = d.D, C = d.C, H = d.H, hd = d.hd;
-    const Drop dr = make_drop(dropout_p, seed);
-    // co-occurrence LUT of this step's weights
-    hipLaunchKernelGGL(k_lut_fwd, dim3((unsigned)(S + 1)), dim3(64), C * sizeof(float), s, w->cooc_w0, w->cooc_b0, w->cooc_w1, w->cooc_b1, S + 1, C,
-                       F32(p.lut), F32(p.hid));
+// Which blocks of this call run as fused kernels (dygformer_fused3_train.hip, dygformer_fused3_bwd.hip).  `packed` = the kernel-ready copy of the
+// CURRENT weights (dygnn_dygformer_pack / dygnn_dygformer_repack; it holds the backward fragment streams too).  NULL, DYGNN_TRAIN_UNFUSED (read on
+// every call) or a shape the fused kernels do not take: the product-by-product path.
+struct Path { bool forward, ffn_bwd, attn_bwd; };
+static Path choose_path(const Call& c, const void* packed) {
+    const uint64_t M = (uint64_t)c.M, BH = (uint64_t)c.B * c.d.H, T = (uint64_t)c.T;
+    Path p;
+    p.ffn_bwd = packed != nullptr && fused3_supported(c.d) && M * 4 * c.d.D < (1ull << 32) && !getenv("DYGNN_TRAIN_UNFUSED");
+    p.forward = p.ffn_bwd && BH * T * T < (1ull << 32);
+    p.attn_bwd = p.ffn_bwd && c.T <= 128 && c.d.H == 2;
+    return p;
+}
+
+// ---- forward ------------------------------------------------------------------------------------------------------------
+// the co-occurrence table of this step's weights, then the windows' meta arrays and the four patch matrices (both paths)
+static int embed_inputs(const Call& c, const dygnn_dygformer_weights* w, const dygnn_csr* csr, const float* node_feat, const float* edge_feat,
+                        const int64_t* src, const int64_t* dst, const double* times) {
+    const Dims& d = c.d;
+    const Plan& p = c.p;
+    hipStream_t s = c.s;
+    if (int rc = cooc_table_device(w, c.S + 1, d.C, c.F32(p.lut), c.F32(p.hid), s)) return rc;
+    EmbedArgs ea{csr->indptr, csr->nbr, csr->eid, csr->ts, src, dst, times, reinterpret_cast<const int32_t*>(c.ws + p.wl.hist_len),
+                 reinterpret_cast<const int64_t*>(c.ws + p.wl.end_pos), node_feat, edge_feat, w->time_w, w->time_b, c.F32(p.lut), c.B, c.Ss, c.Sd, c.Ts, c.T, d.P,
+                 d.L, d.Fn, d.Fe, d.Ft, d.C, c.I32(p.ids), c.I32(p.c0), c.I32(p.c1), c.F32(p.dts), c.F32(p.Pn), c.F32(p.Pe), c.F32(p.Pt), c.F32(p.Pc), csr->num_nodes};
+    hipLaunchKernelGGL(k_embed_inputs, dim3((unsigned)c.B, (unsigned)(c.T >= 8 ? 8 : 1)), dim3(256), (size_t)5 * c.S * 4, s, ea);
     DYGNN_LAUNCH_CHECK();
-    EmbedArgs ea{csr->indptr, csr->nbr, csr->eid, csr->ts, src, dst, times, reinterpret_cast<const int32_t*>(ws + p.wl.hist_len),
-                 reinterpret_cast<const int64_t*>(ws + p.wl.end_pos), node_feat, edge_feat, w->time_w, w->time_b, F32(p.lut), B, Ss, Sd, Ts, T, d.P, d.L,
-                 d.Fn, d.Fe, d.Ft, C, I32(p.ids), I32(p.c0), I32(p.c1), F32(p.dts), F32(p.Pn), F32(p.Pe), F32(p.Pt), F32(p.Pc), csr->num_nodes};
-    hipLaunchKernelGGL(k_embed_inputs, dim3((unsigned)B, (unsigned)(T >= 8 ? 8 : 1)), dim3(256), (size_t)5 * S * 4, s, ea);
-    DYGNN_LAUNCH_CHECK();
-    // The fused forward (dygformer_fused3_train.hip, TR = true): one kernel from the windows to the embeddings that also writes every activation
-    // the backward pass reads into this Plan's buffers.  `packed` = the kernel-ready copy of the CURRENT weights (dygnn_dygformer_pack /
-    // dygnn_dygformer_repack); NULL, or a shape the fused kernel does not take: the product-by-product path below.
-    if (packed != nullptr && fused3_supported(d) && (uint64_t)M * 4 * D < (1ull << 32) && (uint64_t)B * H * T * T < (1ull << 32) && !getenv("DYGNN_TRAIN_UNFUSED")) {
-        TrainOut tr{};
-        for (int l = 0; l <= d.NL; ++l) tr.X[l] = F32(p.X[l]);
-        for (int l = 0; l < d.NL; ++l) {
-            const auto& L = p.layer[l];
-            tr.layer[l] = TrainOut::L{F32(L.xn0), F32(L.m0), F32(L.r0), F32(L.qkv), F32(L.P), F32(L.Pd), F32(L.oa), F32(L.x1), F32(L.xn1), F32(L.m1), F32(L.r1),
-                                      F32(L.hpre), F32(L.hact)};
-        }
-        tr.pooled = F32(p.pooled);
-        tr.dr = dr;
-        return forward_fused3_train(d, make_packed_layout(d), w, static_cast<const float*>(packed), csr, node_feat, edge_feat, src, dst, times, B, F32(p.lut),
-                                    out_src, out_dst, ws, p.wl, tr, s);
+    return DYGNN_OK;
+}
+// The fused forward (dygformer_fused3_train.hip, TR = true): one kernel from the windows to the embeddings that also writes every activation
+// the backward pass reads into this Plan's buffers.
+static int forward_fused(const Call& c, const dygnn_dygformer_weights* w, const void* packed, const dygnn_csr* csr, const float* node_feat,
+                         const float* edge_feat, const int64_t* src, const int64_t* dst, const double* times, float* out_src, float* out_dst) {
+    const Plan& p = c.p;
+    TrainOut tr{};
+    for (int l = 0; l <= c.d.NL; ++l) tr.X[l] = c.F32(p.X[l]);
+    for (int l = 0; l < c.d.NL; ++l) {
+        const auto& L = p.layer[l];
+        tr.layer[l] = TrainOut::L{c.F32(L.xn0), c.F32(L.m0), c.F32(L.r0), c.F32(L.qkv), c.F32(L.P), c.F32(L.Pd), c.F32(L.oa), c.F32(L.x1), c.F32(L.xn1),
+                                  c.F32(L.m1), c.F32(L.r1), c.F32(L.hpre), c.F32(L.hact)};
     }
+    tr.pooled = c.F32(p.pooled);
+    tr.dr = c.dr;
+    return forward_fused3_train(c.d, make_packed_layout(c.d), w, static_cast<const float*>(packed), csr, node_feat, edge_feat, src, dst, times, c.B,
+                                c.F32(p.lut), out_src, out_dst, c.ws, p.wl, tr, c.s);
+}
+// encoder layer l, product by product (DyGFormer.py:418-461): X[l] -> X[l + 1], every intermediate kept
+static int layer_forward_unfused(const Call& c, const dygnn_encoder_layer_weights& Lw, int l) {
+    const auto& L = c.p.layer[l];
+    hipStream_t s = c.s;
+    const int64_t B = c.B, M = c.M;
+    const int D = c.d.D, H = c.d.H, hd = c.d.hd, T = c.T;
+    const Drop& dr = c.dr;
+    auto F32 = [&](size_t off) { return c.F32(off); };
+    const float* Xin = F32(c.p.X[l]);
+    hipLaunchKernelGGL(k_ln_fwd, dim3((unsigned)ceil_div(M, 4)), dim3(256), 0, s, Xin, Lw.norm0_weight, Lw.norm0_bias, M, D, F32(L.xn0), F32(L.m0), F32(L.r0));
+    DYGNN_LAUNCH_CHECK();
+    if (int rc = mm(s, F32(L.xn0), D, false, Lw.in_proj_weight, D, true, F32(L.qkv), 3 * D, (int)M, 3 * D, D, MmOpt().bias(Lw.in_proj_bias))) return rc;
+    // S_bh = scale * Q_bh K_bh^T ; batch z = b*H + h
+    if (int rc = mm(s, F32(L.qkv), 3 * D, false, F32(L.qkv) + D, 3 * D, true, F32(L.S), T, T, T, hd,
+                    MmOpt().alpha(c.scale).batched((int)(B * H), H).strideA((int64_t)T * 3 * D, hd).strideB((int64_t)T * 3 * D, hd).strideC((int64_t)H * T * T, (int64_t)T * T))) return rc;
+    hipLaunchKernelGGL(k_softmax_fwd, dim3((unsigned)ceil_div(B * H * T, 4)), dim3(256), 0, s, F32(L.S), B * H * T, T, dr, (uint32_t)(4 * l + 0), F32(L.P), F32(L.Pd));
+    DYGNN_LAUNCH_CHECK();
+    // Oa_bh = Pd_bh V_bh
+    if (int rc = mm(s, F32(L.Pd), T, false, F32(L.qkv) + 2 * D, 3 * D, false, F32(L.oa), D, T, hd, T,
+                    MmOpt().batched((int)(B * H), H).strideA((int64_t)H * T * T, (int64_t)T * T).strideB((int64_t)T * 3 * D, hd).strideC((int64_t)T * D, hd))) return rc;
+    if (int rc = mm(s, F32(L.oa), D, false, Lw.out_proj_weight, D, true, F32(L.ao), D, (int)M, D, D, MmOpt().bias(Lw.out_proj_bias))) return rc;
+    EW(k_drop_add, M * D, Xin, F32(L.ao), M * D, dr, (uint32_t)(4 * l + 1), F32(L.x1));                                             // DyGFormer.py:456
+    hipLaunchKernelGGL(k_ln_fwd, dim3((unsigned)ceil_div(M, 4)), dim3(256), 0, s, F32(L.x1), Lw.norm1_weight, Lw.norm1_bias, M, D, F32(L.xn1), F32(L.m1), F32(L.r1));
+    DYGNN_LAUNCH_CHECK();
+    if (int rc = mm(s, F32(L.xn1), D, false, Lw.ffn0_weight, D, true, F32(L.hpre), 4 * D, (int)M, 4 * D, D, MmOpt().bias(Lw.ffn0_bias))) return rc;
+    EW(k_gelu_drop, M * 4 * D, F32(L.hpre), M * 4 * D, dr, (uint32_t)(4 * l + 2), F32(L.hact));                                     // :458
+    if (int rc = mm(s, F32(L.hact), 4 * D, false, Lw.ffn1_weight, 4 * D, true, F32(L.f2), D, (int)M, D, 4 * D, MmOpt().bias(Lw.ffn1_bias))) return rc;
+    EW(k_drop_add, M * D, F32(L.x1), F32(L.f2), M * D, dr, (uint32_t)(4 * l + 3), F32(c.p.X[l + 1]));                               // :460
+    return DYGNN_OK;
+}
+// the whole forward, product by product: patch projections, the encoder layers, per-side token means, output layer
+static int forward_unfused(const Call& c, const dygnn_dygformer_weights* w, float* out_src, float* out_dst) {
+    const Dims& d = c.d;
+    const Plan& p = c.p;
+    hipStream_t s = c.s;
+    const int64_t B = c.B, M = c.M;
+    const int D = d.D, C = d.C;
     // projections (DyGFormer.py:148-157): X0[:, 50ch : 50ch+50] = P_ch . W_ch^T + b_ch
     const float* PW[4] = {w->proj_node_w, w->proj_edge_w, w->proj_time_w, w->proj_cooc_w};
     const float* PB[4] = {w->proj_node_b, w->proj_edge_b, w->proj_time_b, w->proj_cooc_b};
     const size_t PM[4] = {p.Pn, p.Pe, p.Pt, p.Pc};
     const int PK[4] = {d.P * d.Fn, d.P * d.Fe, d.P * d.Ft, d.P * C};
     for (int ch = 0; ch < 4; ++ch)
-        if (int rc = mm(s, F32(PM[ch]), PK[ch], false, PW[ch], PK[ch], true, F32(p.X[0]) + ch * C, D, (int)M, C, PK[ch], MmOpt().bias(PB[ch]))) return rc;
-    const float scale = (float)sqrt(1.0 / (double)hd);
-    for (int l = 0; l < d.NL; ++l) {
-        const dygnn_encoder_layer_weights& Lw = w->layers[l];
-        const auto& L = p.layer[l];
-        const float* Xin = F32(p.X[l]);
-        hipLaunchKernelGGL(k_ln_fwd, dim3((unsigned)ceil_div(M, 4)), dim3(256), 0, s, Xin, Lw.norm0_weight, Lw.norm0_bias, M, D, F32(L.xn0), F32(L.m0), F32(L.r0));
-        DYGNN_LAUNCH_CHECK();
-        if (int rc = mm(s, F32(L.xn0), D, false, Lw.in_proj_weight, D, true, F32(L.qkv), 3 * D, (int)M, 3 * D, D, MmOpt().bias(Lw.in_proj_bias))) return rc;
-        // S_bh = scale * Q_bh K_bh^T ; batch z = b*H + h
-        if (int rc = mm(s, F32(L.qkv), 3 * D, false, F32(L.qkv) + D, 3 * D, true, F32(L.S), T, T, T, hd,
-                        MmOpt().alpha(scale).batched((int)(B * H), H).strideA((int64_t)T * 3 * D, hd).strideB((int64_t)T * 3 * D, hd).strideC((int64_t)H * T * T, (int64_t)T * T))) return rc;
-        hipLaunchKernelGGL(k_softmax_fwd, dim3((unsigned)ceil_div(B * H * T, 4)), dim3(256), 0, s, F32(L.S), B * H * T, T, dr, (uint32_t)(4 * l + 0), F32(L.P), F32(L.Pd));
-        DYGNN_LAUNCH_CHECK();
-        // Oa_bh = Pd_bh V_bh
-        if (int rc = mm(s, F32(L.Pd), T, false, F32(L.qkv) + 2 * D, 3 * D, false, F32(L.oa), D, T, hd, T,
-                        MmOpt().batched((int)(B * H), H).strideA((int64_t)H * T * T, (int64_t)T * T).strideB((int64_t)T * 3 * D, hd).strideC((int64_t)T * D, hd))) return rc;
-        if (int rc = mm(s, F32(L.oa), D, false, Lw.out_proj_weight, D, true, F32(L.ao), D, (int)M, D, D, MmOpt().bias(Lw.out_proj_bias))) return rc;
-        EW(k_drop_add_fwd, M * D, Xin, F32(L.ao), M * D, dr, (uint32_t)(4 * l + 1), F32(L.x1));                                         // DyGFormer.py:456
-        hipLaunchKernelGGL(k_ln_fwd, dim3((unsigned)ceil_div(M, 4)), dim3(256), 0, s, F32(L.x1), Lw.norm1_weight, Lw.norm1_bias, M, D, F32(L.xn1), F32(L.m1), F32(L.r1));
-        DYGNN_LAUNCH_CHECK();
-        if (int rc = mm(s, F32(L.xn1), D, false, Lw.ffn0_weight, D, true, F32(L.hpre), 4 * D, (int)M, 4 * D, D, MmOpt().bias(Lw.ffn0_bias))) return rc;
-        EW(k_gelu_drop_fwd, M * 4 * D, F32(L.hpre), M * 4 * D, dr, (uint32_t)(4 * l + 2), F32(L.hact));                                 // :458
-        if (int rc = mm(s, F32(L.hact), 4 * D, false, Lw.ffn1_weight, 4 * D, true, F32(L.f2), D, (int)M, D, 4 * D, MmOpt().bias(Lw.ffn1_bias))) return rc;
-        EW(k_drop_add_fwd, M * D, F32(L.x1), F32(L.f2), M * D, dr, (uint32_t)(4 * l + 3), F32(p.X[l + 1]));                             // :460
-    }
-    hipLaunchKernelGGL(k_pool_fwd, dim3((unsigned)B), dim3(256), 0, s, F32(p.X[d.NL]), B, Ts, T, D, F32(p.pooled));
+        if (int rc = mm(s, c.F32(PM[ch]), PK[ch], false, PW[ch], PK[ch], true, c.F32(p.X[0]) + ch * C, D, (int)M, C, PK[ch], MmOpt().bias(PB[ch]))) return rc;
+    for (int l = 0; l < d.NL; ++l)
+        if (int rc = layer_forward_unfused(c, w->layers[l], l)) return rc;
+    hipLaunchKernelGGL(k_pool_fwd, dim3((unsigned)B), dim3(256), 0, s, c.F32(p.X[d.NL]), B, c.Ts, c.T, D, c.F32(p.pooled));
     DYGNN_LAUNCH_CHECK();
-    if (int rc = mm(s, F32(p.pooled), D, false, w->output_w, D, true, out_src, d.Fn, (int)B, d.Fn, D, MmOpt().bias(w->output_b))) return rc;
-    if (int rc = mm(s, F32(p.pooled) + B * D, D, false, w->output_w, D, true, out_dst, d.Fn, (int)B, d.Fn, D, MmOpt().bias(w->output_b))) return rc;
-    return DYGNN_OK;
+    if (int rc = mm(s, c.F32(p.pooled), D, false, w->output_w, D, true, out_src, d.Fn, (int)B, d.Fn, D, MmOpt().bias(w->output_b))) return rc;
+    return mm(s, c.F32(p.pooled) + B * D, D, false, w->output_w, D, true, out_dst, d.Fn, (int)B, d.Fn, D, MmOpt().bias(w->output_b));
 }
 
-extern "C" int dygnn_dygformer_backward(const dygnn_dygformer_config* cfg, const dygnn_dygformer_weights* w, const dygnn_dygformer_weights* grads,
-                                        const float* grad_out_src, const float* grad_out_dst, int64_t batch, float dropout_p, uint64_t seed,
-                                        const int32_t* seq_lens_host, void* workspace, size_t workspace_bytes, const void* packed, dygnn_stream_t stream) {
-    if (int rc = check_config(cfg)) return rc;
-    const Dims d = make_dims(*cfg);
-    if (int rc = supported(d)) return rc;
-    DYGNN_REQUIRE(w && grads && grad_out_src && grad_out_dst && workspace && seq_lens_host && batch > 0, "backward: bad arguments");
-    const Plan p = make_plan(d, batch);
-    if (workspace_bytes < p.total) { set_error("backward: workspace too small (%zu < %zu bytes)", workspace_bytes, p.total); return DYGNN_E_WORKSPACE; }
-    hipStream_t s = as_stream(stream);
-    char* ws = static_cast<char*>(workspace);
-    auto F32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    auto I32 = [&](size_t off) { return reinterpret_cast<int32_t*>(ws + off); };
-    auto G = [](const float* q) { return const_cast<float*>(q); };        // the grads struct reuses the weights layout; its buffers are written
-    const int64_t B = batch;
-    const int Ss = seq_lens_host[0], Sd = seq_lens_host[1], S = Ss + Sd;
-    DYGNN_REQUIRE(Ss > 0 && Sd > 0 && Ss % d.P == 0 && Sd % d.P == 0 && S <= 2 * d.Smax, "backward: bad sequence lengths");
-    const int Ts = Ss / d.P, T = S / d.P;
-    const int64_t M = B * T;
-    const int D = d.D, C = d.C, H = d.H, hd = d.hd, Fn = d.Fn;
-    const Drop dr = make_drop(dropout_p, seed);
-    const float scale = (float)sqrt(1.0 / (double)hd);
-    // output layer: out = pooled W^T + b over both sides
-    if (int rc = mm(s, grad_out_src, Fn, true, F32(p.pooled), D, false, G(grads->output_w), D, Fn, D, (int)B)) return rc;
-    if (int rc = mm(s, grad_out_dst, Fn, true, F32(p.pooled) + B * D, D, false, G(grads->output_w), D, Fn, D, (int)B, MmOpt().beta(1.f))) return rc;
-    if (int rc = colsum_atomic(s, grad_out_src, Fn, B, Fn, G(grads->output_b))) return rc;
-    if (int rc = colsum_atomic(s, grad_out_dst, Fn, B, Fn, G(grads->output_b))) return rc;
-    if (int rc = mm(s, grad_out_src, Fn, false, w->output_w, D, false, F32(p.dpool), D, (int)B, D, Fn)) return rc;
-    if (int rc = mm(s, grad_out_dst, Fn, false, w->output_w, D, false, F32(p.dpool) + B * D, D, (int)B, D, Fn)) return rc;
-    float* dX = F32(p.dX);
-    EW(k_pool_bwd, M * D, F32(p.dpool), B, Ts, T, D, dX);
-    DwList dw;
-    // `packed` = the kernel-ready copy of the weights the forward ran with (it holds the backward fragment streams too): the FFN blocks run fused
-    const bool fused = packed != nullptr && fused3_supported(d) && (uint64_t)M * 4 * D < (1ull << 32) && !getenv("DYGNN_TRAIN_UNFUSED");
-    for (int l = d.NL - 1; l >= 0; --l) {
-        const dygnn_encoder_layer_weights& Lw = w->layers[l];
-        const dygnn_encoder_layer_weights& Lg = grads->layers[l];
-        const auto& L = p.layer[l];
-        float* dA = F32(p.dA);          // [M][D] scratch
-        float* dBf = F32(p.dB);         // [M][D] scratch
-        float* dF2 = F32(L.dF2);        // [M][D]   operands of this layer's weight gradients: alive until the grouped launch below
-        float* dH = F32(L.dH);          // [M][4D]
-        float* dAo = F32(L.dAo);        // [M][D]
-        float* dQKV = F32(L.dQKV);      // [M][3D]
-        // X_{l+1} = X1 + drop(F2), F2 = Hact W2^T + b2
-        dw.add(dF2, D, D, F32(L.hact), 4 * D, 4 * D, G(Lg.ffn1_weight), 4 * D, G(Lg.ffn1_bias));                               // dW2 [D][4D], db2
-        dw.add(dH, 4 * D, 4 * D, F32(L.xn1), D, D, G(Lg.ffn0_weight), D, G(Lg.ffn0_bias));                                     // dW1 [4D][D], db1
-        if (fused) {      // the whole block in one kernel (dygformer_fused3_bwd.hip: k_ffn_bwd): dF2, dHpre written for the grouped launch, dX <- dX1 in place
-            if (int rc = ffn_backward_fused3(d, make_packed_layout(d), static_cast<const float*>(packed), l, M, dX, F32(L.hpre), F32(L.x1), F32(L.m1), F32(L.r1), dF2, dH,
-                                             G(Lg.norm1_weight), G(Lg.norm1_bias), dr, s)) return rc;
-        } else {
-            EW(k_drop_bwd, M * D, dX, M * D, dr, (uint32_t)(4 * l + 3), dF2);                                                  // dF2
-            if (int rc = mm(s, dF2, D, false, Lw.ffn1_weight, 4 * D, false, dH, 4 * D, (int)M, 4 * D, D)) return rc;           // dHact
-            EW(k_gelu_drop_bwd, M * 4 * D, dH, F32(L.hpre), M * 4 * D, dr, (uint32_t)(4 * l + 2));                             // dHpre
-            if (int rc = mm(s, dH, 4 * D, false, Lw.ffn0_weight, D, false, dBf, D, (int)M, D, 4 * D)) return rc;                // dxn1
-            hipLaunchKernelGGL(k_ln_bwd, dim3((unsigned)ceil_div(M, 64)), dim3(256), 8 * D * sizeof(float), s, dBf, F32(L.x1), F32(L.m1), F32(L.r1), Lw.norm1_weight, M, D,
-                               dX, G(Lg.norm1_weight), G(Lg.norm1_bias));                                                      // dX is now dX1
-            DYGNN_LAUNCH_CHECK();
-        }
-        // X1 = Xin + drop(Ao), Ao = Oa Wo^T + bo ; Oa_bh = Pd_bh V_bh ; S_bh = scale Q_bh K_bh^T ; [Q | K | V] = LN0(Xin) Win^T + bin
-        dw.add(dAo, D, D, F32(L.oa), D, D, G(Lg.out_proj_weight), D, G(Lg.out_proj_bias));                                     // dWo [D][D], dbo
-        dw.add(dQKV, 3 * D, 3 * D, F32(L.xn0), D, D, G(Lg.in_proj_weight), D, G(Lg.in_proj_bias));                              // dWin [3D][D], dbin
-        if (fused && T <= 128 && H == 2) {      // the whole block in one kernel (dygformer_fused3_bwd.hip: k_attn_bwd): dAo, dQKV written for the grouped launch, dX <- dX_l in place
-            if (int rc = attn_backward_fused3(d, make_packed_layout(d), static_cast<const float*>(packed), l, B, T, dX, F32(p.X[l]), F32(L.m0), F32(L.r0), F32(L.qkv), F32(L.P),
-                                              F32(L.Pd), dAo, dQKV, G(Lg.norm0_weight), G(Lg.norm0_bias), dr, s)) return rc;
-            continue;
-        }
-        EW(k_drop_bwd, M * D, dX, M * D, dr, (uint32_t)(4 * l + 1), dAo);                                                      // dAo
-        if (int rc = mm(s, dAo, D, false, Lw.out_proj_weight, D, false, dBf, D, (int)M, D, D)) return rc;                       // dOa
-        // dV_bh = Pd^T dOa_bh
-        if (int rc = mm(s, F32(L.Pd), T, true, dBf, D, false, dQKV + 2 * D, 3 * D, T, hd, T,
-                        MmOpt().batched((int)(B * H), H).strideA((int64_t)H * T * T, (int64_t)T * T).strideB((int64_t)T * D, hd).strideC((int64_t)T * 3 * D, hd))) return rc;
-        // dPd_bh = dOa_bh V_bh^T  (into the S buffer)
-        if (int rc = mm(s, dBf, D, false, F32(L.qkv) + 2 * D, 3 * D, true, F32(L.S), T, T, T, hd,
-                        MmOpt().batched((int)(B * H), H).strideA((int64_t)T * D, hd).strideB((int64_t)T * 3 * D, hd).strideC((int64_t)H * T * T, (int64_t)T * T))) return rc;
-        hipLaunchKernelGGL(k_softmax_bwd, dim3((unsigned)ceil_div(B * H * T, 4)), dim3(256), 0, s, F32(L.S), F32(L.P), B * H * T, T, dr, (uint32_t)(4 * l + 0));
-        DYGNN_LAUNCH_CHECK();
-        // dQ_bh = scale dS K_bh ; dK_bh = scale dS^T Q_bh
-        if (int rc = mm(s, F32(L.S), T, false, F32(L.qkv) + D, 3 * D, false, dQKV, 3 * D, T, hd, T,
-                        MmOpt().alpha(scale).batched((int)(B * H), H).strideA((int64_t)H * T * T, (int64_t)T * T).strideB((int64_t)T * 3 * D, hd).strideC((int64_t)T * 3 * D, hd))) return rc;
-        if (int rc = mm(s, F32(L.S), T, true, F32(L.qkv), 3 * D, false, dQKV + D, 3 * D, T, hd, T,
-                        MmOpt().alpha(scale).batched((int)(B * H), H).strideA((int64_t)H * T * T, (int64_t)T * T).strideB((int64_t)T * 3 * D, hd).strideC((int64_t)T * 3 * D, hd))) return rc;
-        if (int rc = mm(s, dQKV, 3 * D, false, Lw.in_proj_weight, D, false, dA, D, (int)M, D, 3 * D)) return rc;                // dxn0
-        hipLaunchKernelGGL(k_ln_bwd, dim3((unsigned)ceil_div(M, 64)), dim3(256), 8 * D * sizeof(float), s, dA, F32(p.X[l]), F32(L.m0), F32(L.r0), Lw.norm0_weight, M, D,
-                           dX, G(Lg.norm0_weight), G(Lg.norm0_bias));                                                          // dX is now dX_l
-        DYGNN_LAUNCH_CHECK();
-    }
+// ---- backward -----------------------------------------------------------------------------------------------------------
+// the grads struct reuses the weights layout; its buffers are written
+static float* G(const float* q) { return const_cast<float*>(q); }
+
+// Layer l's four weight gradients take their operands from these buffers in the ONE grouped launch at the end of the pass
+struct LayerGrads { float *dF2, *dH, *dAo, *dQKV; };       // [M][D], [M][4D], [M][D], [M][3D]
+
+// X_{l+1} = X1 + drop(F2), F2 = Hact W2^T + b2, product by product: dF2, dHpre written for the grouped launch, dX <- dX1 in place
+static int ffn_backward_unfused(const Call& c, const dygnn_encoder_layer_weights& Lw, const dygnn_encoder_layer_weights& Lg, int l, float* dX, const LayerGrads& g) {
+    const auto& L = c.p.layer[l];
+    hipStream_t s = c.s;
+    const int64_t M = c.M;
+    const int D = c.d.D;
+    float* dBf = c.F32(c.p.dB);     // [M][D] scratch
+    EW(k_drop_bwd, M * D, dX, M * D, c.dr, (uint32_t)(4 * l + 3), g.dF2);                                                     // dF2
+    if (int rc = mm(s, g.dF2, D, false, Lw.ffn1_weight, 4 * D, false, g.dH, 4 * D, (int)M, 4 * D, D)) return rc;               // dHact
+    EW(k_gelu_drop_bwd, M * 4 * D, g.dH, c.F32(L.hpre), M * 4 * D, c.dr, (uint32_t)(4 * l + 2));                              // dHpre
+    if (int rc = mm(s, g.dH, 4 * D, false, Lw.ffn0_weight, D, false, dBf, D, (int)M, D, 4 * D)) return rc;                     // dxn1
+    hipLaunchKernelGGL(k_ln_bwd, dim3((unsigned)ceil_div(M, 64)), dim3(256), 8 * D * sizeof(float), s, dBf, c.F32(L.x1), c.F32(L.m1), c.F32(L.r1), Lw.norm1_weight, M, D,
+                       dX, G(Lg.norm1_weight), G(Lg.norm1_bias));                                                             // dX is now dX1
+    DYGNN_LAUNCH_CHECK();
+    return DYGNN_OK;
+}
+// X1 = Xin + drop(Ao), Ao = Oa Wo^T + bo ; Oa_bh = Pd_bh V_bh ; S_bh = scale Q_bh K_bh^T ; [Q | K | V] = LN0(Xin) Win^T + bin, product by product:
+// dAo, dQKV written for the grouped launch, dX <- dX_l in place
+static int attn_backward_unfused(const Call& c, const dygnn_encoder_layer_weights& Lw, const dygnn_encoder_layer_weights& Lg, int l, float* dX, const LayerGrads& g) {
+    const auto& L = c.p.layer[l];
+    hipStream_t s = c.s;
+    const int64_t B = c.B, M = c.M;
+    const int D = c.d.D, H = c.d.H, hd = c.d.hd, T = c.T;
+    auto F32 = [&](size_t off) { return c.F32(off); };
+    float *dA = F32(c.p.dA), *dBf = F32(c.p.dB);      // [M][D] scratch
+    float* dQKV = g.dQKV;
+    EW(k_drop_bwd, M * D, dX, M * D, c.dr, (uint32_t)(4 * l + 1), g.dAo);                                                     // dAo
+    if (int rc = mm(s, g.dAo, D, false, Lw.out_proj_weight, D, false, dBf, D, (int)M, D, D)) return rc;                        // dOa
+    // dV_bh = Pd^T dOa_bh
+    if (int rc = mm(s, F32(L.Pd), T, true, dBf, D, false, dQKV + 2 * D, 3 * D, T, hd, T,
+                    MmOpt().batched((int)(B * H), H).strideA((int64_t)H * T * T, (int64_t)T * T).strideB((int64_t)T * D, hd).strideC((int64_t)T * 3 * D, hd))) return rc;
+    // dPd_bh = dOa_bh V_bh^T  (into the S buffer)
+    if (int rc = mm(s, dBf, D, false, F32(L.qkv) + 2 * D, 3 * D, true, F32(L.S), T, T, T, hd,
+                    MmOpt().batched((int)(B * H), H).strideA((int64_t)T * D, hd).strideB((int64_t)T * 3 * D, hd).strideC((int64_t)H * T * T, (int64_t)T * T))) return rc;
+    hipLaunchKernelGGL(k_softmax_bwd, dim3((unsigned)ceil_div(B * H * T, 4)), dim3(256), 0, s, F32(L.S), F32(L.P), B * H * T, T, c.dr, (uint32_t)(4 * l + 0));
+    DYGNN_LAUNCH_CHECK();
+    // dQ_bh = scale dS K_bh ; dK_bh = scale dS^T Q_bh
+    if (int rc = mm(s, F32(L.S), T, false, F32(L.qkv) + D, 3 * D, false, dQKV, 3 * D, T, hd, T,
+                    MmOpt().alpha(c.scale).batched((int)(B * H), H).strideA((int64_t)H * T * T, (int64_t)T * T).strideB((int64_t)T * 3 * D, hd).strideC((int64_t)T * 3 * D, hd))) return rc;
+    if (int rc = mm(s, F32(L.S), T, true, F32(L.qkv), 3 * D, false, dQKV + D, 3 * D, T, hd, T,
+                    MmOpt().alpha(c.scale).batched((int)(B * H), H).strideA((int64_t)H * T * T, (int64_t)T * T).strideB((int64_t)T * 3 * D, hd).strideC((int64_t)T * 3 * D, hd))) return rc;
+    if (int rc = mm(s, dQKV, 3 * D, false, Lw.in_proj_weight, D, false, dA, D, (int)M, D, 3 * D)) return rc;                   // dxn0
+    hipLaunchKernelGGL(k_ln_bwd, dim3((unsigned)ceil_div(M, 64)), dim3(256), 8 * D * sizeof(float), s, dA, F32(c.p.X[l]), F32(L.m0), F32(L.r0), Lw.norm0_weight, M, D,
+                       dX, G(Lg.norm0_weight), G(Lg.norm0_bias));                                                             // dX is now dX_l
+    DYGNN_LAUNCH_CHECK();
+    return DYGNN_OK;
+}
+// From dX = dX0 down to the parameters below the encoder: the grouped weight-gradient launch (`dw` holds the layers' problems already), the
+// projections, the time encoder and the co-occurrence encoder.
+static int inputs_backward(const Call& c, const dygnn_dygformer_weights* w, const dygnn_dygformer_weights* grads, float* dX, DwList& dw) {
+    const Dims& d = c.d;
+    const Plan& p = c.p;
+    hipStream_t s = c.s;
+    const int64_t B = c.B, M = c.M;
+    const int D = d.D, C = d.C, S = c.S;
+    auto F32 = [&](size_t off) { return c.F32(off); };
     // projections: X0[:, ch] = P_ch W_ch^T + b_ch.  dX0 is split into channel blocks (aligned operands); the four projection weight gradients
     // join the grouped launch where their shapes allow, the rest takes the general path
     const float* PW[4] = {w->proj_node_w, w->proj_edge_w, w->proj_time_w, w->proj_cooc_w};
@@ -654,14 +578,14 @@ extern "C" int dygnn_dygformer_backward(const dygnn_dygformer_config* cfg, const
     }
     // time encoder
     if (int rc = mm(s, dXc + (size_t)2 * M * Cp, Cp, false, PW[2], PK[2], false, F32(p.dPt), PK[2], (int)M, PK[2], C, MmOpt().a_kpad())) return rc;
-    hipLaunchKernelGGL(k_time_bwd, dim3((unsigned)B), dim3(256), 2 * d.Ft * sizeof(float), s, F32(p.dPt), I32(p.ids), F32(p.dts), w->time_w, w->time_b, B, Ss, Sd, Ts, T,
-                       d.P, d.Ft, G(grads->time_w), G(grads->time_b));
+    hipLaunchKernelGGL(k_time_bwd, dim3((unsigned)B), dim3(256), 2 * d.Ft * sizeof(float), s, F32(p.dPt), c.I32(p.ids), F32(p.dts), w->time_w, w->time_b, B, c.Ss, c.Sd,
+                       c.Ts, c.T, d.P, d.Ft, G(grads->time_w), G(grads->time_b));
     DYGNN_LAUNCH_CHECK();
     // co-occurrence encoder
     if (int rc = mm(s, dXc + (size_t)3 * M * Cp, Cp, false, PW[3], PK[3], false, F32(p.dPc), PK[3], (int)M, PK[3], C, MmOpt().a_kpad())) return rc;
     DYGNN_HIP(hipMemsetAsync(F32(p.dlut), 0, (size_t)(S + 1) * C * sizeof(float), s));
     hipLaunchKernelGGL(k_cooc_bwd, dim3((unsigned)ceil_div(B, kPairsPerWg)), dim3(256), (size_t)kCoocGroups * kCoocRows * C * sizeof(float), s, F32(p.dPc),
-                       I32(p.c0), I32(p.c1), B, Ss, Sd, Ts, T, d.P, C, F32(p.dlut));
+                       c.I32(p.c0), c.I32(p.c1), B, c.Ss, c.Sd, c.Ts, c.T, d.P, C, F32(p.dlut));
     DYGNN_LAUNCH_CHECK();
     float* dh = F32(p.dPc);        // dPc is dead now: reuse its head for dh [S+1][C]
     hipLaunchKernelGGL(k_lut_bwd_hidden, dim3((unsigned)(S + 1)), dim3(64), 0, s, F32(p.dlut), F32(p.hid), w->cooc_w1, C, dh);
@@ -671,4 +595,92 @@ extern "C" int dygnn_dygformer_backward(const dygnn_dygformer_config* cfg, const
                        G(grads->cooc_b0), G(grads->cooc_w1), G(grads->cooc_b1));
     DYGNN_LAUNCH_CHECK();
     return DYGNN_OK;
+}
+
+}  // namespace train
+}  // namespace dygnn
+
+using namespace dygnn;
+using namespace dygnn::train;
+
+extern "C" size_t dygnn_dygformer_train_workspace_bytes(const dygnn_dygformer_config* cfg, int64_t batch) {
+    if (check_config(cfg) != DYGNN_OK || batch < 0) return 0;
+    const Dims d = make_dims(*cfg);
+    if (supported(d) != DYGNN_OK) return 0;
+    return make_plan(d, batch).total;
+}
+
+extern "C" int dygnn_dygformer_train_forward(const dygnn_dygformer_config* cfg, const dygnn_dygformer_weights* w, const dygnn_csr* csr,
+                                             const float* node_feat, const float* edge_feat, const int64_t* src, const int64_t* dst,
+                                             const double* times, int64_t batch, float dropout_p, uint64_t seed, float* out_src, float* out_dst,
+                                             void* workspace, size_t workspace_bytes, int32_t* seq_lens_host, const void* packed, dygnn_stream_t stream) {
+    Dims d;
+    if (int rc = train_dims(cfg, d)) return rc;
+    DYGNN_REQUIRE(w && csr && csr->indptr && node_feat && edge_feat, "train_forward: null pointer");
+    DYGNN_REQUIRE(batch > 0 && src && dst && times && out_src && out_dst && workspace && seq_lens_host, "train_forward: bad arguments");
+    DYGNN_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "train_forward: dropout must be in [0, 1)");
+    Call c;
+    if (int rc = make_call(d, batch, dropout_p, seed, workspace, workspace_bytes, stream, "train_forward", c)) return rc;
+    if (int rc = window_lengths_device(d, csr, src, dst, times, c.B, c.B, c.ws, c.p.wl, c.s)) return rc;
+    // the padded lengths size every product below.  seq_lens_host = {0, 0}: read them back here (one host synchronisation of this
+    // stream); non-zero: the caller already knows them (e.g. from dygnn_window_lengths on a side stream) and the call stays asynchronous
+    if (seq_lens_host[0] <= 0 || seq_lens_host[1] <= 0) {
+        CallDims cd;
+        DYGNN_HIP(hipMemcpyAsync(&cd, c.ws + c.p.wl.dims, sizeof(CallDims), hipMemcpyDeviceToHost, c.s));
+        DYGNN_HIP(hipStreamSynchronize(c.s));
+        seq_lens_host[0] = cd.S_s; seq_lens_host[1] = cd.S_d;
+    }
+    const int Ss = seq_lens_host[0], Sd = seq_lens_host[1];
+    DYGNN_REQUIRE(Ss % d.P == 0 && Sd % d.P == 0 && Ss <= d.Smax && Sd <= d.Smax, "train_forward: bad sequence lengths");
+    c.set_lengths(Ss, Sd);
+    if (int rc = embed_inputs(c, w, csr, node_feat, edge_feat, src, dst, times)) return rc;
+    if (choose_path(c, packed).forward) return forward_fused(c, w, packed, csr, node_feat, edge_feat, src, dst, times, out_src, out_dst);
+    return forward_unfused(c, w, out_src, out_dst);
+}
+
+extern "C" int dygnn_dygformer_backward(const dygnn_dygformer_config* cfg, const dygnn_dygformer_weights* w, const dygnn_dygformer_weights* grads,
+                                        const float* grad_out_src, const float* grad_out_dst, int64_t batch, float dropout_p, uint64_t seed,
+                                        const int32_t* seq_lens_host, void* workspace, size_t workspace_bytes, const void* packed, dygnn_stream_t stream) {
+    Dims d;
+    if (int rc = train_dims(cfg, d)) return rc;
+    DYGNN_REQUIRE(w && grads && grad_out_src && grad_out_dst && workspace && seq_lens_host && batch > 0, "backward: bad arguments");
+    Call c;
+    if (int rc = make_call(d, batch, dropout_p, seed, workspace, workspace_bytes, stream, "backward", c)) return rc;
+    const int Ss = seq_lens_host[0], Sd = seq_lens_host[1];
+    DYGNN_REQUIRE(Ss > 0 && Sd > 0 && Ss % d.P == 0 && Sd % d.P == 0 && Ss + Sd <= 2 * d.Smax, "backward: bad sequence lengths");
+    c.set_lengths(Ss, Sd);
+    const Path path = choose_path(c, packed);
+    const Plan& p = c.p;
+    hipStream_t s = c.s;
+    const int64_t B = c.B, M = c.M;
+    const int D = d.D, Fn = d.Fn;
+    // output layer: out = pooled W^T + b over both sides
+    if (int rc = mm(s, grad_out_src, Fn, true, c.F32(p.pooled), D, false, G(grads->output_w), D, Fn, D, (int)B)) return rc;
+    if (int rc = mm(s, grad_out_dst, Fn, true, c.F32(p.pooled) + B * D, D, false, G(grads->output_w), D, Fn, D, (int)B, MmOpt().beta(1.f))) return rc;
+    if (int rc = colsum_atomic(s, grad_out_src, Fn, B, Fn, G(grads->output_b))) return rc;
+    if (int rc = colsum_atomic(s, grad_out_dst, Fn, B, Fn, G(grads->output_b))) return rc;
+    if (int rc = mm(s, grad_out_src, Fn, false, w->output_w, D, false, c.F32(p.dpool), D, (int)B, D, Fn)) return rc;
+    if (int rc = mm(s, grad_out_dst, Fn, false, w->output_w, D, false, c.F32(p.dpool) + B * D, D, (int)B, D, Fn)) return rc;
+    float* dX = c.F32(p.dX);
+    EW(k_pool_bwd, M * D, c.F32(p.dpool), B, c.Ts, c.T, D, dX);
+    DwList dw;
+    const PackedLayout pl = make_packed_layout(d);
+    const float* pk = static_cast<const float*>(packed);
+    for (int l = d.NL - 1; l >= 0; --l) {
+        const dygnn_encoder_layer_weights& Lw = w->layers[l];
+        const dygnn_encoder_layer_weights& Lg = grads->layers[l];
+        const auto& L = p.layer[l];
+        const LayerGrads g{c.F32(L.dF2), c.F32(L.dH), c.F32(L.dAo), c.F32(L.dQKV)};
+        dw.add(g.dF2, D, D, c.F32(L.hact), 4 * D, 4 * D, G(Lg.ffn1_weight), 4 * D, G(Lg.ffn1_bias));                             // dW2 [D][4D], db2
+        dw.add(g.dH, 4 * D, 4 * D, c.F32(L.xn1), D, D, G(Lg.ffn0_weight), D, G(Lg.ffn0_bias));                                   // dW1 [4D][D], db1
+        if (int rc = path.ffn_bwd ? ffn_backward_fused3(d, pl, pk, l, M, dX, c.F32(L.hpre), c.F32(L.x1), c.F32(L.m1), c.F32(L.r1), g.dF2, g.dH, G(Lg.norm1_weight),
+                                                        G(Lg.norm1_bias), c.dr, s)
+                                  : ffn_backward_unfused(c, Lw, Lg, l, dX, g)) return rc;
+        dw.add(g.dAo, D, D, c.F32(L.oa), D, D, G(Lg.out_proj_weight), D, G(Lg.out_proj_bias));                                   // dWo [D][D], dbo
+        dw.add(g.dQKV, 3 * D, 3 * D, c.F32(L.xn0), D, D, G(Lg.in_proj_weight), D, G(Lg.in_proj_bias));                            // dWin [3D][D], dbin
+        if (int rc = path.attn_bwd ? attn_backward_fused3(d, pl, pk, l, B, c.T, dX, c.F32(p.X[l]), c.F32(L.m0), c.F32(L.r0), c.F32(L.qkv), c.F32(L.P), c.F32(L.Pd), g.dAo,
+                                                          g.dQKV, G(Lg.norm0_weight), G(Lg.norm0_bias), c.dr, s)
+                                   : attn_backward_unfused(c, Lw, Lg, l, dX, g)) return rc;
+    }
+    return inputs_backward(c, w, grads, dX, dw);
 }

@@ -110,25 +110,6 @@ __device__ inline unsigned long long load_key(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ inline unsigned long long wave_max(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(v, o, kWave);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-__device__ inline unsigned long long wave_add(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-__device__ inline double wave_add(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-
 // Phase 1 of an insert: place the keys of positions [first, last) that the table does not hold yet (see the file comment).
 __global__ __launch_bounds__(kBlock) void k_claim(Table t, const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
                                                   const double* __restrict__ times, int64_t first, int64_t last) {
@@ -169,7 +150,7 @@ __global__ __launch_bounds__(kBlock) void k_claim(Table t, const int64_t* __rest
             }
         }
     }
-    placed = wave_add(placed);
+    placed = wave_sum(placed);
     tmax = wave_max(tmax);
     if ((threadIdx.x & (kWave - 1)) == 0) {
         if (placed) atomicAdd(&t.hdr->distinct, placed);
@@ -222,7 +203,7 @@ __global__ __launch_bounds__(kBlock) void k_window_partial(Table t, const double
             if ((int64_t)a < H && (int64_t)b < H) acc += (times[b] - times[a]) / (double)(n - 1);
         }
     }
-    acc = wave_add(acc);
+    acc = wave_sum(acc);
     if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -236,7 +217,7 @@ __global__ __launch_bounds__(kBlock) void k_window_partial(Table t, const double
 __global__ __launch_bounds__(kWave) void k_window_final(Table t, int nblocks) {
     double acc = 0.0;
     for (int b = threadIdx.x; b < nblocks; b += kWave) acc += t.partial[b];
-    acc = wave_add(acc);
+    acc = wave_sum(acc);
     if (threadIdx.x == 0) {
         const double average = acc / (double)t.hdr->distinct;
         t.hdr->S = acc;

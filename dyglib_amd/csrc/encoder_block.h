@@ -12,7 +12,6 @@ using tile::kThreads;
 using tile::kWaves;
 using tile::round16;
 using tile::wave_product;
-using tile::wave_sum;
 using tile::z4;
 
 constexpr int kFfnChunk = 64;     // hidden columns in LDS at a time

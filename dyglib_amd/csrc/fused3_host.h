@@ -79,6 +79,9 @@ inline int const_qkv_env() {
 // dygformer_generic.hip
 int window_lengths_device(const Dims& d, const dygnn_csr* csr, const int64_t* src, const int64_t* dst, const double* times,
                           int64_t B, int64_t G, char* ws, const WorkspaceLayout& wl, hipStream_t s);
+// the co-occurrence table lut [rows][C], row c = W1 relu(W0 c + b0) + b1 (DyGFormer.py:332-335); hid (may be NULL) [rows][C] = the hidden
+// rows relu(W0 c + b0), which the training backward reads
+int cooc_table_device(const dygnn_dygformer_weights* w, int rows, int C, float* lut, float* hid, hipStream_t s);
 // dygformer_fused3_pack.hip
 bool fused3_supported(const Dims& d);
 size_t fused3_packed_floats(const Dims& d);

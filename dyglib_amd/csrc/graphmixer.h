@@ -1,5 +1,5 @@
 // What the GraphMixer training path (graphmixer_train.hip) shares with the inference forward (graphmixer.hip): the constants, the CSR view
-// and history search, the exact GELU, the configuration check and the launches of the two kernels both paths run as they are.
+// and history search, the configuration check and the launches of the two kernels both paths run as they are.
 #pragma once
 #include "common.h"
 
@@ -8,8 +8,6 @@ namespace gm {
 
 constexpr int kMaxTokens = 32;
 constexpr float kLnEps = 1e-5f;
-
-__device__ __forceinline__ float gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }      // nn.GELU(), exact
 
 struct Csr {
     const int64_t* indptr;

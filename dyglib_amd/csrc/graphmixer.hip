@@ -9,6 +9,7 @@
 //
 // Products use the fp32 MFMA tile product of mfma_tile.h.
 #include "common.h"
+#include "gelu_exact.h"
 #include "graphmixer.h"
 #include "mfma_tile.h"
 #include "time_encoding.h"
@@ -24,7 +25,6 @@ using tile::lds_limit;
 using tile::mfma4;
 using tile::round16;
 using tile::wave_product;
-using tile::wave_sum;
 using tile::z4;
 
 constexpr int kFfnRows = 64;      // token rows per workgroup of k_gm_ffn
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(kThreads) void k_gm_token(float* __restrict__ X, co
         for (int i = 0; i < Kh; ++i) {
             float a = b0[i];
             for (int j = 0; j < K; ++j) a = fmaf(W0[i * K + j], T[j * C + ch], a);
-            Hd[i * C + ch] = gelu(a);
+            Hd[i * C + ch] = gelu_exact(a);
         }
         for (int j = 0; j < K; ++j) {
             float a = b1[j];
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(kThreads) void k_gm_ffn(float* __restrict__ X, int6
                 f4 v = z4();
                 if (hcol < hn) {
                     const f4 z = hid[0][mt] + b;
-                    v = f4{gelu(z.x), gelu(z.y), gelu(z.z), gelu(z.w)};
+                    v = f4{gelu_exact(z.x), gelu_exact(z.y), gelu_exact(z.z), gelu_exact(z.w)};
                 }
                 *reinterpret_cast<f4*>(Hc + (16 * mt + c) * ldh + hcol) = v;      // dead columns are zero: stage 2 runs over the whole chunk
             }

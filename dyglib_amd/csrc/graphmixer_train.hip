@@ -25,8 +25,8 @@
 //                                                2 K Kh + Kh + 3 K parameter gradients over the C threads in LDS in a fixed order and writes
 //                                                one partial row per root
 //           k_gmt_ln_fwd / k_gmt_ln_bwd          channel LayerNorm, one wave per row
-//           k_gmt_gelu_drop / k_gmt_hid_bwd      GELU and the site-2 mask; the mask times the exact GELU derivative
-//           k_gmt_res / k_gmt_drop_bwd           site-3 mask and residual; the mask on the gradient
+//           train::k_gelu_drop / k_gelu_drop_bwd GELU and the site-2 mask; the mask times the exact GELU derivative   (train_elements.h: the dense
+//           train::k_drop_add / k_drop_bwd       site-3 mask and residual; the mask on the gradient                   activations are numbered by offset)
 //           k_gmt_cat / k_gmt_bcast              token mean | node part; the mean's gradient / K to the K rows
 //           train::k_colsum_fin (colsum.h)       stage 2 of the fixed-order column sums, shared with the other backbones; into up to six tensors
 // Dense products (channel fc0, fc1, their transposes, output_layer) go through train::mm (fp32 MFMA, gemm.h), a block's two channel weight
@@ -34,30 +34,23 @@
 // two-stage column sums (colsum.h's first stage): those are the same bits run to run.
 #include "colsum.h"
 #include "common.h"
-#include "dropout.h"
 #include "gemm.h"
 #include "graphmixer.h"
 #include "mfma_tile.h"
 #include "time_encoding.h"
+#include "train_elements.h"
 
 namespace dygnn {
 namespace gmt {
 
 using timeenc::cos_time;
 using gm::Csr;
-using gm::gelu;
 using gm::history;
 using gm::kLnEps;
 using gm::kMaxTokens;
-using tile::wave_sum;
 using train::colsum;
 
 constexpr int NV = 4;                 // columns per lane of a row: C <= 256
-
-// d gelu(x) / dx of the exact GELU: Phi(x) + x phi(x)
-__device__ __forceinline__ float dgelu(float x) {
-    return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * (0.3989422804014327f * expf(-0.5f * x * x));
-}
 
 // ---- the gathered token rows (k_gm_proj's sampling and padded-slot rules): TOK [R][C + Ft] ----------------------------------------------------
 __global__ __launch_bounds__(256) void k_gmt_rows(Csr g, const float* __restrict__ edge_feat, const int64_t* __restrict__ nodes,
@@ -127,7 +120,7 @@ __global__ __launch_bounds__(256) void k_gmt_token_fwd(const float* __restrict__
         for (int i = 0; i < Kh; ++i) {
             float a = b0[i];
             for (int j = 0; j < K; ++j) a = fmaf(W0[i * K + j], T[j * C + ch], a);
-            Hd[i * C + ch] = gelu(a) * dr.mask(site, col * Kh + i);
+            Hd[i * C + ch] = gelu_exact(a) * dr.mask(site, col * Kh + i);
         }
         for (int j = 0; j < K; ++j) {
             float a = b1[j];
@@ -181,10 +174,10 @@ __global__ __launch_bounds__(256) void k_gmt_token_bwd(const float* __restrict__
             float a = b0[i];
             for (int j = 0; j < K; ++j) a = fmaf(W0[i * K + j], Y[j * ld + ch], a);
             const float m0 = dr.mask(site, col * Kh + i);
-            HD[i * ld + ch] = gelu(a) * m0;
+            HD[i * ld + ch] = gelu_exact(a) * m0;
             float dh = 0.f;
             for (int j = 0; j < K; ++j) dh = fmaf(W1[j * Kh + i], DO[j * ld + ch], dh);
-            DA[i * ld + ch] = dh * m0 * dgelu(a);
+            DA[i * ld + ch] = dh * m0 * gelu_exact_grad(a);
         }
     }
     __syncthreads();
@@ -310,24 +303,6 @@ __global__ __launch_bounds__(256) void k_gmt_ln_bwd(const float* __restrict__ dy
         const int f = lane + 64 * u;
         if (f < C) dx[r * C + f] = dres[r * C + f] + rstd * ((g[u] - mg) - xh[u] * mgx);
     }
-}
-
-// ---- elementwise: the dense [R][H] and [R][C] activations are numbered as the dropout sites number them (element = offset) -----------------
-__global__ void k_gmt_gelu_drop(const float* __restrict__ hpre, float* __restrict__ hact, int64_t count, train::Drop dr, uint32_t site) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < count) hact[e] = gelu(hpre[e]) * dr.mask(site, (uint64_t)e);
-}
-__global__ void k_gmt_hid_bwd(float* __restrict__ g, const float* __restrict__ hpre, int64_t count, train::Drop dr, uint32_t site) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < count) g[e] = g[e] * dr.mask(site, (uint64_t)e) * dgelu(hpre[e]);
-}
-__global__ void k_gmt_res(const float* __restrict__ x1, const float* __restrict__ t, float* __restrict__ out, int64_t count, train::Drop dr, uint32_t site) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < count) out[e] = t[e] * dr.mask(site, (uint64_t)e) + x1[e];
-}
-__global__ void k_gmt_drop_bwd(const float* __restrict__ g, float* __restrict__ out, int64_t count, train::Drop dr, uint32_t site) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < count) out[e] = g[e] * dr.mask(site, (uint64_t)e);
 }
 
 // Z [n][C + Fn] = [mean over the K tokens | node term + node_feat[v]] (k_gm_out's operand rows, the same sums)
@@ -463,10 +438,10 @@ extern "C" int dygnn_graphmixer_train_forward(const dygnn_graphmixer_config* cfg
                            F32(v.mean), F32(v.rstd));
         DYGNN_LAUNCH_CHECK();
         if (int rc = train::mm(s, F32(v.y), C, false, m.channel_fc0_w, C, true, F32(v.hpre), H, R, H, C, train::MmOpt().bias(m.channel_fc0_b))) return rc;
-        hipLaunchKernelGGL(k_gmt_gelu_drop, dim3(blocks(p.R * H)), dim3(256), 0, s, F32(v.hpre), F32(v.hact), p.R * H, dr, site + 2);
+        hipLaunchKernelGGL(train::k_gelu_drop, dim3(blocks(p.R * H)), dim3(256), 0, s, F32(v.hpre), p.R * H, dr, site + 2, F32(v.hact));
         DYGNN_LAUNCH_CHECK();
         if (int rc = train::mm(s, F32(v.hact), H, false, m.channel_fc1_w, H, true, F32(p.tmp), C, R, C, H, train::MmOpt().bias(m.channel_fc1_b))) return rc;
-        hipLaunchKernelGGL(k_gmt_res, dim3(blocks(p.R * C)), dim3(256), 0, s, F32(v.x1), F32(p.tmp), F32(p.x[l + 1]), p.R * C, dr, site + 3);
+        hipLaunchKernelGGL(train::k_drop_add, dim3(blocks(p.R * C)), dim3(256), 0, s, F32(v.x1), F32(p.tmp), p.R * C, dr, site + 3, F32(p.x[l + 1]));
         DYGNN_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(k_gmt_cat, dim3(blocks(n * (C + Fn))), dim3(256), 0, s, F32(p.x[p.L]), F32(p.term), node_feat, nodes, n, node_rows, K, C, Fn, F32(p.z));
@@ -516,11 +491,11 @@ extern "C" int dygnn_graphmixer_backward(const dygnn_graphmixer_config* cfg, con
         const Layer& v = p.layer[l];
         const uint32_t site = 4u * (uint32_t)l;
         // channel half: site-3 mask, fc1^T, site-2 mask and GELU', fc0^T, LayerNorm
-        hipLaunchKernelGGL(k_gmt_drop_bwd, dim3(blocks(p.R * C)), dim3(256), 0, s, gA, gC, p.R * C, dr, site + 3);
+        hipLaunchKernelGGL(train::k_drop_bwd, dim3(blocks(p.R * C)), dim3(256), 0, s, gA, p.R * C, dr, site + 3, gC);
         DYGNN_LAUNCH_CHECK();
         if (int rc = cs(gC, C, g.channel_fc1_b)) return rc;
         if (int rc = train::mm(s, gC, C, false, m.channel_fc1_w, H, false, dhid, H, R, H, C)) return rc;
-        hipLaunchKernelGGL(k_gmt_hid_bwd, dim3(blocks(p.R * H)), dim3(256), 0, s, dhid, F32(v.hpre), p.R * H, dr, site + 2);
+        hipLaunchKernelGGL(train::k_gelu_drop_bwd, dim3(blocks(p.R * H)), dim3(256), 0, s, dhid, F32(v.hpre), p.R * H, dr, site + 2);
         DYGNN_LAUNCH_CHECK();
         if (int rc = cs(dhid, H, g.channel_fc0_b)) return rc;
         if (int rc = train::mm(s, dhid, H, false, m.channel_fc0_w, C, false, gB, C, R, C, H)) return rc;

@@ -29,17 +29,6 @@ struct Partial {
     unsigned long long npos;
 };
 
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-__device__ inline unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-
 __global__ __launch_bounds__(kBlock) void k_rank_counts(const float* __restrict__ predicts, const float* __restrict__ labels,
                                                         int64_t n, Partial* __restrict__ partials) {
     __shared__ float s_tile[kTile];

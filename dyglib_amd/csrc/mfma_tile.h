@@ -12,11 +12,6 @@ namespace tile {
 using f4 = __attribute__((ext_vector_type(4))) float;
 
 __device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 __device__ __forceinline__ f4 z4() { return f4{0.f, 0.f, 0.f, 0.f}; }
 constexpr int kThreads = 256, kWaves = 4;
 

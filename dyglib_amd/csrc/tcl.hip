@@ -33,7 +33,6 @@ using tile::kWaves;
 using tile::lds_limit;
 using tile::round16;
 using tile::wave_product;
-using tile::wave_sum;
 using tile::z4;
 
 constexpr int kMaxSeq = 64;       // S = K + 1 <= 64: one row of scores per lane set, four row tiles
@@ -196,9 +195,7 @@ __global__ __launch_bounds__(kThreads) void k_tcl_attn(const float* __restrict__
             const int r = wave + kWaves * e;
             if (r >= nq) continue;
             const float s = on ? sc[e] * scale : -INFINITY;
-            float m = s;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+            const float m = wave_max(s);
             const float ex = on ? expf(s - m) : 0.f;
             const float sum = wave_sum(ex);
             Pm[r * LD + lane] = sum > 0.f ? ex / sum : 0.f;         // no valid key: the sequence attends to nothing

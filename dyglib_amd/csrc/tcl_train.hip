@@ -45,7 +45,6 @@ using timeenc::cos_time;
 using tile::f4;
 using tile::mfma4;
 using tile::round16;
-using tile::wave_sum;
 using tile::z4;
 using train::colsum;
 using train::pair_seq;      // the dropout generator's sequence index of side s (train_rows.h)
@@ -102,9 +101,7 @@ __global__ __launch_bounds__(256) void k_tclt_attn_fwd(const float* __restrict__
         const int r = wave + 4 * e;
         if (r >= S) continue;
         const float sv = on ? sc[e] * scale : -INFINITY;
-        float m = sv;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+        const float m = wave_max(sv);
         const float ex = on ? expf(sv - m) : 0.f;
         const float sum = wave_sum(ex);
         const float p = sum > 0.f ? ex / sum : 0.f;

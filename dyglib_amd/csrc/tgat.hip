@@ -273,8 +273,7 @@ __global__ __launch_bounds__(256) void k_tgat_attn_lin(const float* __restrict__
             float sc = vc[0] ? dot4(qh[lane], xv[0]) : 0.f;
 #pragma unroll
             for (int c = 1; c < NCOL; ++c) sc += vc[c] ? dot4(qh[lane + 64 * c], xv[c]) : 0.f;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) sc += __shfl_xor(sc, o, 64);
+            sc = wave_sum(sc);
             if (lane == 0) {
                 sc *= scale;                                              // modules.py:173
                 if (lower_ids[n + r] == 0) sc = -1e10f;                   // modules.py:176-184
@@ -383,16 +382,12 @@ __global__ __launch_bounds__(256) void k_tgat_post(const float* __restrict__ fc_
 #pragma unroll
     for (int u = 0; u < NV; ++u)
         if (lane + kWave * u < Dq) s += x[u];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    const float mean = s / (float)Dq;
+    const float mean = wave_sum(s) / (float)Dq;
     float v = 0.f;
 #pragma unroll
     for (int u = 0; u < NV; ++u)
         if (lane + kWave * u < Dq) { const float d = x[u] - mean; v = fmaf(d, d, v); }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const float rstd = 1.0f / sqrtf(v / (float)Dq + 1e-5f);
+    const float rstd = 1.0f / sqrtf(wave_sum(v) / (float)Dq + 1e-5f);
     float* o = merge_in + i * (Dq + Fn);
 #pragma unroll
     for (int u = 0; u < NV; ++u) {

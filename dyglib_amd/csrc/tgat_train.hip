@@ -29,7 +29,6 @@ namespace tgt {
 
 using f4 = __attribute__((ext_vector_type(4))) float;
 constexpr int NC = 4;                 // float4 columns per lane of an input row: Dkv <= 4 * 64 * 4 = 1024
-using tile::wave_sum;
 
 // TGN: the gradient row of a level-0 node, or NULL where the node passes no gradient on (no pending message; id 0, the padding, never has one)
 __device__ __forceinline__ float* feat0_row(const Feat0Grad& fg, int32_t node, int Fn) {

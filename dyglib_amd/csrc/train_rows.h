@@ -50,12 +50,12 @@ static __global__ __launch_bounds__(256) void k_res_ln(const float* __restrict__
             sum += x[u];
         }
     }
-    const float mean = tile::wave_sum(sum) / (float)d;
+    const float mean = wave_sum(sum) / (float)d;
     float var = 0.f;
 #pragma unroll
     for (int u = 0; u < NV; ++u)
         if (lane + 64 * u < d) { const float c = x[u] - mean; var = fmaf(c, c, var); }
-    const float rstd = 1.0f / sqrtf(tile::wave_sum(var) / (float)d + kLnEps);
+    const float rstd = 1.0f / sqrtf(wave_sum(var) / (float)d + kLnEps);
     if (lane == 0) { mean_o[r] = mean; rstd_o[r] = rstd; }
 #pragma unroll
     for (int u = 0; u < NV; ++u) {
@@ -92,8 +92,8 @@ static __global__ __launch_bounds__(256) void k_res_ln_bwd(const float* __restri
             sgx = fmaf(g[u], xh[u], sgx);
         }
     }
-    sg = tile::wave_sum(sg) / (float)d;
-    sgx = tile::wave_sum(sgx) / (float)d;
+    sg = wave_sum(sg) / (float)d;
+    sgx = wave_sum(sgx) / (float)d;
 #pragma unroll
     for (int u = 0; u < NV; ++u) {
         const int f = lane + 64 * u;

@@ -14,7 +14,20 @@ import re
 import subprocess
 import sys
 
-RENAMED = {"_ZN5dygnn4attn8cos_libmEf": "_ZN5dygnn7timeenc8cos_libmEf"}      # old name -> new name of a symbol that moved namespace
+RENAMED = {      # old name -> new name of a symbol that moved namespace or file
+    "_ZN5dygnn4attn8cos_libmEf": "_ZN5dygnn7timeenc8cos_libmEf",
+    # the element kernels of dygformer_train.hip and graphmixer_train.hip -> train_elements.h (a static copy per including source)
+    "_ZN5dygnn5train15k_gelu_drop_fwdEPKflNS0_4DropEjPf": "_ZN5dygnn5trainL11k_gelu_dropEPKflNS0_4DropEjPf",
+    "_ZN5dygnn5train15k_gelu_drop_bwdEPfPKflNS0_4DropEj": "_ZN5dygnn5trainL15k_gelu_drop_bwdEPfPKflNS0_4DropEj",
+    "_ZN5dygnn5train14k_drop_add_fwdEPKfS2_lNS0_4DropEjPf": "_ZN5dygnn5trainL10k_drop_addEPKfS2_lNS0_4DropEjPf",
+    "_ZN5dygnn5train10k_drop_bwdEPKflNS0_4DropEjPf": "_ZN5dygnn5trainL10k_drop_bwdEPKflNS0_4DropEjPf",
+    "_ZN5dygnn3gmt15k_gmt_gelu_dropEPKfPflNS_5train4DropEj": "_ZN5dygnn5trainL11k_gelu_dropEPKflNS0_4DropEjPf",
+    "_ZN5dygnn3gmt13k_gmt_hid_bwdEPfPKflNS_5train4DropEj": "_ZN5dygnn5trainL15k_gelu_drop_bwdEPfPKflNS0_4DropEj",
+    "_ZN5dygnn3gmt9k_gmt_resEPKfS2_PflNS_5train4DropEj": "_ZN5dygnn5trainL10k_drop_addEPKfS2_lNS0_4DropEjPf",
+    "_ZN5dygnn3gmt14k_gmt_drop_bwdEPKfPflNS_5train4DropEj": "_ZN5dygnn5trainL10k_drop_bwdEPKflNS0_4DropEjPf",
+    # dygformer_train.hip's table kernel -> dygformer_generic.hip's one (k_cooc_lut is gone)
+    "_ZN5dygnn5train9k_lut_fwdEPKfS2_S2_S2_iiPfS3_": "_ZN5dygnn12k_cooc_tableEPKfS1_S1_S1_iPfS2_",
+}
 
 
 def functions(tree):
