@@ -150,10 +150,21 @@ __global__ __launch_bounds__(256) void k_embed_inputs(const EmbedArgs a) {
     if (blockIdx.y == 0)                                    // the meta arrays the backward pass reads
         for (int p = threadIdx.x; p < S; p += 256) { a.ids[b * S + p] = ids[p]; a.dts[b * S + p] = dts[p]; a.c0[b * S + p] = c0[p]; a.c1[b * S + p] = c1[p]; }
     // the patch matrices: the workgroups (b, 0 .. gridDim.y-1) of a pair share its tokens (each rebuilt the 128-position window
-    // above, which is cheap); node / edge rows move as float4
+    // above, which is cheap); node / edge rows move as float4 where a table row is whole float4s (F % 4 == 0: every address is then 16-byte
+    // aligned and no float4 crosses a row), element by element otherwise
     const int tok0 = (int)((int64_t)a.T * blockIdx.y / gridDim.y), ntok = (int)((int64_t)a.T * (blockIdx.y + 1) / gridDim.y) - tok0;
     const int Kn = a.P * a.Fn, Ke = a.P * a.Fe, Kt = a.P * a.Ft, Kc = a.P * a.C;
-    const int Kn4 = Kn >> 2, KV = Kn4 + (Ke >> 2), KS = Kt + Kc;
+    const int Kn4 = (a.Fn & 3) ? 0 : Kn >> 2, Ke4 = (a.Fe & 3) ? 0 : Ke >> 2, KV = Kn4 + Ke4, KS = Kt + Kc;
+    const int Kn1 = (a.Fn & 3) ? Kn : 0, K1 = Kn1 + ((a.Fe & 3) ? Ke : 0);
+    for (int idx = threadIdx.x; idx < ntok * K1; idx += 256) {
+        const int tok = tok0 + idx / K1;
+        int k = idx % K1;
+        const int p0 = tok < a.Ts ? tok * a.P : a.Ss + (tok - a.Ts) * a.P;
+        const int64_t row = b * a.T + tok;
+        if (k < Kn1) { a.Pn[row * Kn + k] = a.node_feat[(size_t)ids[p0 + k / a.Fn] * a.Fn + k % a.Fn]; continue; }
+        k -= Kn1;
+        a.Pe[row * Ke + k] = a.edge_feat[(size_t)eids[p0 + k / a.Fe] * a.Fe + k % a.Fe];
+    }
     for (int idx = threadIdx.x; idx < ntok * KV; idx += 256) {
         const int tok = tok0 + idx / KV, k4 = idx % KV;
         const int p0 = tok < a.Ts ? tok * a.P : a.Ss + (tok - a.Ts) * a.P;
@@ -344,7 +355,8 @@ static Plan make_plan(const Dims& d, int64_t B) {
         auto& L = p.layer[l];
         L.dF2 = take(M * d.D * F); L.dH = take(M * 4 * d.D * F); L.dAo = take(M * d.D * F); L.dQKV = take(M * 3 * d.D * F);
     }
-    p.dpool = take((size_t)2 * B * d.D * F); p.dPt = take(M * d.P * d.Ft * F); p.dPc = take(M * d.P * d.C * F); p.dlut = take((size_t)(S + 1) * d.C * F);
+    // dPc [M][P C] = B S rows of C; the backward pass reuses it for dh [S + 1][C], which is one row more when B = 1
+    p.dpool = take((size_t)2 * B * d.D * F); p.dPt = take(M * d.P * d.Ft * F); p.dPc = take((M * d.P > S + 1 ? M * d.P : S + 1) * d.C * F); p.dlut = take((size_t)(S + 1) * d.C * F);
     p.total = o;
     return p;
 }

@@ -32,6 +32,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from .dropout import Drop
+
 
 # ======================================================================================
 # L1: time-sorted adjacency  (utils/utils.py:283-302 builder, :73-110 constructor)
@@ -197,10 +199,30 @@ def cooccurrence_features(params, counts: torch.Tensor) -> torch.Tensor:
     return h.sum(dim=2)
 
 
-def encoder_layer(params, layer: int, x: torch.Tensor, num_heads: int) -> torch.Tensor:
-    """models/DyGFormer.py:442-461 in eval mode (dropout = identity).  Pre-LN; the attention is
-    nn.MultiheadAttention's explicit path (need_weights=True default): packed in-proj, q scaled by
-    1/sqrt(head_dim) before q.k^T, full softmax with NO mask, out-proj; exact-erf GELU FFN."""
+class TrainDropout:
+    """The training path's dropout for dygformer_forward: probability p (float32, as the C ABI takes it) and seed (the model's
+    `_fixed_dropout_seed`), masks from oracle/dropout.py as dyglib_amd/csrc/dropout.h documents them: site = 4 * layer + {0: softmax
+    output [B][H][T][T], 1: attention output after the out-projection [B][T][D], 2: gelu(h) [B][T][4D], 3: FFN output [B][T][D]}, element
+    index = the element's offset in that dense row-major tensor (T = T_src + T_dst of the call), kept elements times float32 1/(1-p).
+    `dropped[site]` records the share of zeros of every mask drawn."""
+
+    def __init__(self, p: float, seed: int):
+        self.gen = Drop(p, seed)
+        self.dropped = {}
+
+    def mask(self, site: int, shape) -> torch.Tensor:
+        """the multipliers of site `site` for a dense tensor of `shape`: a constant, so autograd flows through the product"""
+        n = int(np.prod(shape))
+        m = self.gen.mask(site, np.arange(n, dtype=np.int64)).reshape(tuple(shape))
+        self.dropped[site] = float((m == 0).mean()) if n else 0.0
+        return torch.from_numpy(m)
+
+
+def encoder_layer(params, layer: int, x: torch.Tensor, num_heads: int, dropout: Optional[TrainDropout] = None) -> torch.Tensor:
+    """models/DyGFormer.py:442-461.  Pre-LN; the attention is nn.MultiheadAttention's explicit path (need_weights=True default): packed
+    in-proj, q scaled by 1/sqrt(head_dim) before q.k^T, full softmax with NO mask, out-proj; exact-erf GELU FFN.  dropout=None: eval
+    mode (dropout = identity); a TrainDropout: train mode with the training path's masks at the four sites of :429 and :456-460."""
+    drop = (lambda t, site: t) if dropout is None else (lambda t, site: t * dropout.mask(4 * layer + site, t.shape))
     p = f"transformers.{layer}."
     B, T, D = x.shape
     hd = D // num_heads
@@ -210,22 +232,23 @@ def encoder_layer(params, layer: int, x: torch.Tensor, num_heads: int) -> torch.
     q = q.reshape(B, T, num_heads, hd).transpose(1, 2) * math.sqrt(1.0 / float(hd))
     k = k.reshape(B, T, num_heads, hd).transpose(1, 2)
     v = v.reshape(B, T, num_heads, hd).transpose(1, 2)
-    att = torch.softmax(q @ k.transpose(-2, -1), dim=-1)
+    att = drop(torch.softmax(q @ k.transpose(-2, -1), dim=-1), 0)
     o = (att @ v).transpose(1, 2).reshape(B, T, D)
     o = F.linear(o, _t(params, p + "multi_head_attention.out_proj.weight"), _t(params, p + "multi_head_attention.out_proj.bias"))
-    x = x + o                                                                                   # :456
+    x = x + drop(o, 1)                                                                          # :456
     h = F.layer_norm(x, (D,), _t(params, p + "norm_layers.1.weight"), _t(params, p + "norm_layers.1.bias"), 1e-5)
-    h = F.gelu(F.linear(h, _t(params, p + "linear_layers.0.weight"), _t(params, p + "linear_layers.0.bias")))
+    h = drop(F.gelu(F.linear(h, _t(params, p + "linear_layers.0.weight"), _t(params, p + "linear_layers.0.bias"))), 2)
     h = F.linear(h, _t(params, p + "linear_layers.1.weight"), _t(params, p + "linear_layers.1.bias"))
-    return x + h                                                                                # :460
+    return x + drop(h, 3)                                                                       # :460
 
 
 def dygformer_forward(params: Dict[str, np.ndarray], node_feat: np.ndarray, edge_feat: np.ndarray,
                       adj: OracleAdjacency, src_ids: np.ndarray, dst_ids: np.ndarray, times: np.ndarray,
                       patch_size: int, max_input_sequence_length: int, num_heads: int = 2,
-                      num_layers: int = 2, taps: Optional[dict] = None):
+                      num_layers: int = 2, taps: Optional[dict] = None, dropout: Optional[TrainDropout] = None):
     """models/DyGFormer.py:68-194.  Returns (src_emb[B,F_n], dst_emb[B,F_n]) as float32 tensors.
-    `taps`, when given, receives intermediate results for stage-level parity tests."""
+    `taps`, when given, receives intermediate results for stage-level parity tests.  `dropout` (a TrainDropout): the encoder layers in
+    train mode with the training path's masks."""
     P, L = patch_size, max_input_sequence_length
     node_t = node_feat if isinstance(node_feat, torch.Tensor) else torch.from_numpy(node_feat)
     edge_t = edge_feat if isinstance(edge_feat, torch.Tensor) else torch.from_numpy(edge_feat)
@@ -260,7 +283,7 @@ def dygformer_forward(params: Dict[str, np.ndarray], node_feat: np.ndarray, edge
         taps.update(src_ids=s_id, src_eids=s_e, src_times=s_t, dst_ids=d_id, dst_eids=d_e, dst_times=d_t,
                     src_counts=c_s, dst_counts=c_d, encoder_input=x.clone(), layer_outputs=[])
     for l in range(num_layers):                                                                 # :177-178
-        x = encoder_layer(params, l, x, num_heads)
+        x = encoder_layer(params, l, x, num_heads, dropout)
         if taps is not None:
             taps["layer_outputs"].append(x.clone())
     s = x[:, :Ts].mean(dim=1)                                                                   # :181-187
